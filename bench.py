@@ -14,10 +14,15 @@ line; it exits non-zero if the number of ranks that took part differs from --gpu
 Other workloads behind the same protocol / JSON schema:
     --resolution 256 --dtype bf16      BASELINE configs[1] (16-bit activation storage)
     --model comodgan-512 --batch 16    BASELINE configs[4]
-The default N = 1 run appends them as "secondary" (and the exact-fp32-MFMA variant of the primary workload as
-"value_exact_f32"), so that one driver run times everything; --no-secondary skips that.
 
-Extra objects on the line:
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, ...); --dump-outputs DIR also writes the output of the last timed step as DIR/output.npy (float32; a fixed,
+seeded sample of the images when the whole output exceeds 64 MB), on inputs that are the same from run to run.
+Everything else is measured with --full only: the N = 1 run with --full appends the other workloads as "secondary" (and
+the exact-fp32-MFMA variant of the primary workload as "value_exact_f32"), so that one driver run times everything
+(--no-secondary skips that), and adds the objects below, the batch-1 latency and the one-rank RCCL leg.
+
+Extra objects on the line (--full):
   roofline     dominant kernel (largest share of GPU time), measured live with hipEvent pairs around every launch on the
                launch stream (one stream, whole-batch launches): achieved = algorithmic flops (or bytes) of its launches /
                their summed duration, against the MI355X peak of the binding resource.
@@ -74,7 +79,14 @@ def parse(argv=None):
     ap.add_argument("--io", type=str, default="f32", choices=["f32", "u8"],
                     help="migan: u8 = uint8 image + mask in, composed uint8 image out (demo.py's pre/post-processing inside the first / "
                          "last kernels, migan_forward_u8); the all-gather then moves uint8 shards (4x fewer bytes)")
-    ap.add_argument("--cpu-images", type=int, default=4, help="sample size of the CPU baseline (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: roofline, CPU baseline and parity, batch-1 latency, "
+                         "the one-rank RCCL leg and (default workload) the secondary workloads.  Off: set up, warm up, time --steps steps, "
+                         "print the line")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write the output of the last one as DIR/output.npy (float32; at most 64 MB: a fixed, "
+                         "seeded sample of the images when the output is larger)")
+    ap.add_argument("--cpu-images", type=int, default=4, help="sample size of the CPU baseline (--full; 0 = skip)")
     ap.add_argument("--no-gather", action="store_true", help="N>1: skip the output all-gather")
     ap.add_argument("--gather-dtype", type=str, default="auto", choices=["auto", "f32", "f16", "u8"],
                     help="N>1: what the ranks exchange.  auto = the forward's own output (fp32 [n,3,R,R], 100.7 MB per rank and step at "
@@ -99,11 +111,11 @@ def parse(argv=None):
     ap.add_argument("--force-pg", action="store_true",
                     help="N=1: also create a one-rank NCCL (= RCCL) process group and time the same steps through the pipelined output "
                          "gather (rccl_world1 on the line): the collective path on the hardware without a second GPU")
-    ap.add_argument("--no-latency", action="store_true", help="skip the batch-1 latency measurement (latency_b1_ms)")
-    ap.add_argument("--no-secondary", action="store_true", help="N=1 default run: skip the secondary workloads")
+    ap.add_argument("--no-latency", action="store_true", help="--full: skip the batch-1 latency measurement (latency_b1_ms)")
+    ap.add_argument("--no-secondary", action="store_true", help="N=1 --full run of the default workload: skip the secondary workloads")
     ap.add_argument("--cpu-all-cores", action="store_true",
                     help="also time the CPU port on every logical core (on the 256-thread host of the GPU box: 0.015 images/s, ~70 s per "
-                         "image -- oversubscription; off by default so that the default run stays within minutes)")
+                         "image -- oversubscription; with --full, and off by default so that a --full run stays within minutes)")
     ap.add_argument("--cpu-threads", type=int, default=16,
                     help="threads of the CPU baseline (0 = all logical cores); 16 is the fastest setting measured for this\n"
                          "graph of small oneDNN convs on the 256-thread GPU-box host (8: 1.04, 16: 0.94, 32: 1.07, 64: 1.72, 128: 4.4 s/img)")
@@ -257,6 +269,34 @@ def flush_c_stdio():
     except Exception:   # pragma: no cover
         pass
     sys.stdout.flush()
+
+
+DUMP_BUDGET_BYTES = 64 * 10**6
+
+
+def dump_outputs(dirpath, y, budget=DUMP_BUDGET_BYTES, seed=0):
+    """--dump-outputs: what the timed path returned in its last step as DIR/output.npy, float32 (a uint8 image is widened, not
+    rescaled).  Where the whole output is larger than `budget` bytes, a fixed, seeded sample of its images (first axis, ascending)
+    is written instead: the same images from run to run.  Returns the description that goes on the line."""
+    os.makedirs(dirpath, exist_ok=True)
+    n = int(y.shape[0])
+    per_image = int(np.prod(tuple(y.shape[1:]))) * 4
+    k = n if n * per_image <= budget else max(1, budget // per_image)
+    idx = np.arange(n) if k == n else np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+    sample = y.detach() if k == n else y.detach()[torch.as_tensor(idx, device=y.device)]
+    arr = sample.to(torch.float32).cpu().numpy()
+    np.save(os.path.join(dirpath, "output.npy"), arr)
+    return {"dir": dirpath, "files": {"output": {"shape": list(arr.shape), "dtype": "float32",
+                                                 "images": "all" if k == n else [int(i) for i in idx]}}}
+
+
+def dump_last_step(args, rank, pipe, slot, y):
+    """--dump-outputs after the timed steps, on rank 0: what a caller of the timed path receives from the last step -- the gathered
+    batch of all ranks where the step ends in the output gather (`slot` = that step's gather slot, complete after the drain), the
+    step's own output `y` otherwise.  Shared by the GPU run and the --dry plumbing run."""
+    if not args.dump_outputs or rank != 0:
+        return None
+    return dump_outputs(args.dump_outputs, pipe.result(slot) if pipe is not None else y)
 
 
 def kernel_source_sha():
@@ -520,9 +560,11 @@ def run_workload(args, rank, local_rank, world, dist, dev):
             if rc:
                 raise RuntimeError(f"occupy_launch failed with {rc}")
 
+    last_slot = [None]                                       # N > 1: the gather slot of the latest step (--dump-outputs)
+
     def step():
         if inplace:
-            slot = pipe.forward_and_submit(wl["model"], wl["x"])
+            slot = last_slot[0] = pipe.forward_and_submit(wl["model"], wl["x"])
             if occupy is not None:
                 occupy()
             return pipe.shards(slot)[0]
@@ -534,7 +576,7 @@ def run_workload(args, rank, local_rank, world, dist, dev):
         else:
             y = wl["step"]()
         if gather:
-            pipe.submit(y if y.dtype == gdt else y.to(gdt))
+            last_slot[0] = pipe.submit(y if y.dtype == gdt else y.to(gdt))
         if occupy is not None:
             occupy()
         return y
@@ -572,14 +614,15 @@ def run_workload(args, rank, local_rank, world, dist, dev):
         for _ in range(args.warmup):
             step()
         elapsed, y = timed_loop(step, args.steps)
+        dumped = dump_last_step(args, rank, pipe, last_slot[0], y)
         compute_only = None
-        if gather:                                           # the same steps without the collective, for the record
+        if gather and args.full:                             # the same steps without the collective, for the record
             for _ in range(2):
                 wl["step"]()
             el2, _ = timed_loop(wl["step"], args.steps)
             compute_only = el2 / args.steps * 1e3
         alt = None
-        if wl.get("alt") and world == 1:                     # the same workload the way the reference's demo.py calls it
+        if args.full and wl.get("alt") and world == 1:       # the same workload the way the reference's demo.py calls it
             for _ in range(2):
                 wl["alt"]["step"]()
             el3, _ = timed_loop(wl["alt"]["step"], max(3, args.steps // 2))
@@ -596,25 +639,27 @@ def run_workload(args, rank, local_rank, world, dist, dev):
     if rank != 0:
         return None
     # ---- roofline of the dominant kernel: hipEvent pair around every launch (same stream) -----
-    rounds = []
-    with torch.no_grad():
-        for i in range(3 + min(args.steps, 5)):
-            _, ms = wl["timed"]()
-            if i >= 3:
-                rounds.append(ms)
-    launches = wl["launches"]()
-    dom = roofline_from_launches(launches, rounds, batch, wl["gemm"])
-    attach_traffic(dom, *wl["traffic"])
-    # the line's `roofline` describes the whole forward (time-weighted over all launches); the dominant kernel symbol is a sub-object
-    roof = forward_roofline(dom, ms_per_step)
-    finish_traffic(roof, dom)
-    if args.dump_layers:
-        med = np.median(np.asarray(rounds), axis=0)
-        with open(args.dump_layers, "w") as f:
-            json.dump([dict(L, ms=float(t)) for L, t in zip(launches, med)], f, indent=1)
+    roof = None
+    if args.full or args.dump_layers:
+        rounds = []
+        with torch.no_grad():
+            for i in range(3 + min(args.steps, 5)):
+                _, ms = wl["timed"]()
+                if i >= 3:
+                    rounds.append(ms)
+        launches = wl["launches"]()
+        dom = roofline_from_launches(launches, rounds, batch, wl["gemm"])
+        attach_traffic(dom, *wl["traffic"])
+        # the line's `roofline` describes the whole forward (time-weighted over all launches); the dominant kernel symbol is a sub-object
+        roof = forward_roofline(dom, ms_per_step)
+        finish_traffic(roof, dom)
+        if args.dump_layers:
+            med = np.median(np.asarray(rounds), axis=0)
+            with open(args.dump_layers, "w") as f:
+                json.dump([dict(L, ms=float(t)) for L, t in zip(launches, med)], f, indent=1)
     # ---- CPU baseline + parity on the same inputs (rank 0, N = 1 protocol) ---------------------
     cpu = parity = parity32 = envelope = ymax = None
-    if args.cpu_images > 0 and world == 1:      # the CPU baseline is an N = 1 measurement (rank 0 only)
+    if args.full and args.cpu_images > 0 and world == 1:      # the CPU baseline is an N = 1 measurement (rank 0 only)
         n = min(args.cpu_images if name == "migan" else max(1, args.cpu_images // 4), batch)
         cores = os.cpu_count() or 1
         threads = min(args.cpu_threads or cores, cores)
@@ -665,7 +710,7 @@ def run_workload(args, rank, local_rank, world, dist, dev):
                     "f16x2": "fp16x2-split MFMA, fp32 accumulate",
                     "f16": "fp16 MFMA on fp16-rounded operands, fp32 accumulate"}.get(wl["gemm"], wl["gemm"]) + \
                    "; depthwise 3x3, FIR, activations, epilogues in fp32 VALU"
-    if name == "migan" and world == 1 and not args.no_latency and args.io == "f32":
+    if args.full and name == "migan" and world == 1 and not args.no_latency and args.io == "f32":
         try:
             lat, y1, x1 = latency_batch1(wl["model"], pkg, res, dev)
             if args.cpu_images > 0 and not getattr(args, "is_secondary", False):      # (the secondary lines report the time only)
@@ -677,7 +722,7 @@ def run_workload(args, rank, local_rank, world, dist, dev):
             out["latency_b1"] = lat
         except Exception as e:   # pragma: no cover
             out["latency_b1"] = {"error": f"{type(e).__name__}: {e}"}
-    if world == 1 and (args.force_pg or primary_default(args)):
+    if world == 1 and (args.force_pg or (args.full and primary_default(args))):
         try:
             out["rccl_world1"] = rccl_world1(wl, pkg, batch, dev, max(3, min(args.steps, 10)))
         except Exception as e:
@@ -718,6 +763,8 @@ def run_workload(args, rank, local_rank, world, dist, dev):
         out["reserved_cus"] = args.reserve_cus
     if args.occupy:
         out["occupy"] = args.occupy
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     return out
 
 
@@ -832,6 +879,7 @@ def secondary_line(base_args, **over):
     """run another workload with the same protocol in this process and return its (trimmed) line"""
     a = argparse.Namespace(**vars(base_args))
     a.dump_layers = ""
+    a.dump_outputs = ""                                      # (DIR/output.npy is the primary workload's)
     a.is_secondary = True
     for k, v in over.items():
         setattr(a, k, v)
@@ -863,21 +911,26 @@ def dry_run(args, rank, world, dist):
     dev = torch.device("cpu")
     u8 = args.io == "u8"
     shape = (batch, 8, 8, 3) if u8 else (batch, 3, 8, 8)
-    y = torch.full(shape, rank, dtype=torch.uint8 if u8 else torch.float32)
+    odt = torch.uint8 if u8 else torch.float32
     gather = world > 1 and not args.no_gather
-    gdt = gather_dtype_of(args, y.dtype)
+    gdt = gather_dtype_of(args, odt)
     pipe = pkg.distributed.OutputGather(shape, gdt, dev) if gather else None
+    last_slot, y = None, torch.full(shape, rank % 256, dtype=odt)
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        # the stand-in "forward" of step i on this rank: every element (rank + world * i) mod 256, so that a dump or a result of the
+        # wrong step or rank shows
+        y = torch.full(shape, (rank + world * i) % 256, dtype=odt)
         if gather:
-            slot = pipe.submit(y.to(gdt))
+            last_slot = pipe.submit(y.to(gdt))
     if gather:
         pipe.drain()
-        full = pipe.result(slot)
-        assert full.shape[0] == world * batch and float(full[-1, 0, 0, 0]) == world - 1
+        full = pipe.result(last_slot)
+        assert full.shape[0] == world * batch and float(full[-1, 0, 0, 0]) == (world - 1 + world * (args.steps - 1)) % 256
     if world > 1:
         dist.barrier()
     el = time.perf_counter() - t0
+    dumped = dump_last_step(args, rank, pipe, last_slot, y)
     ranks_seen = world
     if world > 1:
         got = [torch.zeros(1, dtype=torch.int64) for _ in range(world)]
@@ -890,7 +943,8 @@ def dry_run(args, rank, world, dist):
             "vs_baseline": None, "dtype": args.dtype, "data": "none (--dry: launch plumbing only, no forward was run)",
             "config": {"workload": "dry run", "global_batch": world * batch, "parallelism": f"batch-shard x{world}"},
             "dry": True, "rccl_ranks": ranks_seen, "backend": args.backend, "gather_dtype": str(gdt).replace("torch.", ""),
-            "gather_mb_per_rank_per_step": round(float(np.prod(shape)) * torch.empty(0, dtype=gdt).element_size() / 1e6, 6)}
+            "gather_mb_per_rank_per_step": round(float(np.prod(shape)) * torch.empty(0, dtype=gdt).element_size() / 1e6, 6),
+            **({"dumped_outputs": dumped} if dumped is not None else {})}
 
 
 def worker(rank, local_rank, world, args):
@@ -922,7 +976,7 @@ def worker(rank, local_rank, world, args):
         out = run_workload(args, rank, local_rank, world, dist, dev)
         t_primary = time.perf_counter() - t_wall
         name, res, batch = split_model(args)
-        if out is not None and world == 1 and not args.no_secondary and args.model == "migan-512" and not args.resolution \
+        if out is not None and args.full and world == 1 and not args.no_secondary and args.model == "migan-512" and not args.resolution \
                 and not args.batch and args.dtype == "f32" and args.gemm == "f16x2" and args.io == "f32" and args.nan_policy == "propagate":
             # the default driver run: also time the exact-fp32-MFMA variant of the same workload and the other two
             # single-GPU BASELINE configs, same protocol

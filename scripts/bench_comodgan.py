@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Measurement of the second model (BASELINE.json configs[4]): images/sec of the comodgan-512
 generator forward, batch 16, fp32, one MI355X.  Thin front end of `bench.py --model comodgan-512` (same protocol and
-JSON schema; the default `bench.py` run also reports this workload under "secondary").
+JSON schema) with --full, so that the line carries `roofline` and `cpu_baseline`; `bench.py --full` also reports this workload
+under "secondary".
 
     python scripts/bench_comodgan.py [--batch 16] [--steps 10] [--warmup 3] [--cpu-images 4] [--dump-layers f.json]
 """
@@ -19,4 +20,6 @@ if __name__ == "__main__":
         argv = ["--model", "comodgan-512"] + argv
     if not any(a.startswith("--steps") for a in argv):
         argv += ["--steps", "10", "--warmup", "3"]
+    if "--full" not in argv:
+        argv.append("--full")
     bench.main(argv)

@@ -13,4 +13,4 @@ cd $R
 cp $OUT/pmc_traffic_migan512.json profiles/pmc_traffic_latest.json
 cp $OUT/pmc_traffic_migan256_bf16.json profiles/pmc_traffic_migan256_bf16_latest.json
 cp $OUT/pmc_traffic_comodgan512.json profiles/pmc_traffic_comodgan_latest.json
-timeout 800 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout 800 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"

@@ -17,7 +17,7 @@ cd $R
 [ -s $OUT/pmc_traffic_migan512.json ] && cp $OUT/pmc_traffic_migan512.json profiles/pmc_traffic_latest.json
 [ -s $OUT/pmc_traffic_migan256_bf16.json ] && cp $OUT/pmc_traffic_migan256_bf16.json profiles/pmc_traffic_migan256_bf16_latest.json
 [ -s $OUT/pmc_traffic_comodgan512.json ] && cp $OUT/pmc_traffic_comodgan512.json profiles/pmc_traffic_comodgan_latest.json
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -c 600 $OUT/bench.json
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -c 600 $OUT/bench.json
 timeout 300 python bench.py --no-secondary --cpu-images 0 --no-latency --dump-layers $OUT/per_launch.json > $OUT/per_launch_bench.json 2> $OUT/per_launch.err; echo "layers rc=$?"
 timeout 300 python bench.py --no-secondary --cpu-images 0 --no-latency --batch 1 --streams 1 --dump-layers $OUT/per_launch_batch1.json > $OUT/per_launch_batch1_bench.json 2>> $OUT/per_launch.err; echo "layers b1 rc=$?"
 timeout 300 python bench.py --model migan-256 --dtype bf16 --no-secondary --cpu-images 0 --no-latency --dump-layers $OUT/per_launch_migan256_bf16.json > $OUT/per_launch_migan256_bf16_bench.json 2>> $OUT/per_launch.err; echo "layers bf16 rc=$?"

@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -147,3 +149,48 @@ def test_line_roofline_describes_the_whole_forward():
     gemm = [dict(layer="g", kernel="k_gemm", flops=8e9, mfma_flops=8e9, bytes=1e6)]
     r2 = b.forward_roofline(b.roofline_from_launches(gemm, [[0.9]], batch, "f16x2"), 0.9)
     assert r2["bound"] == "mfma" and abs(r2["peak"] - 833.3) < 0.1 and abs(r2["frac"] - 32 * 8e9 / 0.9e-3 / 1e12 / 833.3) < 1e-3
+
+
+def test_dump_outputs_writes_the_last_step_the_same_from_run_to_run(tmp_path):
+    """--dump-outputs DIR: the output of the last timed step as DIR/output.npy in float32, recorded on the line, identical for identical
+    arguments; for N > 1 the gathered batch of all ranks, from the gather slot of the LAST step (the dry run's stand-in forward of step i
+    on rank r writes r + world * i, through the same dump call as the GPU run)"""
+    r, out = _run("--dry", "--steps", "2", "--dump-outputs", str(tmp_path / "a"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    y = np.load(tmp_path / "a" / "output.npy")
+    assert y.dtype == np.float32 and y.shape == (32, 3, 8, 8) and float(y.min()) == float(y.max()) == 1.0
+    assert out["dumped_outputs"]["files"]["output"] == {"shape": [32, 3, 8, 8], "dtype": "float32", "images": "all"}
+    r, out = _run("--dry", "--steps", "2", "--dump-outputs", str(tmp_path / "b"))
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "output.npy"), y)
+    # two ranks, three steps through a double-buffered gather: step 2 reuses step 0's slot, step 1's slot holds 2 / 3
+    r, out = _run("--gpus", "2", "--backend", "gloo", "--dry", "--steps", "3", "--dump-outputs", str(tmp_path / "c"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    y2 = np.load(tmp_path / "c" / "output.npy")
+    assert y2.dtype == np.float32 and y2.shape == (64, 3, 8, 8)
+    assert set(np.unique(y2[:32])) == {4.0} and set(np.unique(y2[32:])) == {5.0}
+    r, out = _run("--gpus", "2", "--backend", "gloo", "--dry", "--steps", "2", "--io", "u8", "--dump-outputs", str(tmp_path / "d"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    y3 = np.load(tmp_path / "d" / "output.npy")
+    assert y3.dtype == np.float32 and y3.shape == (64, 8, 8, 3) and set(np.unique(y3[:32])) == {2.0} and set(np.unique(y3[32:])) == {3.0}
+
+
+def test_dump_outputs_samples_a_large_output_within_the_budget(tmp_path):
+    """an output above the byte budget (64 MB: the migan-512 batch of 32 is 100.7 MB) is written as a fixed, seeded sample of its
+    images, in ascending order"""
+    import importlib.util
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    assert b.DUMP_BUDGET_BYTES == 64 * 10**6 and b.parse([]).full is False and b.parse(["--full"]).full is True
+    y = torch.arange(32 * 3 * 4 * 4, dtype=torch.float32).reshape(32, 3, 4, 4)
+    per_image = 3 * 4 * 4 * 4
+    d1 = b.dump_outputs(str(tmp_path / "a"), y, budget=10 * per_image + 5)
+    d2 = b.dump_outputs(str(tmp_path / "b"), y, budget=10 * per_image + 5)
+    idx = d1["files"]["output"]["images"]
+    assert idx == d2["files"]["output"]["images"] and len(idx) == 10 and idx == sorted(set(idx)) and idx != list(range(10))
+    got = np.load(tmp_path / "a" / "output.npy")
+    assert got.nbytes <= 10 * per_image + 5
+    np.testing.assert_array_equal(got, y.numpy()[idx])
+    full = b.dump_outputs(str(tmp_path / "c"), y)
+    assert full["files"]["output"]["images"] == "all" and np.load(tmp_path / "c" / "output.npy").shape == (32, 3, 4, 4)
