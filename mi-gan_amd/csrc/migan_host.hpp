@@ -522,6 +522,10 @@ inline void prepare_kernels() {
   std::lock_guard<std::mutex> lock(mu);
   if (dev >= 0 && dev < (int)done.size() && done[dev]) return;
   for (const auto& e : kernel_table()) rt_check(rt::allow_dynamic_lds((const void*)e.fn, 96 * 1024), "hipFuncSetAttribute");
+  // narrow FIR-up: the 18 x 18 x Cout fp32 tile of launch_narrow (81 KiB at Cout = 64); the other forms take no dynamic LDS
+  for (int m : {MODE_NORMAL, MODE_DOWN, MODE_UP})
+    rt_check(rt::allow_dynamic_lds((const void*)narrow_fn(m, false), 96 * 1024), "hipFuncSetAttribute");
+  rt_check(rt::allow_dynamic_lds((const void*)narrow_fn(MODE_NORMAL, true), 96 * 1024), "hipFuncSetAttribute");
   {
     const PipeSlice sl = pipe_slice();
     for (int i = 0; i < sl.n; ++i) rt_check(rt::allow_dynamic_lds((const void*)sl.entries[i].fn, 160 * 1024), "hipFuncSetAttribute");
@@ -1679,6 +1683,8 @@ int migan_sepconv_forward(const migan_sepconv_desc* d, void* stream) {
     MIGAN_CHECK(d->torgb_weight == nullptr || (d->up == 1 && d->down == 1 && d->img_out && d->torgb_bias), MIGAN_EINVAL,
                 "ToRGB needs up == down == 1, torgb_bias and img_out");
     MIGAN_CHECK(d->fromrgb_weight == nullptr || (d->up == 1 && d->down == 1), MIGAN_EINVAL, "fromrgb is only fused into plain layers");
+    MIGAN_CHECK(d->fromrgb_weight == nullptr || d->fromrgb_bias != nullptr, MIGAN_EINVAL, "fromrgb_weight without fromrgb_bias");
+    prepare_kernels();
     const int nmode = d->down == 2 ? MODE_DOWN : (d->up == 2 ? MODE_UP : MODE_NORMAL);
     SepArgs a{};
     a.x = d->x; a.y = d->y; a.skip = d->skip;
@@ -1691,6 +1697,9 @@ int migan_sepconv_forward(const migan_sepconv_desc* d, void* stream) {
     launch_narrow(nmode, d->fromrgb_weight != nullptr, a, (rt::stream_t)stream);
     return MIGAN_OK;
   }
+  MIGAN_CHECK(d->fromrgb_weight == nullptr || d->fromrgb_bias != nullptr, MIGAN_EINVAL, "fromrgb_weight without fromrgb_bias");
+  // (every refusal before the first launch: a refused call leaves y, img_out and the scratch tensors untouched)
+  MIGAN_CHECK(d->torgb_weight == nullptr || (d->up == 1 && d->img_out && d->torgb_bias), MIGAN_EINVAL, "ToRGB needs up == 1, torgb_bias and img_out");
   const void* gemm_in = d->x;
   int mode = d->up == 2 ? MODE_UP : MODE_NORMAL, gemm_h = h_in, gemm_w = w_in;
   // split GEMM variants need room for the 16-bit weight planes; without it the exact fp32 MFMA path runs
@@ -1741,7 +1750,6 @@ int migan_sepconv_forward(const migan_sepconv_desc* d, void* stream) {
     sa.src[0] = (const float*)d->conv2_weight; sa.dst_off[0] = kSplitHeader; sa.count[0] = (unsigned)(d->cin * d->cout); sa.ci[0] = (unsigned)d->cin; sa.n = 1;
     launch_split(sa, (rt::stream_t)stream);
   }
-  MIGAN_CHECK(d->torgb_weight == nullptr || (mode != MODE_UP && d->img_out && d->torgb_bias), MIGAN_EINVAL, "ToRGB needs up == 1, torgb_bias and img_out");
   // one workgroup owns all output channels of its pixels (cout <= 128, or 256 on whole 8x16 tiles): ToRGB fuses into the epilogue;
   // otherwise torgb_kernel runs on y afterwards, as in the generator plan
   const bool fuse_rgb = d->torgb_weight != nullptr && g.nchunks == 1;

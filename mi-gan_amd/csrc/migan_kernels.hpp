@@ -2195,8 +2195,8 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) narrow_sepconv_kernel(const SepArg
   float r0 = 0.0f, r1 = 0.0f, r2 = 0.0f;
   for (int co = 0; co < CO; ++co) {
     float v = act1(p.noise ? g[co] + nz : g[co]);
-    if (p.trgb_w) { r0 += p.trgb_w[co] * v; r1 += p.trgb_w[CO + co] * v; r2 += p.trgb_w[2 * CO + co] * v; }
     if (sk) v += sk[co];
+    if (p.trgb_w) { r0 += p.trgb_w[co] * v; r1 += p.trgb_w[CO + co] * v; r2 += p.trgb_w[2 * CO + co] * v; }     // ToRGB reads the stored tensor
     yo[co] = v;
   }
   if (p.trgb_w) {      // torgb (:277 / :312) + Upsample2d of the running image (:308-313)

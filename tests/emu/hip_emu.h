@@ -24,6 +24,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -369,7 +371,28 @@ inline int get_device(int* dev) { *dev = 0; return 0; }
 // the emulator executes every launch synchronously, in enqueue order: streams and ordering events are no-ops
 inline int stream_create(stream_t* s) { *s = reinterpret_cast<stream_t>(0x1); return 0; }
 inline int stream_destroy(stream_t) { return 0; }
-inline int allow_dynamic_lds(const void*, size_t) { return 0; }
+// Dynamic LDS above the default 64 KiB needs the per-function attribute first (hipFuncSetAttribute(...,
+// hipFuncAttributeMaxDynamicSharedMemorySize, bytes)); launch refuses a kernel that was not raised far enough.
+constexpr size_t kDefaultDynLds = 64 * 1024;
+inline std::map<const void*, size_t>& dyn_lds_limits() {
+  static std::map<const void*, size_t> m;
+  return m;
+}
+inline std::mutex& dyn_lds_mutex() {
+  static std::mutex mu;
+  return mu;
+}
+inline int allow_dynamic_lds(const void* fn, size_t bytes) {
+  if (fn == nullptr || bytes > 160 * 1024) return 1;
+  std::lock_guard<std::mutex> lock(dyn_lds_mutex());
+  dyn_lds_limits()[fn] = bytes;
+  return 0;
+}
+inline size_t dynamic_lds_limit(const void* fn) {
+  std::lock_guard<std::mutex> lock(dyn_lds_mutex());
+  const auto it = dyn_lds_limits().find(fn);
+  return it == dyn_lds_limits().end() ? kDefaultDynLds : it->second;
+}
 
 template <class Args>
 struct Thunk {
@@ -384,6 +407,7 @@ struct Thunk {
 template <class Args>
 inline int launch(void (*kernel)(const Args), const Args& a, unsigned grid, unsigned block, size_t lds, stream_t) {
   if (block == 0 || block % 64 != 0 || block > (unsigned)hipemu::kMaxLanes || lds > 160 * 1024) return 1;
+  if (lds > kDefaultDynLds && lds > dynamic_lds_limit((const void*)kernel)) return 1;
   Thunk<Args> t{kernel, &a};
   hipemu::run_grid(&Thunk<Args>::call, &t, grid, block, lds);
   return 0;

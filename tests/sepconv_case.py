@@ -2,6 +2,7 @@
 compared with the numpy oracle in the same storage mode.  Shared by the CPU tests (product kernel source on the fiber
 emulator, host memory) and the GPU tests (libmigan_hip.so, device memory).  Test infrastructure only."""
 import numpy as np
+import pytest
 
 from oracle import migan_oracle as orc
 from tests.emu_util import aligned, from_storage, nchw, nhwc, storage_close, storage_ulp, to_storage
@@ -66,8 +67,13 @@ def weights(pkg, cin, cout, seed, res_out, noise, wscale=1.0):
 
 
 def run_sepconv_case(lib, pkg, mem, *, cin, cout, h, w=None, batch, down=1, up=1, noise=False, skip=False, seed=1, storage="f32",
-                     gemm=-1, fromrgb=False, torgb=False, with_prev=False, wscale=1.0, nan_at=None):
+                     gemm=-1, fromrgb=False, torgb=False, with_prev=False, wscale=1.0, nan_at=None, oracle_f64=False, drop=(),
+                     refused=None):
+    """oracle_f64: evaluate the oracle in float64 (fp32 storage: the kernel against the exact function, same tolerances).
+    drop: pointer arguments passed as null although their companions are set (e.g. "fromrgb_bias", "img_out", "noise_strength").
+    refused: (exception type, message fragment) the call must raise; y and img_out must then still hold their NaN fill."""
     w = w or h
+    odt = np.float64 if oracle_f64 and storage == "f32" else np.float32
     ho, wo = (h // 2, w // 2) if down == 2 else ((h * 2, w * 2) if up == 2 else (h, w))
     sd = weights(pkg, cin, cout, seed, (ho, wo), noise, wscale)
     osd = dict(sd)
@@ -87,7 +93,7 @@ def run_sepconv_case(lib, pkg, mem, *, cin, cout, h, w=None, batch, down=1, up=1
         fw = (pkg.synth.normal((cin, 4, 1, 1), seed, "fw") * 0.7).astype(np.float32)
         fb = (pkg.synth.normal((cin,), seed, "fb") * 0.3).astype(np.float32)
         img = (pkg.synth.normal((batch, 4, h, w), seed, "img") * 0.8).astype(np.float32)
-        x = orc.lrelu_agc(orc.pointwise(img, fw, fb))                  # reference :194-195 (not a stored tensor)
+        x = orc.lrelu_agc(orc.pointwise(img.astype(odt), fw, fb))      # reference :194-195 (not a stored tensor)
         xin = dev(img)
         kw.update(fromrgb_weight=mem.ptr(dev(fw)), fromrgb_bias=mem.ptr(dev(fb)))
     else:
@@ -96,7 +102,7 @@ def run_sepconv_case(lib, pkg, mem, *, cin, cout, h, w=None, batch, down=1, up=1
             x[nan_at] = np.nan                       # NaN-propagating builds only (Generator(nan_policy="propagate")): the mask must follow the oracle
         xin = dev(to_storage(nhwc(x), storage))
     gemm16 = storage != "f32" and gemm != 2          # 16-bit storage: GEMM variant "f16" unless f16x2 (2) is asked for
-    want = orc.separable_conv(x.copy(), osd, "m", gemm16)
+    want = orc.separable_conv(x.astype(odt), osd, "m", gemm16)
     sk = None
     if skip:
         sk = orc.round_storage(pkg.synth.normal((batch, cout, ho, wo), seed, "skip").astype(np.float32), storage)
@@ -119,13 +125,23 @@ def run_sepconv_case(lib, pkg, mem, *, cin, cout, h, w=None, batch, down=1, up=1
         kw.update(torgb_weight=mem.ptr(dev(tw)), torgb_bias=mem.ptr(dev(tb)), img_out=mem.ptr(img_out))
         if with_prev:
             prev = pkg.synth.normal((batch, 3, ho // 2, wo // 2), seed, "prev").astype(np.float32)
-            want_img = want_img + orc.upsample2d(prev)
+            want_img = want_img + orc.upsample2d(prev.astype(odt))
             kw.update(img_prev=mem.ptr(dev(prev)))
-    lib.sepconv_forward(stream=mem.stream, x=mem.ptr(xin), y=mem.ptr(y), skip=mem.ptr(skh), conv1_weight=mem.ptr(w1),
-                        conv1_bias=mem.ptr(b1), conv2_weight=mem.ptr(w2), noise_const=mem.ptr(nc), noise_strength=mem.ptr(ns),
-                        batch=batch, cin=cin, cout=cout, res_in=h, width_in=w, down=down, up=up,
-                        scratch=mem.ptr(scratch), scratch_bytes=0 if scratch is None else batch * ho * wo * cin * 4,
-                        wsplit=mem.ptr(wsp), wsplit_bytes=wsp_n * 4, dtype=pkg.hipbind.dtype_code(storage), gemm=gemm, **kw)
+    ns = None if "noise_strength" in drop else ns
+    kw.update({name: None for name in drop if name != "noise_strength"})
+    args = dict(stream=mem.stream, x=mem.ptr(xin), y=mem.ptr(y), skip=mem.ptr(skh), conv1_weight=mem.ptr(w1), conv1_bias=mem.ptr(b1),
+                conv2_weight=mem.ptr(w2), noise_const=mem.ptr(nc), noise_strength=mem.ptr(ns), batch=batch, cin=cin, cout=cout, res_in=h,
+                width_in=w, down=down, up=up, scratch=mem.ptr(scratch), scratch_bytes=0 if scratch is None else batch * ho * wo * cin * 4,
+                wsplit=mem.ptr(wsp), wsplit_bytes=wsp_n * 4, dtype=pkg.hipbind.dtype_code(storage), gemm=gemm, **kw)
+    if refused is not None:
+        with pytest.raises(refused[0], match=refused[1]):
+            lib.sepconv_forward(**args)
+        mem.sync()
+        assert np.isnan(from_storage(mem.get(y), storage)).all(), "a refused call wrote y"
+        if img_out is not None:
+            assert np.isnan(mem.get(img_out)).all(), "a refused call wrote img_out"
+        return None
+    lib.sepconv_forward(**args)
     mem.sync()
     got = nchw(from_storage(mem.get(y), storage))
     if nan_at is not None:

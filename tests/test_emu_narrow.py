@@ -30,6 +30,9 @@ CASES = [
     (dict(cin=32, cout=32, h=16, batch=2, fromrgb=True), "0, true>"),                            # encoder.b1024.conv1 with the fused FromRGB
     (dict(cin=32, cout=32, h=16, batch=2, noise=True, torgb=True, with_prev=True), "0, false>"),   # ... and the ToRGB tail
     (dict(cin=8, cout=8, h=8, batch=1, noise=True, torgb=True), "0, false>"),
+    (dict(cin=16, cout=64, h=6, w=10, batch=2, up=2, noise=True, skip=True), "2, false>"),     # FIR-up into 64 channels: 81 KiB of dynamic LDS
+    (dict(cin=32, cout=32, h=12, w=20, batch=2, skip=True, torgb=True), "0, false>"),           # ToRGB reads the stored value v + skip
+    (dict(cin=32, cout=32, h=8, batch=3, noise=True, skip=True, torgb=True, with_prev=True), "0, false>"),
 ]
 
 

@@ -38,6 +38,9 @@ CASES = [
     (dict(cin=32, cout=32, h=16, batch=2, fromrgb=True), "0, true>"),                            # encoder.b1024.conv1 with the fused FromRGB
     (dict(cin=32, cout=32, h=16, batch=2, noise=True, torgb=True, with_prev=True), "0, false>"),   # ... and the ToRGB tail
     (dict(cin=8, cout=8, h=8, batch=1, noise=True, torgb=True), "0, false>"),
+    (dict(cin=16, cout=64, h=6, w=10, batch=2, up=2, noise=True, skip=True), "2, false>"),     # FIR-up into 64 channels: 81 KiB of dynamic LDS
+    (dict(cin=32, cout=32, h=12, w=20, batch=2, skip=True, torgb=True), "0, false>"),           # ToRGB reads the stored value v + skip
+    (dict(cin=32, cout=32, h=8, batch=3, noise=True, skip=True, torgb=True, with_prev=True), "0, false>"),
 ]
 
 
@@ -77,3 +80,26 @@ def test_generator_1024_any_size_and_batch(pkg, mem):
     assert sum(k.startswith(NARROW) for k in kernels) == 3          # encoder.b1024.conv1, synthesis.b1024.conv1 / conv2 (encoder.b1024.conv2, 32 -> 64, runs the tiled kernels)
     with pytest.raises((NotImplementedError, RuntimeError)):        # the uint8 forward is not offered above 512
         m.forward_uint8(torch.zeros((1, res, res, 3), dtype=torch.uint8, device=dev), torch.zeros((1, res, res), dtype=torch.uint8, device=dev))
+
+
+@pytest.mark.parametrize("res,hw,batch,narrow,downs", [
+    (2048, 512, 2, 7, 1),     # encoder.b2048.conv1 / .conv2 (FIR-down 16 -> 32) / b1024.conv1, synthesis.b1024.conv1 / conv2, b2048.conv1 / conv2
+    (4096, 1024, 2, 11, 2),   # ... and encoder.b4096.conv1 / .conv2 (8 -> 16), synthesis.b4096.conv1 / conv2
+])
+def test_generator_above_1024_any_size(pkg, mem, res, hw, batch, narrow, downs):
+    """Generator(2048) / Generator(4096) on an input of a quarter of their size through forward_any_size -- the narrow down=2 branch of
+    the plan (is_narrow(c, channels_at(res / 2)), first at 2048) inside a generator -- against the torch-CPU port of the reference"""
+    dev = torch.device("cuda", 0)
+    seed = 37
+    sd = pkg.synth.make_state_dict(res, seed=seed, regime="export")
+    m = pkg.Generator(resolution=res)
+    m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in sd.items()}, strict=True)
+    m = m.to(dev).eval()
+    x = (pkg.synth.normal((batch, 4, hw, hw), seed, "xhw") * 0.7).astype(np.float32)
+    with torch.no_grad():
+        y = m.forward_any_size(torch.from_numpy(x).to(dev)).cpu().numpy()
+    want = torc.generator(x, sd, res).numpy()
+    assert np.abs(y - want).max() <= 1e-3, float(np.abs(y - want).max())
+    kernels = [l["kernel"] for l in m.launch_info()]
+    assert sum(k.startswith(NARROW) for k in kernels) == narrow, kernels
+    assert sum(k == NARROW + "1, false>" for k in kernels) == downs, kernels      # encoder.b2048.conv2 (16 -> 32), b4096.conv2 (8 -> 16)
