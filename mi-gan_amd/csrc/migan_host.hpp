@@ -70,6 +70,8 @@ inline int ilog2(int v) {
   return l;
 }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// bit of a layer kind in the kc16 / w3 / pipe / pipe_na8 masks: 1 plain (+ fused ToRGB), 2 fused FromRGB, 4 FIR-up
+inline int layer_bit(bool fromrgb, int mode) { return fromrgb ? 2 : (mode == MODE_UP ? 4 : 1); }
 
 // Tuning knobs read once from the environment (experiments only; defaults are the shipped choice).
 struct Tuning {
@@ -167,16 +169,18 @@ inline Geo choose_geo(int mode, int cin, int cout, int h_in, int w_in, bool from
   const bool full = h_in % 8 == 0 && w_in % 16 == 0;               // whole 8x16 tiles
   g.NT = (cout % 128 == 0) ? 128 : 64;
   int GH, GW, IMGS;
-  if (mode == MODE_NORMAL) {
-    g.MT = 128; g.KC = 32;
+  g.MT = 128; g.KC = 32;
+  if (mode == MODE_NORMAL || mode == MODE_PW) {
+    // MODE_PW: pointwise GEMM at h_in x w_in (second half of a down=2 layer; its input is dwfir_kernel's output)
+    MIGAN_CHECK(mode == MODE_NORMAL || !fromrgb, MIGAN_EINVAL, "fromrgb is only fused into plain layers");
     if (small) {
       g.MT = 32; g.NT = 128; GH = 4;
       if (sq2 && h_in == 4) { GW = 4; IMGS = 2; } else { GW = 8; IMGS = 1; }
-    } else if (full && cout % 256 == 0 && !fromrgb && g.gemmv >= 2 && tuning().wide) {
+    } else if (mode == MODE_NORMAL && full && cout % 256 == 0 && !fromrgb && g.gemmv >= 2 && tuning().wide) {
       // wide layers: one 8-wave workgroup owns 256 output channels of 8x16 pixels; half of its waves run the
       // depthwise stage of the next K chunk while the other half keeps the matrix cores busy (sepconv_wide_kernel)
       g.wide = true; g.NT = 256; GH = 8; GW = 16; IMGS = 1;
-    } else if (full && cout == 256 && with_torgb && tuning().nt256) {
+    } else if (mode == MODE_NORMAL && full && cout == 256 && with_torgb && tuning().nt256) {
       // 256-channel layer followed by ToRGB: one workgroup owns all 256 output channels of 4x16 pixels so the
       // ToRGB tail fuses into its epilogue (saves the feature re-read of torgb_kernel).  Measured on its own the
       // 64 x 256 tile is ~7 % slower than 128 x 128 (2-row depthwise strips, twice the weight-tile traffic), so
@@ -187,22 +191,8 @@ inline Geo choose_geo(int mode, int cin, int cout, int h_in, int w_in, bool from
     else { GH = 8; GW = 16; IMGS = 1; }
     g.sy = GH; g.sx = GW; g.off = 0;
     g.tiles_y = cdiv(h_in, GH); g.tiles_x = cdiv(w_in, GW);
-  } else if (mode == MODE_PW) {
-    // pointwise GEMM at h_in x w_in (second half of a down=2 layer; its input is dwfir_kernel's output)
-    MIGAN_CHECK(!fromrgb, MIGAN_EINVAL, "fromrgb is only fused into plain layers");
-    g.MT = 128; g.KC = 32;
-    if (small) {
-      g.MT = 32; g.NT = 128; GH = 4;
-      if (sq2 && h_in == 4) { GW = 4; IMGS = 2; } else { GW = 8; IMGS = 1; }
-    }
-    else if (sq2 && h_in == 8) { GH = 8; GW = 8; IMGS = 2; }
-    else if (sq2 && h_in == 4) { GH = 4; GW = 4; IMGS = 8; }
-    else { GH = 8; GW = 16; IMGS = 1; }
-    g.sy = GH; g.sx = GW; g.off = 0;
-    g.tiles_y = cdiv(h_in, GH); g.tiles_x = cdiv(w_in, GW);
   } else {
     MIGAN_CHECK(!fromrgb, MIGAN_EINVAL, "fromrgb is only fused into plain layers");
-    g.MT = 128; g.KC = 32;
     if (small >= 2) { g.MT = 32; g.NT = 128; GH = 4; GW = 8; IMGS = 1; }   // 4x8 grid of GEMM pixels, 2x6 interior
     else if (small) { g.MT = 64; g.NT = 128; GH = 8; GW = 8; IMGS = 1; }   // 8x8 grid, 6x6 interior
     else if (sq2 && h_in < 8) { GH = 8; GW = 8; IMGS = 2; }
@@ -219,8 +209,7 @@ inline Geo choose_geo(int mode, int cin, int cout, int h_in, int w_in, bool from
   g.MINW = 2;                                    // 2 workgroups per CU
   // 64-output-channel layers on main tiles (the 512x512 layers): optionally 16-channel K chunks at 3-4 workgroups per CU
   if (g.gemmv == 2 && g.NT == 64 && g.MT == 128 && !g.wide && IMGS == 1 && GW == 16 && GH == 8 && mode != MODE_PW) {
-    const int bit = fromrgb ? 2 : (mode == MODE_UP ? 4 : 1);
-    if (tuning().kc16 & bit) { g.KC = 16; g.MINW = tuning().kc16_minw; }
+    if (tuning().kc16 & layer_bit(fromrgb, mode)) { g.KC = 16; g.MINW = tuning().kc16_minw; }
   }
   MIGAN_CHECK(IMGS * GH * GW == g.MT, MIGAN_EINVAL, "internal: tile geometry does not fill the GEMM tile");
   if (small) {
@@ -243,7 +232,7 @@ inline Geo choose_geo(int mode, int cin, int cout, int h_in, int w_in, bool from
   // are ragged by construction
   g.maing = (IMGS == 1 && GW == 16 && GH == (g.MT == 64 ? 4 : 8)) && (full || mode == MODE_UP);
   if (g.maing && g.gemmv >= 2 && g.NT == 64 && g.MT == 128 && g.KC == 32 && !g.wide && mode != MODE_PW) {
-    const int bit = fromrgb ? 2 : (mode == MODE_UP ? 4 : 1);
+    const int bit = layer_bit(fromrgb, mode);
     // (the plain 3-workgroup tiles are compiled for exactly two K chunks: Cin == 64, the layers they were measured on)
     if ((tuning().w3 & bit) && (bit != 1 || cin == 64)) g.MINW = 3;
   }
@@ -310,31 +299,33 @@ inline const std::vector<KernelEntry>& kernel_table() {
   return t;
 }
 
-// sepconv_wide_kernel<TORGB, STV, X1, BALL, DMA>: x1 = GEMM variant "f16" (one fp16 piece per operand; 16-bit storage only);
-// ball = waves 4-7 run all the MFMAs (tuning().wide >= 2); dma = LDS-DMA staging (tuning().wide == 3, fp32 storage)
-#define MIGAN_WIDE_ROW(T, X, B) {sepconv_wide_kernel<T, 0, X, B>, sepconv_wide_kernel<T, 1, X, B>, sepconv_wide_kernel<T, 2, X, B>}
-#define MIGAN_WIDE_NAMES(T, X, B) {"migan::sepconv_wide_kernel<" #T ", 0, " #X ", " #B ", false, false>", "migan::sepconv_wide_kernel<" #T ", 1, " #X ", " #B ", false, false>", \
-                                   "migan::sepconv_wide_kernel<" #T ", 2, " #X ", " #B ", false, false>"}
-inline bool wide_ball() { return tuning().wide >= 2; }
-inline bool wide_dma(int stv, bool x1) { return tuning().wide == 3 && stv == 0 && !x1; }
-inline SepKernelFn wide_fn(bool torgb, int stv, bool x1 = false, bool ball = false, bool dma = false) {
-  static const SepKernelFn f[2][2][2][3] = {
-      {{MIGAN_WIDE_ROW(false, false, false), MIGAN_WIDE_ROW(true, false, false)}, {MIGAN_WIDE_ROW(false, true, false), MIGAN_WIDE_ROW(true, true, false)}},
-      {{MIGAN_WIDE_ROW(false, false, true), MIGAN_WIDE_ROW(true, false, true)}, {MIGAN_WIDE_ROW(false, true, true), MIGAN_WIDE_ROW(true, true, true)}}};
-  if (x1 && stv == 0) return nullptr;       // the "f16" GEMM variant exists for 16-bit storage only
-  if (dma) return torgb ? sepconv_wide_kernel<true, 0, false, true, true> : sepconv_wide_kernel<false, 0, false, true, true>;
-  return f[ball ? 1 : 0][x1 ? 1 : 0][torgb ? 1 : 0][stv];
+// The kernel families below keep one table each: a row is the function, its symbol as rocprofv3 prints it (one macro spells both) and the
+// dynamic LDS it may ask for (prepare_kernels raises that limit; 0: the default limit will do).
+constexpr size_t kLds96 = 96 * 1024, kLds160 = 160 * 1024;
+
+// sepconv_wide_kernel<TORGB, STV, X1, BALL, DMA, UP>: x1 = GEMM variant "f16" (one fp16 piece per operand; 16-bit storage only: its fp32-storage
+// rows are never picked); ball = waves 4-7 run all the MFMAs (tuning().wide >= 2); dma = LDS-DMA staging (tuning().wide == 3, fp32 storage);
+// up = the FIR-up layer on the same tile
+struct WideEntry { bool torgb; int stv; bool x1, ball, dma, up; SepKernelFn fn; const char* name; size_t max_lds; };
+#define MIGAN_W(T, S, X, B, D, U)                                                                                                 \
+  {T, S, X, B, D, U, sepconv_wide_kernel<T, S, X, B, D, U>, "migan::sepconv_wide_kernel<" #T ", " #S ", " #X ", " #B ", " #D ", " #U ">", \
+   (X && S == 0) ? 0 : kLds160}
+#define MIGAN_W3(T, X, B) MIGAN_W(T, 0, X, B, false, false), MIGAN_W(T, 1, X, B, false, false), MIGAN_W(T, 2, X, B, false, false)
+inline const std::vector<WideEntry>& wide_table() {
+  static const std::vector<WideEntry> t = {
+      MIGAN_W3(false, false, false), MIGAN_W3(true, false, false), MIGAN_W3(false, true, false), MIGAN_W3(true, true, false),
+      MIGAN_W3(false, false, true),  MIGAN_W3(true, false, true),  MIGAN_W3(false, true, true),  MIGAN_W3(true, true, true),
+      MIGAN_W(false, 0, false, true, true, false), MIGAN_W(true, 0, false, true, true, false), MIGAN_W(false, 0, false, true, true, true)};
+  return t;
 }
-inline SepKernelFn wide_up_fn() { return sepconv_wide_kernel<false, 0, false, true, true, true>; }
-constexpr const char* kWideUpName = "migan::sepconv_wide_kernel<false, 0, false, true, true, true>";
-inline const char* wide_name(const Geo& g) {
-  if (g.mode == MODE_UP) return kWideUpName;
-  static const char* n[2][2][2][3] = {
-      {{MIGAN_WIDE_NAMES(false, false, false), MIGAN_WIDE_NAMES(true, false, false)}, {MIGAN_WIDE_NAMES(false, true, false), MIGAN_WIDE_NAMES(true, true, false)}},
-      {{MIGAN_WIDE_NAMES(false, false, true), MIGAN_WIDE_NAMES(true, false, true)}, {MIGAN_WIDE_NAMES(false, true, true), MIGAN_WIDE_NAMES(true, true, true)}}};
-  if (wide_dma(g.stv, g.gemmv == 3))
-    return g.torgb ? "migan::sepconv_wide_kernel<true, 0, false, true, true, false>" : "migan::sepconv_wide_kernel<false, 0, false, true, true, false>";
-  return n[wide_ball() ? 1 : 0][g.gemmv == 3 ? 1 : 0][g.torgb ? 1 : 0][g.stv];
+#undef MIGAN_W3
+#undef MIGAN_W
+inline const WideEntry& wide_entry(const Geo& g) {
+  const bool up = g.mode == MODE_UP, x1 = g.gemmv == 3;
+  const bool dma = up || (tuning().wide == 3 && g.stv == 0 && !x1), ball = dma || tuning().wide >= 2;
+  for (const WideEntry& e : wide_table())
+    if (e.max_lds && e.torgb == g.torgb && e.stv == g.stv && e.x1 == x1 && e.ball == ball && e.dma == dma && e.up == up) return e;
+  throw Error(MIGAN_EINVAL, "internal: no wide-tile kernel instantiation for this geometry");
 }
 // symbol of the fused-SeparableConv2d kernel this thread launched last (migan_last_kernel: tests ask which form ran)
 inline const char*& last_kernel_ref() {
@@ -346,15 +337,14 @@ inline const char*& last_kernel_ref() {
 // from batch 2 on for the layers that have an instantiation), so an image is bit-identical whatever batch >= 2 it is in.
 PipeSlice pipe_slice();
 inline bool PipeResident(const PipeEntry& e) { return (e.cin / 32) * (2 * e.NT * 64) <= 32 * 1024; }    // all weight planes of a column tile stay in LDS
-inline const PipeEntry* pick_pipe(const Geo& g, int cin, int cout, int batch, bool fused_rgb, bool u8, bool has_skip = false) {
-  const int bit = g.fromrgb ? 2 : (g.mode == MODE_UP ? 4 : 1);
+inline const PipeEntry* pick_pipe(const Geo& g, int cin, int cout, int batch, bool fused_rgb, bool has_skip = false) {
+  const int bit = layer_bit(g.fromrgb, g.mode);
   // the plain epilogue of the pipelined kernels has no skip add (no layer of the generator needs one there: its only plain + skip layer is the
   // 512-channel synthesis.b4.conv1); a plain SeparableConv2d with a skip tensor through migan_sepconv_forward keeps the one-tile kernels
   if (g.mode == MODE_NORMAL && has_skip) return nullptr;
   if (!(tuning().pipe & bit) || g.stv != 0 || g.gemmv != 2 || !g.maing || g.wide || g.MT != 128 || g.KC != 32 || g.lgIMGS != 0) return nullptr;
   if (g.mode != MODE_NORMAL && g.mode != MODE_UP) return nullptr;
   if (batch < tuning().pipe_min_batch || g.tiles_x * g.tiles_y * g.nchunks * batch < tuning().pipe_min_tiles) return nullptr;
-  (void)u8;
   const PipeSlice sl = pipe_slice();
   for (int i = 0; i < sl.n; ++i) {
     const PipeEntry& e = sl.entries[i];
@@ -392,25 +382,30 @@ inline const DownEntry* pick_pipedown(int cin, int cout, int h_in, int w_in, int
 // sepconv_wide2_kernel (migan_wide2.hpp): persistent 16 x 16-pixel x 256-channel tiles for the plain layers the 128 x 256 wide tile serves, where
 // the launch fills the chip with them.  The choice depends on the batch (tiles per image: 64 at 128 x 128, 16 at 64 x 64): the two forms sum
 // a layer's K chunks in the same order with the same operand split, so an image does not depend on which one ran (tests compare them bit for bit).
+// Its pointwise form (variant 3) serves the second half of a down=2 layer that is not fused (Cout = 512: encoder.b128 / b64 .conv2 of migan-512):
+// the 128-column pointwise tiles re-read their A operand per column chunk (measured traffic 1.70x algorithmic), this one reads it once per 256.
 SepKernelFn wide2_fn(int variant);
-// tuning().w2: 0 off | 1 weight planes DMA'd as 16-channel halves (four 16 KB slots) | 2 (default) as whole 32-channel chunks (two 32 KB slots)
-inline int wide2_variant() { return tuning().w2 == 1 ? 0 : 1; }
-inline const char* wide2_name() { return wide2_variant() ? "migan::sepconv_wide2_kernel<1>" : "migan::sepconv_wide2_kernel<0>"; }
-inline bool use_wide2(const Geo& g, int cin, int cout, int batch, bool fused_rgb, bool has_skip, bool u8) {
-  if (!tuning().w2 || !g.wide || g.mode != MODE_NORMAL || g.stv != 0 || g.gemmv != 2 || g.fromrgb || fused_rgb || has_skip || u8) return false;
-  const int h = g.tiles_y * 8, w = g.tiles_x * 16;               // (wide tiles are whole 8 x 16 tiles)
-  if (h % 16 != 0 || w % 16 != 0 || cin % 64 != 0 || cout % 256 != 0) return false;
-  return (h / 16) * (w / 16) * (cout / 256) * batch >= tuning().w2_min_tiles;
+struct Wide2Entry { int variant; SepKernelFn fn; const char* name; size_t max_lds; };
+#define MIGAN_W2(V) {V, wide2_fn(V), "migan::sepconv_wide2_kernel<" #V ">", kLds160}
+inline const std::vector<Wide2Entry>& wide2_table() {
+  static const std::vector<Wide2Entry> t = {MIGAN_W2(0), MIGAN_W2(1), MIGAN_W2(3)};
+  return t;
 }
-// ... and its pointwise form for the second half of a down=2 layer that is not fused (Cout = 512: encoder.b128 / b64 .conv2 of migan-512): the
-// 128-column pointwise tiles re-read their A operand per column chunk (measured traffic 1.70x algorithmic), this one reads it once per 256
-constexpr const char* kWide2PwName = "migan::sepconv_wide2_kernel<3>";
-inline bool use_wide2_pw(const Geo& g, int cin, int cout, int h, int w, int batch, bool has_skip) {
-  if (!tuning().w2 || !tuning().w2_pw || g.mode != MODE_PW || !g.maing || g.stv != 0 || g.gemmv != 2 || has_skip) return false;
-  if (h % 16 != 0 || w % 16 != 0 || cin % 64 != 0 || cout % 256 != 0) return false;
-  return (h / 16) * (w / 16) * (cout / 256) * batch >= tuning().w2_min_tiles;
+#undef MIGAN_W2
+// the row a launch of `batch` images takes, or nullptr.  tuning().w2: 0 off | 1 weight planes DMA'd as 16-channel halves (four 16 KB slots, variant 0) |
+// 2 (default) as whole 32-channel chunks (two 32 KB slots, variant 1)
+inline const Wide2Entry* pick_wide2(const Geo& g, const SepArgs& a, int batch) {
+  if (!tuning().w2 || g.stv != 0 || g.gemmv != 2 || a.skip != nullptr) return nullptr;
+  int variant;
+  if (g.mode == MODE_NORMAL && g.wide && !g.fromrgb && a.trgb_w == nullptr && a.u8_img == nullptr) variant = tuning().w2 == 1 ? 0 : 1;
+  else if (g.mode == MODE_PW && g.maing && tuning().w2_pw) variant = 3;
+  else return nullptr;
+  if (a.H % 16 != 0 || a.W % 16 != 0 || a.CI % 64 != 0 || a.CO % 256 != 0) return nullptr;      // whole 16 x 16 tiles
+  if ((a.H / 16) * (a.W / 16) * (a.CO / 256) * batch < tuning().w2_min_tiles) return nullptr;
+  for (const Wide2Entry& e : wide2_table())
+    if (e.variant == variant) return &e;
+  return nullptr;
 }
-inline const char* kernel_name(const Geo& g);
 inline const KernelEntry& pick_kernel(const Geo& g) {
   for (const auto& e : kernel_table())
     if (e.mode == g.mode && e.MT == g.MT && e.NT == g.NT && e.KC == g.KC && e.fromrgb == g.fromrgb && e.NI == g.NI &&
@@ -419,7 +414,7 @@ inline const KernelEntry& pick_kernel(const Geo& g) {
   throw Error(MIGAN_EINVAL, "internal: no kernel instantiation for this geometry");
 }
 
-inline const char* kernel_name(const Geo& g) { return g.wide ? wide_name(g) : pick_kernel(g).name; }
+inline const char* kernel_name(const Geo& g) { return g.wide ? wide_entry(g).name : pick_kernel(g).name; }
 
 // persistent variants exist where they fit the register budget without spilling
 inline bool has_persistent_variant(const Geo& g) {
@@ -461,44 +456,53 @@ typedef void (*DwFirKernelFn)(const DwFirArgs);
 // stv: activation storage format 0/1/2; + 2 (3/4) when the pointwise GEMM behind it is the "f16" variant and takes its A operand
 // ready-made (dwfir_variant)
 inline int dwfir_variant(int stv, int gemmv) { return (gemmv == 3 && stv != 0) ? stv + 2 : stv; }
-inline const char* dwfir_name(const DwGeo& g, int stv = 0) {
-  static const char* n[2][5] = {{"migan::dwfir_kernel<9, false, 0>", "migan::dwfir_kernel<9, false, 1>", "migan::dwfir_kernel<9, false, 2>",
-                                 "migan::dwfir_kernel<9, false, 3>", "migan::dwfir_kernel<9, false, 4>"},
-                                {"migan::dwfir_kernel<7, true, 0>", "migan::dwfir_kernel<7, true, 1>", "migan::dwfir_kernel<7, true, 2>",
-                                 "migan::dwfir_kernel<7, true, 3>", "migan::dwfir_kernel<7, true, 4>"}};
-  return n[g.maing ? 1 : 0][stv];
+struct DwFirEntry { bool maing; int variant; DwFirKernelFn fn; const char* name; size_t max_lds; };
+#define MIGAN_DW(NI, MAING, V) {MAING, V, dwfir_kernel<NI, MAING, V>, "migan::dwfir_kernel<" #NI ", " #MAING ", " #V ">", kLds96}
+inline const std::vector<DwFirEntry>& dwfir_table() {
+  static const std::vector<DwFirEntry> t = {MIGAN_DW(9, false, 0), MIGAN_DW(9, false, 1), MIGAN_DW(9, false, 2), MIGAN_DW(9, false, 3), MIGAN_DW(9, false, 4),
+                                            MIGAN_DW(7, true, 0),  MIGAN_DW(7, true, 1),  MIGAN_DW(7, true, 2),  MIGAN_DW(7, true, 3),  MIGAN_DW(7, true, 4)};
+  return t;
 }
-inline DwFirKernelFn dwfir_fn(bool maing, int stv) {
-  static const DwFirKernelFn f[2][5] = {{dwfir_kernel<9, false, 0>, dwfir_kernel<9, false, 1>, dwfir_kernel<9, false, 2>,
-                                         dwfir_kernel<9, false, 3>, dwfir_kernel<9, false, 4>},
-                                        {dwfir_kernel<7, true, 0>, dwfir_kernel<7, true, 1>, dwfir_kernel<7, true, 2>,
-                                         dwfir_kernel<7, true, 3>, dwfir_kernel<7, true, 4>}};
-  return f[maing ? 1 : 0][stv];
+#undef MIGAN_DW
+inline const DwFirEntry& dwfir_entry(const DwGeo& g, int variant = 0) {
+  for (const DwFirEntry& e : dwfir_table())
+    if (e.maing == g.maing && e.variant == variant) return e;
+  throw Error(MIGAN_EINVAL, "internal: no dwfir_kernel instantiation of this variant");
 }
 typedef void (*RgbKernelFn)(const RgbArgs);
-inline RgbKernelFn torgb_fn(int stv) {
-  static const RgbKernelFn f[3] = {torgb_kernel<0>, torgb_kernel<1>, torgb_kernel<2>};
-  return f[stv];
+struct RgbEntry { int stv; RgbKernelFn fn; const char* name; size_t max_lds; };
+#define MIGAN_RGB(S) {S, torgb_kernel<S>, "migan::torgb_kernel<" #S ">", 0}
+inline const std::vector<RgbEntry>& torgb_table() {
+  static const std::vector<RgbEntry> t = {MIGAN_RGB(0), MIGAN_RGB(1), MIGAN_RGB(2)};
+  return t;
 }
-inline const char* torgb_name(int stv) {
-  static const char* n[3] = {"migan::torgb_kernel<0>", "migan::torgb_kernel<1>", "migan::torgb_kernel<2>"};
-  return n[stv];
+#undef MIGAN_RGB
+inline const RgbEntry& torgb_entry(int stv) {
+  for (const RgbEntry& e : torgb_table())
+    if (e.stv == stv) return e;
+  throw Error(MIGAN_EINVAL, "internal: no torgb_kernel for this storage format");
 }
 
 // layers with fewer than 64 channels (resolutions above 512): one plain kernel per (down / up, fromrgb)
 // (the tiled kernels take Cin % 32 == 0 and Cout % 64 == 0: choose_geo)
 inline bool is_narrow(int cin, int cout) { return cin % 32 != 0 || cout % 64 != 0; }
-inline SepKernelFn narrow_fn(int mode, bool fromrgb) {
-  if (fromrgb) return narrow_sepconv_kernel<MODE_NORMAL, true>;
-  return mode == MODE_DOWN ? narrow_sepconv_kernel<MODE_DOWN, false> : (mode == MODE_UP ? narrow_sepconv_kernel<MODE_UP, false> : narrow_sepconv_kernel<MODE_NORMAL, false>);
+// (dynamic LDS: the 18 x 18 x Cout fp32 tile of the FIR-up form, 81 KiB at Cout = 64: launch_narrow; the other forms take none)
+struct NarrowEntry { int mode; bool fromrgb; SepKernelFn fn; const char* name; size_t max_lds; };
+#define MIGAN_N(MODE, RGB) {MODE, RGB, narrow_sepconv_kernel<MODE, RGB>, "migan::narrow_sepconv_kernel<" #MODE ", " #RGB ">", kLds96}
+inline const std::vector<NarrowEntry>& narrow_table() {
+  static_assert(MODE_NORMAL == 0 && MODE_DOWN == 1 && MODE_UP == 2, "the rows below spell the modes as rocprofv3 prints them");
+  static const std::vector<NarrowEntry> t = {MIGAN_N(0, true), MIGAN_N(0, false), MIGAN_N(1, false), MIGAN_N(2, false)};
+  return t;
 }
-inline const char* narrow_name(int mode, bool fromrgb) {
-  if (fromrgb) return "migan::narrow_sepconv_kernel<0, true>";
-  return mode == MODE_DOWN ? "migan::narrow_sepconv_kernel<1, false>" : (mode == MODE_UP ? "migan::narrow_sepconv_kernel<2, false>" : "migan::narrow_sepconv_kernel<0, false>");
+#undef MIGAN_N
+inline const NarrowEntry& narrow_entry(int mode, bool fromrgb) {
+  for (const NarrowEntry& e : narrow_table())
+    if (e.fromrgb == fromrgb && (fromrgb || e.mode == mode)) return e;      // (FromRGB: the plain form, whatever the mode)
+  throw Error(MIGAN_EINVAL, "internal: no narrow kernel for this mode");
 }
 
 // (a.B / H / W / HO / WO / CI / CO set by the caller)
-inline void launch_narrow(int mode, bool fromrgb, SepArgs a, rt::stream_t stream) {
+inline const char* launch_narrow(int mode, bool fromrgb, SepArgs a, rt::stream_t stream) {
   unsigned grid;
   size_t lds = 0;
   if (mode == MODE_UP) {           // one workgroup per 16 x 16 low-resolution pixels, their 18 x 18 1x1 outputs in LDS
@@ -508,8 +512,9 @@ inline void launch_narrow(int mode, bool fromrgb, SepArgs a, rt::stream_t stream
   } else {                         // one thread per output pixel
     grid = (unsigned)(((size_t)a.B * a.HO * a.WO + kThreads - 1) / kThreads);
   }
-  rt_check(rt::launch(narrow_fn(mode, fromrgb), a, grid, kThreads, lds, stream), narrow_name(mode, fromrgb));
-  last_kernel_ref() = narrow_name(mode, fromrgb);
+  const NarrowEntry& e = narrow_entry(mode, fromrgb);
+  rt_check(rt::launch(e.fn, a, grid, kThreads, lds, stream), e.name);
+  return last_kernel_ref() = e.name;
 }
 
 // Raise the dynamic-LDS limit of every instantiation (tiles use up to 145 KiB).  The attribute is per device, so
@@ -521,30 +526,19 @@ inline void prepare_kernels() {
   rt_check(rt::get_device(&dev), "hipGetDevice");
   std::lock_guard<std::mutex> lock(mu);
   if (dev >= 0 && dev < (int)done.size() && done[dev]) return;
-  for (const auto& e : kernel_table()) rt_check(rt::allow_dynamic_lds((const void*)e.fn, 96 * 1024), "hipFuncSetAttribute");
-  // narrow FIR-up: the 18 x 18 x Cout fp32 tile of launch_narrow (81 KiB at Cout = 64); the other forms take no dynamic LDS
-  for (int m : {MODE_NORMAL, MODE_DOWN, MODE_UP})
-    rt_check(rt::allow_dynamic_lds((const void*)narrow_fn(m, false), 96 * 1024), "hipFuncSetAttribute");
-  rt_check(rt::allow_dynamic_lds((const void*)narrow_fn(MODE_NORMAL, true), 96 * 1024), "hipFuncSetAttribute");
-  {
-    const PipeSlice sl = pipe_slice();
-    for (int i = 0; i < sl.n; ++i) rt_check(rt::allow_dynamic_lds((const void*)sl.entries[i].fn, 160 * 1024), "hipFuncSetAttribute");
-    const DownSlice ds = pipedown_slice();
-    for (int i = 0; i < ds.n; ++i) rt_check(rt::allow_dynamic_lds((const void*)ds.entries[i].fn, 160 * 1024), "hipFuncSetAttribute");
-  }
-  for (int t = 0; t < 2; ++t)
-    for (int sv = 0; sv < 3; ++sv) {
-      for (int ball = 0; ball < 2; ++ball) {
-        rt_check(rt::allow_dynamic_lds((const void*)wide_fn(t != 0, sv, false, ball != 0), 160 * 1024), "hipFuncSetAttribute");
-        if (sv) rt_check(rt::allow_dynamic_lds((const void*)wide_fn(t != 0, sv, true, ball != 0), 160 * 1024), "hipFuncSetAttribute");
-      }
-      if (sv == 0) rt_check(rt::allow_dynamic_lds((const void*)wide_fn(t != 0, 0, false, true, true), 160 * 1024), "hipFuncSetAttribute");
-      if (sv == 0 && t == 0) rt_check(rt::allow_dynamic_lds((const void*)wide_up_fn(), 160 * 1024), "hipFuncSetAttribute");
-      if (sv == 0 && t == 0)
-        for (int v : {0, 1, 3}) rt_check(rt::allow_dynamic_lds((const void*)wide2_fn(v), 160 * 1024), "hipFuncSetAttribute");
-      rt_check(rt::allow_dynamic_lds((const void*)dwfir_fn(t != 0, sv), 96 * 1024), "hipFuncSetAttribute");
-      if (sv) rt_check(rt::allow_dynamic_lds((const void*)dwfir_fn(t != 0, sv + 2), 96 * 1024), "hipFuncSetAttribute");
-    }
+  const auto raise = [](const void* fn, size_t bytes) {
+    if (bytes) rt_check(rt::allow_dynamic_lds(fn, bytes), "hipFuncSetAttribute");
+  };
+  for (const auto& e : kernel_table()) raise((const void*)e.fn, kLds96);
+  const PipeSlice ps = pipe_slice();
+  for (int i = 0; i < ps.n; ++i) raise((const void*)ps.entries[i].fn, kLds160);
+  const DownSlice ds = pipedown_slice();
+  for (int i = 0; i < ds.n; ++i) raise((const void*)ds.entries[i].fn, kLds160);
+  for (const auto& e : wide_table()) raise((const void*)e.fn, e.max_lds);
+  for (const auto& e : wide2_table()) raise((const void*)e.fn, e.max_lds);
+  for (const auto& e : dwfir_table()) raise((const void*)e.fn, e.max_lds);
+  for (const auto& e : torgb_table()) raise((const void*)e.fn, e.max_lds);
+  for (const auto& e : narrow_table()) raise((const void*)e.fn, e.max_lds);
   if (dev >= (int)done.size()) done.resize(dev + 1, 0);
   if (dev >= 0) done[dev] = 1;
 }
@@ -586,6 +580,26 @@ inline std::vector<ProfRow>& prof_layers() {
 }
 #endif
 
+// Parameters of one SeparableConv2d and of the FromRGB / ToRGB fused around it (null: absent), wherever they live: plan slots or a migan_sepconv_desc
+struct SepParams {
+  const float *wdw = nullptr, *bdw = nullptr, *wpw = nullptr;
+  const unsigned short* wsplit = nullptr;      // null: the exact-fp32 GEMM
+  const float *noise = nullptr, *noise_strength = nullptr, *frgb_w = nullptr, *frgb_b = nullptr, *trgb_w = nullptr, *trgb_b = nullptr, *img_prev = nullptr;
+  float* img_out = nullptr;
+};
+// tensor and shape part of a launch's SepArgs (tile geometry: fill_geo or the launcher; uint8 I/O pointers: the caller)
+inline SepArgs sep_args(const SepParams& p, const void* x, void* y, const void* skip, int B, int H, int W, int CI, int CO, int HO, int WO) {
+  SepArgs a{};
+  a.x = x; a.y = y; a.skip = skip;
+  a.wdw = p.wdw; a.bdw = p.bdw; a.wpw = p.wpw; a.wsplit = p.wsplit;
+  a.noise = p.noise; a.noise_strength = p.noise_strength;
+  a.frgb_w = p.frgb_w; a.frgb_b = p.frgb_b;
+  a.trgb_w = p.trgb_w; a.trgb_b = p.trgb_b;
+  a.img_prev = p.img_prev; a.img_out = p.img_out;
+  a.B = B; a.H = H; a.W = W; a.CI = CI; a.CO = CO; a.HO = HO; a.WO = WO;
+  return a;
+}
+
 inline void fill_geo(SepArgs& a, const Geo& g) {
   a.lgGH = g.lgGH; a.lgGW = g.lgGW; a.lgIMGS = g.lgIMGS;
   a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y; a.nchunks = g.nchunks;
@@ -613,44 +627,36 @@ inline unsigned grid_of(const Geo& g, int batch, bool fused_rgb = false) {
   return use_persistent(g, batch, fused_rgb) ? (unsigned)tuning().persist_grid : tiles_of(g, batch);
 }
 
-// name of the kernel launch_sepconv runs for this geometry and batch
-inline const char* launched_kernel_name(Geo g, int cin, int cout, int batch, bool fused_rgb, bool has_skip);
-
-// n_decide: the batch the kernel FORM is chosen for (0 = a.B).  The per-launch timing run launches the whole batch at once but must time the
-// forms the production forward -- sub-batches on staggered streams -- launches.
-inline void launch_sepconv(Geo g, const SepArgs& a, rt::stream_t stream, int n_decide = 0) {
-  prepare_kernels();
+// One fused-SeparableConv2d launch, decided: what rt::launch gets, and the symbol that migan_last_kernel / migan_launch_info report.
+struct SepLaunch {
+  SepKernelFn fn;
+  const char* name;
+  unsigned grid, threads;
+  size_t lds_bytes;
+  SepArgs args;                    // the caller's, with what the chosen family lays out itself overridden
+};
+// The kernel family of a launch, first match: pipelined persistent form, 256 x 256 tile, 128 x 256 wide tile, sepconv_kernel table.
+// n_decide: the batch the kernel FORM is chosen for (0 = a.B); grids are sized for a.B, the batch actually launched.  The per-launch timing run
+// launches the whole batch at once but must time the forms the production forward -- sub-batches on staggered streams -- launches.
+inline SepLaunch resolve_sepconv(Geo g, const SepArgs& a, int n_decide = 0) {
   const bool fused_rgb = a.trgb_w != nullptr;
   const int nd = n_decide > 0 ? n_decide : a.B;
-  if (const PipeEntry* pe = pick_pipe(g, a.CI, a.CO, nd, fused_rgb, a.u8_img != nullptr, a.skip != nullptr)) {
+  const unsigned pipe_grid = (unsigned)tuning().pipe_grid;
+  if (const PipeEntry* pe = pick_pipe(g, a.CI, a.CO, nd, fused_rgb, a.skip != nullptr)) {
     MIGAN_CHECK(a.wsplit != nullptr, MIGAN_EINVAL, "internal: the pipelined kernel needs the fp16 weight planes");
-    SepArgs ap = a;
-    ap.nchunks = a.CO / pe->NT;                          // (FIR-up: 64-column chunks, see pick_pipe)
-    const unsigned tiles = (unsigned)(g.tiles_x * g.tiles_y * ap.nchunks * a.B);
-    const unsigned grid = std::min(tiles, (unsigned)tuning().pipe_grid);
-    rt_check(rt::launch(pe->fn, ap, grid, (unsigned)pipe_threads(pe->na), pe->lds_bytes, stream), pe->name);
-    last_kernel_ref() = pe->name;
-    return;
+    SepLaunch l{pe->fn, pe->name, 0, (unsigned)pipe_threads(pe->na), pe->lds_bytes, a};
+    l.args.nchunks = a.CO / pe->NT;                      // (FIR-up: 64-column chunks, see pick_pipe)
+    l.grid = std::min((unsigned)(g.tiles_x * g.tiles_y * l.args.nchunks * a.B), pipe_grid);
+    return l;
   }
-  if (use_wide2(g, a.CI, a.CO, nd, fused_rgb, a.skip != nullptr, a.u8_img != nullptr)) {
+  if (const Wide2Entry* we = pick_wide2(g, a, nd)) {
     MIGAN_CHECK(a.wsplit != nullptr, MIGAN_EINVAL, "internal: the 256 x 256 tile kernel needs the fp16 weight planes");
-    SepArgs aw = a;
+    SepLaunch l{we->fn, we->name, 0, (unsigned)kW2Threads, (size_t)W2Lds::TOTAL, a};
+    SepArgs& aw = l.args;
     aw.tiles_x = a.W / 16; aw.tiles_y = a.H / 16; aw.nchunks = a.CO / 256;
     aw.sy = 16; aw.sx = 16; aw.off = 0;
-    const unsigned tiles = (unsigned)(aw.tiles_x * aw.tiles_y * aw.nchunks * a.B);
-    rt_check(rt::launch(wide2_fn(wide2_variant()), aw, std::min(tiles, (unsigned)tuning().pipe_grid), (unsigned)kW2Threads, (size_t)W2Lds::TOTAL, stream), wide2_name());
-    last_kernel_ref() = wide2_name();
-    return;
-  }
-  if (use_wide2_pw(g, a.CI, a.CO, a.H, a.W, nd, a.skip != nullptr)) {
-    MIGAN_CHECK(a.wsplit != nullptr, MIGAN_EINVAL, "internal: the 256 x 256 tile kernel needs the fp16 weight planes");
-    SepArgs aw = a;
-    aw.tiles_x = a.W / 16; aw.tiles_y = a.H / 16; aw.nchunks = a.CO / 256;
-    aw.sy = 16; aw.sx = 16; aw.off = 0;
-    const unsigned tiles = (unsigned)(aw.tiles_x * aw.tiles_y * aw.nchunks * a.B);
-    rt_check(rt::launch(wide2_fn(3), aw, std::min(tiles, (unsigned)tuning().pipe_grid), (unsigned)kW2Threads, (size_t)W2Lds::TOTAL, stream), kWide2PwName);
-    last_kernel_ref() = kWide2PwName;
-    return;
+    l.grid = std::min((unsigned)(aw.tiles_x * aw.tiles_y * aw.nchunks * a.B), pipe_grid);
+    return l;
   }
   g.persist = use_persistent(g, a.B, fused_rgb);      // (grid size: the batch actually launched)
   g.torgb = fused_rgb;
@@ -658,34 +664,34 @@ inline void launch_sepconv(Geo g, const SepArgs& a, rt::stream_t stream, int n_d
               "ToRGB can only be fused into a plain layer whose output channels fit one column tile");
   if (g.wide) {
     MIGAN_CHECK(a.wsplit != nullptr, MIGAN_EINVAL, "internal: the wide kernel needs the fp16 weight planes");
-    const SepKernelFn fn = g.mode == MODE_UP ? wide_up_fn() : wide_fn(fused_rgb, g.stv, g.gemmv == 3, wide_ball(), wide_dma(g.stv, g.gemmv == 3));
-    rt_check(rt::launch(fn, a, tiles_of(g, a.B), kWideThreads, g.lds_bytes, stream), wide_name(g));
-    last_kernel_ref() = wide_name(g);
-    return;
+    const WideEntry& e = wide_entry(g);
+    return SepLaunch{e.fn, e.name, tiles_of(g, a.B), (unsigned)kWideThreads, g.lds_bytes, a};
   }
   const KernelEntry& k = pick_kernel(g);
-  rt_check(rt::launch(k.fn, a, grid_of(g, a.B, fused_rgb), kThreads, g.lds_bytes, stream), k.name);
-  last_kernel_ref() = k.name;
+  return SepLaunch{k.fn, k.name, grid_of(g, a.B, fused_rgb), (unsigned)kThreads, g.lds_bytes, a};
+}
+// returns the symbol it launched
+inline const char* launch_sepconv(const Geo& g, const SepArgs& a, rt::stream_t stream, int n_decide = 0) {
+  prepare_kernels();
+  const SepLaunch l = resolve_sepconv(g, a, n_decide);
+  rt_check(rt::launch(l.fn, l.args, l.grid, l.threads, l.lds_bytes, stream), l.name);
+  return last_kernel_ref() = l.name;
 }
 
-// (has_skip: the decisions launch_sepconv takes with a.skip != nullptr -- a plain or pointwise layer with a skip tensor keeps the one-tile kernels)
-inline const char* launched_kernel_name(Geo g, int cin, int cout, int batch, bool fused_rgb, bool has_skip) {
-  if (const PipeEntry* pe = pick_pipe(g, cin, cout, batch, fused_rgb, false, has_skip)) return pe->name;
-  if (use_wide2(g, cin, cout, batch, fused_rgb, has_skip, false)) return wide2_name();
-  if (use_wide2_pw(g, cin, cout, g.tiles_y * g.sy, g.tiles_x * g.sx, batch, has_skip)) return kWide2PwName;      // (maing: whole 8 x 16 tiles)
-  g.persist = use_persistent(g, batch, fused_rgb);
-  g.torgb = fused_rgb;
-  return kernel_name(g);
+// The fused form of the down=2 layer `a` describes (x, H, W: the layer's own input), or nullptr: dwfir_kernel + pointwise GEMM.
+// sepconv_pipedown_kernel has no FromRGB / ToRGB / noise / skip and needs the fp16 weight planes.
+inline const DownEntry* pick_fused_down(const SepArgs& a, int n_decide, int stv, int gemmv) {
+  if (a.frgb_w || a.trgb_w || a.noise || a.skip || a.wsplit == nullptr) return nullptr;
+  return pick_pipedown(a.CI, a.CO, a.H, a.W, n_decide, stv, gemmv);
 }
-
-inline void launch_pipedown(const DownEntry& e, SepArgs a, rt::stream_t stream) {
+inline const char* launch_pipedown(const DownEntry& e, SepArgs a, rt::stream_t stream) {
   prepare_kernels();
   MIGAN_CHECK(a.wsplit != nullptr, MIGAN_EINVAL, "internal: the fused down=2 kernel needs the fp16 weight planes");
   a.tiles_x = a.W / 32; a.tiles_y = a.H / 8; a.nchunks = 1;
   a.prof = prof_buffer();
   const unsigned tiles = (unsigned)(a.tiles_x * a.tiles_y * a.B);
   rt_check(rt::launch(e.fn, a, std::min(tiles, (unsigned)tuning().pipe_grid), (unsigned)((e.na + e.nb) * 64), e.lds_bytes, stream), e.name);
-  last_kernel_ref() = e.name;
+  return last_kernel_ref() = e.name;
 }
 inline void launch_dwfir(const DwGeo& g, DwFirArgs a, rt::stream_t stream, int stv = 0) {
   prepare_kernels();
@@ -697,7 +703,8 @@ inline void launch_dwfir(const DwGeo& g, DwFirArgs a, rt::stream_t stream, int s
   unsigned grid = dwfir_grid(g, a.B);
   if (tuning().small && tuning().small_dwfir)
     while (a.kpw > 1 && grid * 2 <= (unsigned)tuning().small_max_wgs) { a.kpw /= 2; a.nkg *= 2; grid *= 2; }
-  rt_check(rt::launch(dwfir_fn(g.maing, stv), a, grid, kThreads, g.lds_bytes, stream), dwfir_name(g, stv));
+  const DwFirEntry& e = dwfir_entry(g, stv);
+  rt_check(rt::launch(e.fn, a, grid, kThreads, g.lds_bytes, stream), e.name);
 }
 
 // 16-bit elements one tensor occupies in a weight-split buffer: header + planes, rounded to 16 bytes
@@ -712,7 +719,8 @@ inline void launch_split(const SplitArgs& a, rt::stream_t stream) {
 inline void launch_torgb(const RgbArgs& a, rt::stream_t stream, int stv = 0) {
   const size_t npix = (size_t)a.B * a.H * a.W;
   const unsigned grid = (unsigned)((npix * 16 + kThreads - 1) / kThreads);
-  rt_check(rt::launch(torgb_fn(stv), a, grid, kThreads, 0, stream), torgb_name(stv));
+  const RgbEntry& e = torgb_entry(stv);
+  rt_check(rt::launch(e.fn, a, grid, kThreads, 0, stream), e.name);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -970,7 +978,7 @@ inline void migan_handle::build_plan(migan::Plan& P, int H, int W) const {
       MIGAN_CHECK(stv == 0, MIGAN_EUNSUPPORTED, "resolutions above 512 (layers with fewer than 64 channels) run with fp32 activation storage only");
       MIGAN_CHECK(cin % 4 == 0 && cout % 4 == 0 && cin <= 64 && cout <= 64, MIGAN_EINVAL, "internal: narrow layer with unexpected channel counts");
       L.g.mode = mode; L.g.nchunks = 1;                // (no tile geometry: one thread per output pixel)
-      L.kernel = narrow_name(mode, fromrgb);
+      L.kernel = narrow_entry(mode, fromrgb).name;
     } else {
       L.g = choose_geo(mode, cin, cout, L.hin, L.win, fromrgb, with_torgb, gemm, stv);
       L.g.torgb = with_torgb && L.g.nchunks == 1;        // one workgroup owns all channels of its pixels: ToRGB fuses
@@ -1042,7 +1050,7 @@ inline void migan_handle::build_plan(migan::Plan& P, int H, int W) const {
         L.is_dwfir = true;
         L.hin = hs(res); L.win = ws(res); L.hout = hs(res / 2); L.wout = ws(res / 2);
         L.dg = choose_dwfir_geo(c, L.hin, L.win);
-        L.kernel = dwfir_name(L.dg, dwfir_variant(stv, gemm));
+        L.kernel = dwfir_entry(L.dg, dwfir_variant(stv, gemm)).name;
         L.cin = c; L.cout = c;
         L.in_buf = feat[ilog2(res)]; L.out_buf = DWT;
         L.w_dw = slot_index(b + ".conv2.conv1.weight");
@@ -1096,7 +1104,7 @@ inline void migan_handle::build_plan(migan::Plan& P, int H, int W) const {
     } else {
       Launch L;
       L.layer = b + ".torgb";
-      L.kernel = torgb_name(stv);
+      L.kernel = torgb_entry(stv).name;
       L.is_rgb = true;
       L.cin = c; L.cout = 3;
       L.hin = L.hout = hs(res); L.win = L.wout = ws(res);
@@ -1166,30 +1174,39 @@ inline void migan_handle::run_range(const migan::Plan& P, const float* x, float*
   };
   auto wptr = [&](int s) -> const float* { return s < 0 ? nullptr : slots[s].ptr; };
   unsigned short* wsplit = reinterpret_cast<unsigned short*>(shared);
+  auto params_of = [&](const Launch& L) {
+    SepParams p;
+    p.wdw = wptr(L.w_dw); p.bdw = wptr(L.b_dw); p.wpw = wptr(L.w_pw);
+    p.wsplit = !L.narrow && L.g.gemmv ? wsplit + L.wsplit_off : nullptr;      // (narrow layers read conv2.weight in fp32)
+    p.noise = L.noise_plane_off >= 0 ? reinterpret_cast<const float*>(shared + L.noise_plane_off) : wptr(L.w_noise);
+    p.noise_strength = wptr(L.w_ns);
+    p.frgb_w = wptr(L.w_frgb); p.frgb_b = wptr(L.b_frgb);
+    p.trgb_w = wptr(L.w_trgb); p.trgb_b = wptr(L.b_trgb);
+    p.img_prev = (const float*)bptr(L.imgprev_buf); p.img_out = (float*)bptr(L.imgout_buf);
+    return p;
+  };
+  // (nd: the sub-batch size the production forward launches with -- the per-launch timing run covers the whole batch in one launch but
+  // must time the kernel forms the throughput run uses)
+  const int nd = n_geo > 0 ? n_geo : n;
+  // a down=2 layer is two plan entries (depthwise + FIR-down, pointwise GEMM); where the fused kernel applies, the first entry launches
+  // nothing and the second launches sepconv_pipedown_kernel on the first one's input: decided at the first entry, for both
+  const DownEntry* down = nullptr;
+  SepArgs down_args{};
   for (size_t li = 0; li < P.launches.size(); ++li) {
     const Launch& L = P.launches[li];
     if (timed) rt_check(rt::event_record(events[2 * li], stream), "hipEventRecord");
-    // a down=2 layer is two plan entries (depthwise + FIR-down, pointwise GEMM); where the fused kernel applies, the first entry launches
-    // nothing and the second launches sepconv_pipedown_kernel on the first one's input
-    // (nd: the sub-batch size the production forward launches with -- the per-launch timing run covers the whole batch in one launch but
-    // must time the kernel forms the throughput run uses)
-    const int nd = n_geo > 0 ? n_geo : n;
-    const bool dw_fused = L.is_dwfir && li + 1 < P.launches.size() &&
-                          pick_pipedown(L.cin, P.launches[li + 1].cout, L.hin, L.win, nd, stv, gemm) != nullptr;
-    const bool pw_fused = !L.is_dwfir && !L.is_rgb && L.g.mode == MODE_PW && li >= 1 && P.launches[li - 1].is_dwfir &&
-                          pick_pipedown(L.cin, L.cout, P.launches[li - 1].hin, P.launches[li - 1].win, nd, stv, gemm) != nullptr;
-    if (dw_fused) {
-      L.kernel_last = pick_pipedown(L.cin, P.launches[li + 1].cout, L.hin, L.win, nd, stv, gemm)->name;      // (its bytes belong to that launch)
-    } else if (pw_fused) {
-      const Launch& D = P.launches[li - 1];
-      const DownEntry* de = pick_pipedown(L.cin, L.cout, D.hin, D.win, nd, stv, gemm);
-      SepArgs a{};
-      a.x = bptr(D.in_buf); a.y = bptr(L.out_buf);
-      a.wdw = wptr(D.w_dw); a.bdw = wptr(D.b_dw); a.wpw = wptr(L.w_pw);
-      a.wsplit = wsplit + L.wsplit_off;
-      a.B = n; a.H = D.hin; a.W = D.win; a.CI = L.cin; a.CO = L.cout; a.HO = L.hout; a.WO = L.wout;
-      launch_pipedown(*de, a, stream);
-      L.kernel_last = de->name;
+    if (L.is_dwfir && li + 1 < P.launches.size()) {
+      const Launch& G = P.launches[li + 1];      // the pointwise GEMM of the pair
+      SepParams p = params_of(G);
+      p.wdw = wptr(L.w_dw); p.bdw = wptr(L.b_dw);
+      down_args = sep_args(p, bptr(L.in_buf), bptr(G.out_buf), nullptr, n, L.hin, L.win, G.cin, G.cout, G.hout, G.wout);
+      down = pick_fused_down(down_args, nd, stv, gemm);
+    }
+    if (L.is_dwfir && down) {
+      L.kernel_last = down->name;      // (its bytes belong to that launch)
+    } else if (down) {
+      L.kernel_last = launch_pipedown(*down, down_args, stream);
+      down = nullptr;
     } else if (L.is_dwfir) {
       DwFirArgs a{};
       a.x = bptr(L.in_buf); a.y = (float*)bptr(L.out_buf); a.wdw = wptr(L.w_dw); a.bdw = wptr(L.b_dw);
@@ -1198,17 +1215,8 @@ inline void migan_handle::run_range(const migan::Plan& P, const float* x, float*
     } else if (L.narrow) {
       MIGAN_CHECK(u8 == nullptr || (L.in_buf != BUF_X && L.imgout_buf != BUF_Y), MIGAN_EUNSUPPORTED,
                   "the uint8-in / uint8-out forward is not available at resolutions above 512");
-      SepArgs a{};
-      a.x = bptr(L.in_buf); a.y = bptr(L.out_buf); a.skip = bptr(L.skip_buf);
-      a.wdw = wptr(L.w_dw); a.bdw = wptr(L.b_dw); a.wpw = wptr(L.w_pw);
-      a.noise = L.noise_plane_off >= 0 ? reinterpret_cast<const float*>(shared + L.noise_plane_off) : wptr(L.w_noise);
-      a.noise_strength = wptr(L.w_ns);
-      a.frgb_w = wptr(L.w_frgb); a.frgb_b = wptr(L.b_frgb);
-      a.trgb_w = wptr(L.w_trgb); a.trgb_b = wptr(L.b_trgb);
-      a.img_prev = (const float*)bptr(L.imgprev_buf); a.img_out = (float*)bptr(L.imgout_buf);
-      a.B = n; a.H = L.hin; a.W = L.win; a.CI = L.cin; a.CO = L.cout; a.HO = L.hout; a.WO = L.wout;
-      launch_narrow(L.mode, L.fromrgb, a, stream);
-      L.kernel_last = narrow_name(L.mode, L.fromrgb);
+      const SepArgs a = sep_args(params_of(L), bptr(L.in_buf), bptr(L.out_buf), bptr(L.skip_buf), n, L.hin, L.win, L.cin, L.cout, L.hout, L.wout);
+      L.kernel_last = launch_narrow(L.mode, L.fromrgb, a, stream);
     } else if (L.is_rgb) {
       RgbArgs a{};
       a.x = bptr(L.in_buf); a.w = wptr(L.w_trgb); a.b = wptr(L.b_trgb);
@@ -1217,20 +1225,11 @@ inline void migan_handle::run_range(const migan::Plan& P, const float* x, float*
       if (u8 && L.imgout_buf == BUF_Y) { a.u8_img = (const unsigned char*)u8->img; a.u8_mask = (const unsigned char*)u8->mask; a.u8_out = (unsigned char*)u8->out; }
       launch_torgb(a, stream, stv);
     } else {
-      SepArgs a{};
-      a.x = bptr(L.in_buf); a.y = bptr(L.out_buf); a.skip = bptr(L.skip_buf);
-      a.wdw = wptr(L.w_dw); a.bdw = wptr(L.b_dw); a.wpw = wptr(L.w_pw);
-      a.wsplit = L.g.gemmv ? wsplit + L.wsplit_off : nullptr;
-      a.noise = L.noise_plane_off >= 0 ? reinterpret_cast<const float*>(shared + L.noise_plane_off) : wptr(L.w_noise);
-      a.noise_strength = wptr(L.w_ns);
-      a.frgb_w = wptr(L.w_frgb); a.frgb_b = wptr(L.b_frgb);
-      a.trgb_w = wptr(L.w_trgb); a.trgb_b = wptr(L.b_trgb);
-      a.img_prev = (const float*)bptr(L.imgprev_buf); a.img_out = (float*)bptr(L.imgout_buf);
+      SepArgs a = sep_args(params_of(L), bptr(L.in_buf), bptr(L.out_buf), bptr(L.skip_buf), n, L.hin, L.win, L.cin, L.cout, L.hout, L.wout);
       if (u8 && L.in_buf == BUF_X) { a.u8_img = (const unsigned char*)u8->img; a.u8_mask = (const unsigned char*)u8->mask; }
       if (u8 && L.imgout_buf == BUF_Y && a.trgb_w) {
         a.u8_img = (const unsigned char*)u8->img; a.u8_mask = (const unsigned char*)u8->mask; a.u8_out = (unsigned char*)u8->out;
       }
-      a.B = n; a.H = L.hin; a.W = L.win; a.CI = L.cin; a.CO = L.cout; a.HO = L.hout; a.WO = L.wout;
       // launches that would leave most CUs idle run the 32-row tiles: a quarter of the work per workgroup, four times the workgroups
       const Geo* Gp = &L.g;
       for (const Geo& gs : L.g_small) {
@@ -1241,8 +1240,7 @@ inline void migan_handle::run_range(const migan::Plan& P, const float* x, float*
       }
       const Geo& G = *Gp;
       fill_geo(a, G);
-      launch_sepconv(G, a, stream, nd);
-      L.kernel_last = launched_kernel_name(G, L.cin, L.cout, nd, a.trgb_w != nullptr, a.skip != nullptr);
+      L.kernel_last = launch_sepconv(G, a, stream, nd);
     }
     if (timed) rt_check(rt::event_record(events[2 * li + 1], stream), "hipEventRecord");
     if (!timed && (int)li == mid_after) rt_check(rt::event_record(ev_mid[part], stream), "hipEventRecord");
@@ -1677,6 +1675,12 @@ int migan_sepconv_forward(const migan_sepconv_desc* d, void* stream) {
   const int h_out = d->down == 2 ? h_in / 2 : (d->up == 2 ? h_in * 2 : h_in);
   const int w_out = d->down == 2 ? w_in / 2 : (d->up == 2 ? w_in * 2 : w_in);
   MIGAN_CHECK(d->noise_const == nullptr || d->noise_strength != nullptr, MIGAN_EINVAL, "noise_const without noise_strength");
+  SepParams p;
+  p.wdw = (const float*)d->conv1_weight; p.bdw = (const float*)d->conv1_bias; p.wpw = (const float*)d->conv2_weight;
+  p.noise = (const float*)d->noise_const; p.noise_strength = (const float*)d->noise_strength;
+  p.frgb_w = (const float*)d->fromrgb_weight; p.frgb_b = (const float*)d->fromrgb_bias;
+  p.trgb_w = (const float*)d->torgb_weight; p.trgb_b = (const float*)d->torgb_bias;
+  p.img_prev = (const float*)d->img_prev; p.img_out = (float*)d->img_out;
   if (is_narrow(d->cin, d->cout) && d->cin <= 64 && d->cout <= 64 && d->cin % 4 == 0 && d->cout % 4 == 0) {
     // fewer than 64 channels on either side (the layers of resolutions above 512): the plain kernel, the whole layer in one launch
     MIGAN_CHECK(stv == 0, MIGAN_EUNSUPPORTED, "layers with fewer than 64 channels run with fp32 activation storage only");
@@ -1686,14 +1690,7 @@ int migan_sepconv_forward(const migan_sepconv_desc* d, void* stream) {
     MIGAN_CHECK(d->fromrgb_weight == nullptr || d->fromrgb_bias != nullptr, MIGAN_EINVAL, "fromrgb_weight without fromrgb_bias");
     prepare_kernels();
     const int nmode = d->down == 2 ? MODE_DOWN : (d->up == 2 ? MODE_UP : MODE_NORMAL);
-    SepArgs a{};
-    a.x = d->x; a.y = d->y; a.skip = d->skip;
-    a.wdw = (const float*)d->conv1_weight; a.bdw = (const float*)d->conv1_bias; a.wpw = (const float*)d->conv2_weight;
-    a.noise = (const float*)d->noise_const; a.noise_strength = (const float*)d->noise_strength;
-    a.frgb_w = (const float*)d->fromrgb_weight; a.frgb_b = (const float*)d->fromrgb_bias;
-    a.trgb_w = (const float*)d->torgb_weight; a.trgb_b = (const float*)d->torgb_bias;
-    a.img_prev = (const float*)d->img_prev; a.img_out = (float*)d->img_out;
-    a.B = d->batch; a.H = h_in; a.W = w_in; a.CI = d->cin; a.CO = d->cout; a.HO = h_out; a.WO = w_out;
+    const SepArgs a = sep_args(p, d->x, d->y, d->skip, d->batch, h_in, w_in, d->cin, d->cout, h_out, w_out);
     launch_narrow(nmode, d->fromrgb_weight != nullptr, a, (rt::stream_t)stream);
     return MIGAN_OK;
   }
@@ -1709,22 +1706,17 @@ int migan_sepconv_forward(const migan_sepconv_desc* d, void* stream) {
   const bool have_planes = d->wsplit != nullptr && d->wsplit_bytes >= wsplit_need;
   MIGAN_CHECK(stv == 0 || have_planes, MIGAN_EINVAL, "16-bit activation storage needs the wsplit buffer (fp16 GEMM variants)");
   const int gemmv = have_planes ? want : 0;
-  const DownEntry* fused_down = nullptr;
-  if (d->down == 2 && have_planes && d->fromrgb_weight == nullptr && d->torgb_weight == nullptr && d->noise_const == nullptr && d->skip == nullptr)
-    fused_down = pick_pipedown(d->cin, d->cout, h_in, w_in, d->batch, stv, gemmv);
-  if (fused_down) {
+  if (gemmv) p.wsplit = (const unsigned short*)d->wsplit + kSplitHeader;
+  if (!p.trgb_w) { p.img_prev = nullptr; p.img_out = nullptr; }
+  const SepArgs whole = sep_args(p, d->x, d->y, d->skip, d->batch, h_in, w_in, d->cin, d->cout, h_out, w_out);
+  if (const DownEntry* fused_down = d->down == 2 ? pick_fused_down(whole, d->batch, stv, gemmv) : nullptr) {
     // one launch: depthwise + FIR-down feed the 1x1 through LDS (no scratch tensor)
     SplitArgs sa{};
     sa.dst = (unsigned short*)d->wsplit;
     sa.f16 = 1;
     sa.src[0] = (const float*)d->conv2_weight; sa.dst_off[0] = kSplitHeader; sa.count[0] = (unsigned)(d->cin * d->cout); sa.ci[0] = (unsigned)d->cin; sa.n = 1;
     launch_split(sa, (rt::stream_t)stream);
-    SepArgs a{};
-    a.x = d->x; a.y = d->y;
-    a.wdw = (const float*)d->conv1_weight; a.bdw = (const float*)d->conv1_bias; a.wpw = (const float*)d->conv2_weight;
-    a.wsplit = (const unsigned short*)d->wsplit + kSplitHeader;
-    a.B = d->batch; a.H = h_in; a.W = w_in; a.CI = d->cin; a.CO = d->cout; a.HO = h_out; a.WO = w_out;
-    launch_pipedown(*fused_down, a, (rt::stream_t)stream);
+    launch_pipedown(*fused_down, whole, (rt::stream_t)stream);
     return MIGAN_OK;
   }
   if (d->down == 2) {
@@ -1753,17 +1745,8 @@ int migan_sepconv_forward(const migan_sepconv_desc* d, void* stream) {
   // one workgroup owns all output channels of its pixels (cout <= 128, or 256 on whole 8x16 tiles): ToRGB fuses into the epilogue;
   // otherwise torgb_kernel runs on y afterwards, as in the generator plan
   const bool fuse_rgb = d->torgb_weight != nullptr && g.nchunks == 1;
-  SepArgs a{};
-  a.x = gemm_in; a.y = d->y; a.skip = d->skip;
-  a.wdw = (const float*)d->conv1_weight; a.bdw = (const float*)d->conv1_bias; a.wpw = (const float*)d->conv2_weight;
-  a.wsplit = gemmv ? (const unsigned short*)d->wsplit + kSplitHeader : nullptr;
-  a.noise = (const float*)d->noise_const; a.noise_strength = (const float*)d->noise_strength;
-  a.frgb_w = (const float*)d->fromrgb_weight; a.frgb_b = (const float*)d->fromrgb_bias;
-  if (fuse_rgb) {
-    a.trgb_w = (const float*)d->torgb_weight; a.trgb_b = (const float*)d->torgb_bias;
-    a.img_prev = (const float*)d->img_prev; a.img_out = (float*)d->img_out;
-  }
-  a.B = d->batch; a.H = gemm_h; a.W = gemm_w; a.CI = d->cin; a.CO = d->cout; a.HO = h_out; a.WO = w_out;
+  SepArgs a = sep_args(p, gemm_in, d->y, d->skip, d->batch, gemm_h, gemm_w, d->cin, d->cout, h_out, w_out);
+  if (!fuse_rgb) { a.trgb_w = a.trgb_b = a.img_prev = nullptr; a.img_out = nullptr; }
   fill_geo(a, g);
   launch_sepconv(g, a, (rt::stream_t)stream);
   if (d->torgb_weight != nullptr && !fuse_rgb) {
