@@ -240,11 +240,14 @@ int migan_pack_input(const void* img_hwc_u8, const void* mask_u8, void* x_nchw, 
 int migan_compose_output(const void* y_nchw, const void* img_hwc_u8, const void* mask_u8, void* out_hwc_u8,
                          int batch, int resolution, void* stream);
 
-/* Process-wide tuning knobs, the run-time form of the MIGAN_* environment variables (experiments and tests):
- * "kc16" (bit mask: 16-channel K chunks for the 64-channel 512x512 layers), "kc16_minw", "w3" (the same mask: those layers on 32-channel chunks at 3 workgroups per CU), "wide", "nt256", "persist_min",
- * "persist_grid", "streams", "stagger", "stagger_pct", "single_b", "debug_split", "pipe" (bit mask: software-pipelined persistent kernels for
- * 1 plain, 2 fused-FromRGB, 4 FIR-up layers), "pipe_grid", "pipe_min_tiles".  Applies to handles created or re-planned afterwards. */
+/* Process-wide tuning knobs, the run-time form of the MIGAN_* environment variables (experiments and tests).  The keys are what
+ * migan_tuning_key enumerates (index 0, 1, ... until it returns NULL).  A value is normalised (clamped or rounded) before it is stored;
+ * migan_get_tuning reads the stored value, and setting that value again changes nothing.  "kc16", "w3", "pipe" and "pipe_na8" are bit
+ * masks over layer kinds: 1 plain (+ fused ToRGB), 2 fused-FromRGB, 4 FIR-up layers; "pipe" also has 8, the down=2 layers as one fused
+ * launch.  An unknown key is MIGAN_EINVAL.  Applies to handles created or re-planned afterwards. */
 int migan_set_tuning(const char* key, int value);
+int migan_get_tuning(const char* key, int* value);
+const char* migan_tuning_key(int index);
 
 const char* migan_last_error(void);
 /* Symbol (as rocprofv3 prints it) of the fused-SeparableConv2d kernel the calling thread launched last, "" before the first launch:

@@ -7,6 +7,7 @@
 #pragma once
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -73,7 +74,8 @@ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 // bit of a layer kind in the kc16 / w3 / pipe / pipe_na8 masks: 1 plain (+ fused ToRGB), 2 fused FromRGB, 4 FIR-up
 inline int layer_bit(bool fromrgb, int mode) { return fromrgb ? 2 : (mode == MODE_UP ? 4 : 1); }
 
-// Tuning knobs read once from the environment (experiments only; defaults are the shipped choice).
+// Tuning knobs (experiments only; defaults are the shipped choice).  kKnobs below is the one list of them: the key each is set and
+// read by, the environment variable that sets it at start-up where a comment here names one, and how a value is normalised.
 struct Tuning {
   int force_single_b = 0;      // MIGAN_SINGLE_B=1: never double-buffer the 1x1 weight tile
   int gemm = 2;                // MIGAN_GEMM=f32|bf16x3|f16x2: 0 exact fp32 MFMA; 1 error-compensated bf16 MFMA (6 products of
@@ -96,7 +98,7 @@ struct Tuning {
                                // (135 VGPRs instead of 184; synthesis.b512.conv2 1.34 -> 1.07 ms).  The FIR-up tile (4 chunks) needs 60 bytes
                                // of scratch at that budget and loses 10 %: profiles/r02_w3_and_persistence_sweep.txt
   int small = 1;               // launches of at most small_max_wgs small tiles use them (default GEMM variant of the storage format)
-  int small_max_wgs = 512;     // (MIGAN_GEOMETRIES_SMALL; single-image latency and the <= 16x16 layers)
+  int small_max_wgs = 512;     // (the MIGAN_GEOMETRIES_SMALL rows of migan_table.hpp; single-image latency and the <= 16x16 layers)
   int small_kc = 64;           // K chunk of those tiles: 32 or 64 channels (batch 1: 0.85 ms with 32, 0.81 ms with 64)
   int small_up32 = 1;          // FIR-up layers: try the 32-row tile before the 64-row one
   int small_dwfir = 1;         // dwfir_kernel: small launches walk fewer channel chunks per workgroup (more workgroups)
@@ -104,7 +106,7 @@ struct Tuning {
   int streams = 2;             // MIGAN_STREAMS=1|2: default of migan_set_streams
   int stagger = -1;            // MIGAN_STAGGER: launch index of the first half after which the second half starts (-1: plan default)
   int debug_split = 0;         // diagnostics: keep the two-sub-batch execution in keep-intermediates mode
-  int stagger_pct = 15;        // MIGAN_STAGGER_PCT: the next sub-batch starts after this share of a forward's launches (round 5 sweep, two runs each:
+  int stagger_pct = 15;        // 0..100: the next sub-batch starts after this share of a forward's launches (round 5 sweep, two runs each:
                                // 5 .. 18 % 3680 - 3693 images/s, 22 % (rounds 2 - 4) 3655 - 3663, 30 % 3655, 40 % 3638)
   int pipe = 15;               // MIGAN_PIPE bit mask: software-pipelined persistent kernels (sepconv_pipe_kernel; fp32 storage, f16x2 GEMM) for
                                // 1 plain (+ fused ToRGB) layers, 2 the fused-FromRGB layer, 4 FIR-up layers, 8 down=2 layers as one fused launch
@@ -123,23 +125,67 @@ struct Tuning {
   int pipe_min_batch = 1;      // smallest batch that takes them (1: a single-image forward runs them on its 512x512 / 256x256 layers too -- 2048 / 512 tiles;
                                // latency_b1 0.70 -> 0.66 ms; its other layers run the latency tiles, so it is not bit-identical to a batched forward either way)
 };
+// how a requested value becomes the stored one; each is a clamp or a rounding, so a stored value normalises to itself
+namespace knob {
+inline int any(int v) { return v; }
+inline int flag(int v) { return v != 0; }
+template <int LO, int HI = INT_MAX>
+inline int clamp(int v) { return std::min(HI, std::max(LO, v)); }
+inline int mult8(int v) { return std::max(8, v / 8 * 8); }   // multiple of 8: one share per XCD
+inline int na(int v) { return v == 8 ? 8 : 4; }
+}  // namespace knob
+
+struct Knob {
+  const char* key;        // what migan_set_tuning / migan_get_tuning accept
+  const char* env;        // variable read once at start-up, or nullptr
+  int Tuning::*field;
+  int (*norm)(int);
+};
+// (`gemm` is not a knob: MIGAN_GEMM is a string and environment-only; migan_set_gemm chooses per handle)
+inline const Knob kKnobs[] = {
+    {"kc16", "MIGAN_KC16", &Tuning::kc16, knob::any},
+    {"kc16_minw", "MIGAN_KC16_MINW", &Tuning::kc16_minw, knob::clamp<2, 4>},
+    {"w3", "MIGAN_W3", &Tuning::w3, knob::any},
+    {"wide", "MIGAN_WIDE", &Tuning::wide, knob::any},
+    {"wide_up", nullptr, &Tuning::wide_up, knob::any},
+    {"small", nullptr, &Tuning::small, knob::any},
+    {"small_max_wgs", nullptr, &Tuning::small_max_wgs, knob::any},
+    {"small_kc", nullptr, &Tuning::small_kc, knob::any},
+    {"small_up32", nullptr, &Tuning::small_up32, knob::any},
+    {"small_dwfir", nullptr, &Tuning::small_dwfir, knob::any},
+    {"small_ksplit", nullptr, &Tuning::small_ksplit, knob::any},
+    {"nt256", "MIGAN_NT256", &Tuning::nt256, knob::flag},
+    {"persist_min", "MIGAN_PERSIST_MIN", &Tuning::persist_min, knob::clamp<1>},
+    {"persist_grid", "MIGAN_PERSIST_GRID", &Tuning::persist_grid, knob::mult8},
+    {"streams", "MIGAN_STREAMS", &Tuning::streams, knob::clamp<1, 4>},
+    {"stagger", "MIGAN_STAGGER", &Tuning::stagger, knob::any},
+    {"single_b", "MIGAN_SINGLE_B", &Tuning::force_single_b, knob::flag},
+    {"debug_split", nullptr, &Tuning::debug_split, knob::flag},
+    {"stagger_pct", nullptr, &Tuning::stagger_pct, knob::clamp<0, 100>},
+    {"pipe", "MIGAN_PIPE", &Tuning::pipe, knob::any},
+    {"pipe_grid", "MIGAN_PIPE_GRID", &Tuning::pipe_grid, knob::mult8},
+    {"pipe_na", nullptr, &Tuning::pipe_na, knob::na},
+    {"pipe_na8", nullptr, &Tuning::pipe_na8, knob::any},
+    {"pipe_dna", nullptr, &Tuning::pipe_dna, knob::any},
+    {"pipe_min_tiles", nullptr, &Tuning::pipe_min_tiles, knob::clamp<1>},
+    {"pipe_min_batch", nullptr, &Tuning::pipe_min_batch, knob::clamp<1>},
+    {"w2", "MIGAN_W2", &Tuning::w2, knob::clamp<0, 2>},
+    {"w2_min_tiles", nullptr, &Tuning::w2_min_tiles, knob::clamp<1>},
+    {"w2_pw", nullptr, &Tuning::w2_pw, knob::flag},
+};
+inline const Knob& knob_of(const char* key) {
+  MIGAN_CHECK(key != nullptr, MIGAN_EINVAL, "null key");
+  for (const Knob& k : kKnobs)
+    if (std::strcmp(k.key, key) == 0) return k;
+  throw Error(MIGAN_EINVAL, std::string("unknown tuning key: ") + key);
+}
+
 inline Tuning& tuning() {
   static Tuning t = [] {
     Tuning v;
-    if (const char* e = std::getenv("MIGAN_SINGLE_B")) v.force_single_b = std::atoi(e) != 0;
     if (const char* e = std::getenv("MIGAN_GEMM")) v.gemm = std::string(e) == "f32" ? 0 : (std::string(e) == "bf16x3" ? 1 : 2);
-    if (const char* e = std::getenv("MIGAN_WIDE")) v.wide = std::atoi(e);
-    if (const char* e = std::getenv("MIGAN_NT256")) v.nt256 = std::atoi(e) != 0;
-    if (const char* e = std::getenv("MIGAN_PERSIST_MIN")) v.persist_min = std::max(1, std::atoi(e));
-    if (const char* e = std::getenv("MIGAN_PERSIST_GRID")) v.persist_grid = std::max(8, std::atoi(e) / 8 * 8);   // multiple of 8: one share per XCD
-    if (const char* e = std::getenv("MIGAN_KC16")) v.kc16 = std::atoi(e);
-    if (const char* e = std::getenv("MIGAN_KC16_MINW")) v.kc16_minw = std::min(4, std::max(2, std::atoi(e)));
-    if (const char* e = std::getenv("MIGAN_W3")) v.w3 = std::atoi(e);
-    if (const char* e = std::getenv("MIGAN_STREAMS")) v.streams = std::min(4, std::max(1, std::atoi(e)));
-    if (const char* e = std::getenv("MIGAN_STAGGER")) v.stagger = std::atoi(e);
-    if (const char* e = std::getenv("MIGAN_PIPE")) v.pipe = std::atoi(e);
-    if (const char* e = std::getenv("MIGAN_W2")) v.w2 = std::min(2, std::max(0, std::atoi(e)));
-    if (const char* e = std::getenv("MIGAN_PIPE_GRID")) v.pipe_grid = std::max(8, std::atoi(e) / 8 * 8);
+    for (const Knob& k : kKnobs)
+      if (const char* e = k.env ? std::getenv(k.env) : nullptr) v.*k.field = k.norm(std::atoi(e));
     return v;
   }();
   return t;
@@ -1908,41 +1954,19 @@ int migan_prof_layer(int index, unsigned long long out[16]) {
 // Affects handles created / re-planned afterwards.
 int migan_set_tuning(const char* key, int value) {
   MIGAN_API_BEGIN
-  using namespace migan;
-  MIGAN_CHECK(key != nullptr, MIGAN_EINVAL, "null key");
-  Tuning& t = tuning();
-  const std::string k = key;
-  if (k == "kc16") t.kc16 = value;
-  else if (k == "kc16_minw") t.kc16_minw = std::min(4, std::max(2, value));
-  else if (k == "w3") t.w3 = value;
-  else if (k == "wide") t.wide = value;
-  else if (k == "wide_up") t.wide_up = value;
-  else if (k == "small") t.small = value;
-  else if (k == "small_max_wgs") t.small_max_wgs = value;
-  else if (k == "small_kc") t.small_kc = value;
-  else if (k == "small_up32") t.small_up32 = value;
-  else if (k == "small_dwfir") t.small_dwfir = value;
-  else if (k == "small_ksplit") t.small_ksplit = value;
-  else if (k == "nt256") t.nt256 = value != 0;
-  else if (k == "persist_min") t.persist_min = std::max(1, value);
-  else if (k == "persist_grid") t.persist_grid = std::max(8, value / 8 * 8);
-  else if (k == "streams") t.streams = std::min(4, std::max(1, value));
-  else if (k == "stagger") t.stagger = value;
-  else if (k == "single_b") t.force_single_b = value != 0;
-  else if (k == "debug_split") t.debug_split = value != 0;
-  else if (k == "stagger_pct") t.stagger_pct = std::min(100, std::max(0, value));
-  else if (k == "pipe") t.pipe = value;
-  else if (k == "pipe_grid") t.pipe_grid = std::max(8, value / 8 * 8);
-  else if (k == "pipe_na") t.pipe_na = value == 8 ? 8 : 4;
-  else if (k == "pipe_na8") t.pipe_na8 = value;
-  else if (k == "pipe_dna") t.pipe_dna = value;
-  else if (k == "pipe_min_tiles") t.pipe_min_tiles = std::max(1, value);
-  else if (k == "pipe_min_batch") t.pipe_min_batch = std::max(1, value);
-  else if (k == "w2") t.w2 = std::min(2, std::max(0, value));
-  else if (k == "w2_min_tiles") t.w2_min_tiles = std::max(1, value);
-  else if (k == "w2_pw") t.w2_pw = value != 0;
-  else throw Error(MIGAN_EINVAL, "unknown tuning key: " + k);
+  const migan::Knob& k = migan::knob_of(key);
+  migan::tuning().*k.field = k.norm(value);
   MIGAN_API_END
+}
+// the stored (normalised) value
+int migan_get_tuning(const char* key, int* value) {
+  MIGAN_API_BEGIN
+  MIGAN_CHECK(value != nullptr, MIGAN_EINVAL, "null value");
+  *value = migan::tuning().*migan::knob_of(key).field;
+  MIGAN_API_END
+}
+const char* migan_tuning_key(int index) {
+  return index >= 0 && index < (int)(sizeof(migan::kKnobs) / sizeof(migan::kKnobs[0])) ? migan::kKnobs[index].key : nullptr;
 }
 
 const char* migan_last_error(void) { return migan::last_error_ref().c_str(); }

@@ -68,7 +68,7 @@ EXPORTS = (
     "migan_forward_timed", "migan_set_debug", "migan_debug_tensor", "migan_sepconv_forward",
     "migan_pack_input", "migan_compose_output",
     "migan_pipeline_mask_resize", "migan_pipeline_scratch_bytes", "migan_pipeline_bbox", "migan_pipeline_pre", "migan_pipeline_post",
-    "migan_forward_split", "migan_forward_parts", "migan_set_tuning", "migan_last_error", "migan_last_kernel", "migan_nan_policy", "migan_backend", "migan_gemm_variant", "migan_version",
+    "migan_forward_split", "migan_forward_parts", "migan_set_tuning", "migan_get_tuning", "migan_tuning_key", "migan_last_error", "migan_last_kernel", "migan_nan_policy", "migan_backend", "migan_gemm_variant", "migan_version",
     # include/comodgan_hip.h
     "comodgan_create", "comodgan_destroy", "comodgan_num_weights", "comodgan_weight_info", "comodgan_set_weight",
     "comodgan_commit", "comodgan_workspace_bytes", "comodgan_assume_static_weights", "comodgan_noise_floats", "comodgan_forward",
@@ -155,6 +155,8 @@ class MiganLib:
         L.migan_debug_tensor.argtypes = [vp, ci, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]
         L.migan_sepconv_forward.argtypes = [C.POINTER(SepConvDesc), vp]
         L.migan_set_tuning.argtypes = [C.c_char_p, ci]
+        L.migan_get_tuning.argtypes = [C.c_char_p, C.POINTER(ci)]
+        L.migan_tuning_key.argtypes = [ci]
         L.migan_pack_input.argtypes = [vp, vp, vp, ci, ci, vp]
         L.migan_compose_output.argtypes = [vp, vp, vp, vp, ci, ci, vp]
         fp = C.POINTER(C.c_float)
@@ -180,12 +182,13 @@ class MiganLib:
         L.migan_nan_policy.restype = C.c_char_p
         L.migan_backend.restype = C.c_char_p
         L.migan_gemm_variant.restype = C.c_char_p
+        L.migan_tuning_key.restype = C.c_char_p
         L.migan_backend.restype = C.c_char_p
         if not allow_test_backend and L.migan_backend().decode() != PRODUCT_BACKEND:
             raise MiganError(f"{self.path} reports backend {L.migan_backend().decode()!r}, not {PRODUCT_BACKEND!r}: only the gfx950 HIP "
                              f"library is a product backend (the CPU emulator build is test infrastructure)")
         for name in EXPORTS:
-            if name not in ("migan_last_error", "migan_last_kernel", "migan_nan_policy", "migan_backend", "migan_gemm_variant"):
+            if name not in ("migan_last_error", "migan_last_kernel", "migan_nan_policy", "migan_backend", "migan_gemm_variant", "migan_tuning_key"):
                 getattr(L, name).restype = ci
 
     # -- error mapping: EINVAL -> ValueError-like, like the reference's constructor / load_state_dict
@@ -217,6 +220,19 @@ class MiganLib:
 
     def set_tuning(self, key: str, value: int) -> None:
         self.check(self.lib.migan_set_tuning(key.encode(), int(value)))
+
+    def get_tuning(self, key: str) -> int:
+        """the stored value of a knob (what set_tuning normalised the request to)"""
+        v = C.c_int(0)
+        self.check(self.lib.migan_get_tuning(key.encode(), C.byref(v)))
+        return v.value
+
+    def tuning_keys(self) -> list:
+        """every key set_tuning / get_tuning accept"""
+        keys = []
+        while (k := self.lib.migan_tuning_key(len(keys))) is not None:
+            keys.append(k.decode())
+        return keys
 
     def pack_input(self, img_ptr: int, mask_ptr: int, x_ptr: int, batch: int, resolution: int, stream: int = 0) -> None:
         self.check(self.lib.migan_pack_input(C.c_void_p(img_ptr), C.c_void_p(mask_ptr), C.c_void_p(x_ptr), int(batch),

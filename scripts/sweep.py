@@ -17,8 +17,6 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import torch
 
-DEFAULTS = dict(kc16=0, kc16_minw=3, w3=3, wide=3, nt256=1, persist_min=8192, persist_grid=512, single_b=0, stagger=-1, stagger_pct=22)
-
 VARIANTS = [
     # label, tuning overrides, streams, dtype
     ("base_s1", {}, 1, "f32"),
@@ -72,6 +70,7 @@ def main():
     args = ap.parse_args()
     pkg = importlib.import_module("mi-gan_amd")
     lib = pkg.load_library()
+    start = {k: lib.get_tuning(k) for k in lib.tuning_keys()}      # every variant starts from what this process started with
     from oracle import migan_torch_cpu as torc
     res = int(args.model.split("-")[1])
     dev = torch.device("cuda", 0)
@@ -84,7 +83,7 @@ def main():
     for label, tune, streams, dtype in VARIANTS:
         if only and label not in only:
             continue
-        for k, v in DEFAULTS.items():
+        for k, v in start.items():
             lib.set_tuning(k, v)
         for k, v in tune.items():
             lib.set_tuning(k, v)

@@ -7,12 +7,11 @@ import itertools
 import re
 from dataclasses import dataclass, field
 
+from tests.knobs import knobs
 from tests.sepconv_case import run_sepconv_case
 
 STORAGES = ("f32", "bf16", "f16")
 STV = {"f32": 0, "bf16": 1, "f16": 2}
-# the tuning knobs a row may set, and their defaults (restored after every case)
-DEFAULT_KNOBS = dict(pipe_min_tiles=256, pipe_grid=256, w2_min_tiles=256, persist_min=8192, persist_grid=512)
 # the emulator cases have a few dozen tiles: let the persistent kernels take them, a few tiles per workgroup (as test_emu_pipe / _wide2 do)
 PERSISTENT = dict(pipe_min_tiles=1, pipe_grid=8, w2_min_tiles=1)
 
@@ -229,34 +228,23 @@ COMPANIONS = (
 COMPANION_ROWS = ("narrow_plain", "tile_plain", "pipe64", "wide")
 
 
-def set_knobs(lib, knobs):
-    for k, v in {**DEFAULT_KNOBS, **knobs}.items():
-        lib.set_tuning(k, v)
-
-
 def run_matrix_case(lib, pkg, mem, row_name, f, storage, seed=29):
     """run one case of the table; returns the kernel names it launched (for the coverage checks), [] for a refusal"""
     row = ROW[row_name]
     want = expected(row, f, storage)
-    set_knobs(lib, row.knobs)
-    try:
+    with knobs(lib, **row.knobs):
         if want[0] == "refused":
             run_sepconv_case(lib, pkg, mem, seed=seed, storage=storage, oracle_f64=True, refused=(want[1], want[2]), **row.kw, **f)
             return []
         run_sepconv_case(lib, pkg, mem, seed=seed, storage=storage, oracle_f64=True, **row.kw, **f)
         assert lib.last_kernel() == want[1], (lib.last_kernel(), want[1])
         return [want[1]] + want[2]
-    finally:
-        set_knobs(lib, {})
 
 
 def run_companion_case(lib, pkg, mem, row_name, flags, drop, fragment):
     row = ROW[row_name]
-    set_knobs(lib, row.knobs)
-    try:
+    with knobs(lib, **row.knobs):
         run_sepconv_case(lib, pkg, mem, seed=31, oracle_f64=True, drop=drop, refused=(ValueError, fragment), **row.kw, **flags)
-    finally:
-        set_knobs(lib, {})
 
 
 def table_kernels(lib, pkg, mem):

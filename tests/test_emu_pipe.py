@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from tests.emu_util import emu_lib
+from tests.knobs import knobs
 from tests.sepconv_case import HostMem, run_sepconv_case
 
 
@@ -25,17 +26,8 @@ def pkg():
 @pytest.fixture(autouse=True, params=[4, 8])
 def small_grids(request, lib):
     # the emulator cases have a few dozen tiles: let them take the pipelined kernels, a few tiles per workgroup
-    lib.set_tuning("pipe_min_tiles", 1)
-    lib.set_tuning("pipe_grid", 8)
-    lib.set_tuning("pipe_na", request.param)
-    lib.set_tuning("pipe_na8", 0)      # (this wave count for every form)
-    yield request.param
-    lib.set_tuning("pipe_dna", 12)
-    lib.set_tuning("pipe_min_tiles", 256)
-    lib.set_tuning("pipe_grid", 256)
-    lib.set_tuning("pipe", 15)
-    lib.set_tuning("pipe_na", 4)
-    lib.set_tuning("pipe_na8", 9)
+    with knobs(lib, pipe_min_tiles=1, pipe_grid=8, pipe_na=request.param, pipe_na8=0):      # (pipe_na8 = 0: this wave count for every form)
+        yield request.param
 
 
 PIPE = "migan::sepconv_pipe_kernel<"
@@ -77,20 +69,17 @@ def test_plain_layer_with_a_skip_tensor_keeps_the_one_tile_kernel(lib, pkg):
 
 
 def test_pipe_off_takes_the_one_tile_kernels(lib, pkg):
-    lib.set_tuning("pipe", 0)
-    run_sepconv_case(lib, pkg, HostMem(), cin=64, cout=64, h=16, w=32, batch=2, noise=True, seed=3)
-    assert lib.last_kernel().startswith("migan::sepconv_kernel<"), lib.last_kernel()
+    with knobs(lib, pipe=0):
+        run_sepconv_case(lib, pkg, HostMem(), cin=64, cout=64, h=16, w=32, batch=2, noise=True, seed=3)
+        assert lib.last_kernel().startswith("migan::sepconv_kernel<"), lib.last_kernel()
 
 
 def test_single_image_forwards_take_them_too_unless_told_otherwise(lib, pkg):
     run_sepconv_case(lib, pkg, HostMem(), cin=64, cout=64, h=16, w=32, batch=1, noise=True, seed=3)
     assert lib.last_kernel().startswith(PIPE), lib.last_kernel()
-    lib.set_tuning("pipe_min_batch", 2)
-    try:
+    with knobs(lib, pipe_min_batch=2):
         run_sepconv_case(lib, pkg, HostMem(), cin=64, cout=64, h=16, w=32, batch=1, noise=True, seed=3)
         assert lib.last_kernel().startswith("migan::sepconv_kernel<"), lib.last_kernel()
-    finally:
-        lib.set_tuning("pipe_min_batch", 1)
 
 
 DOWN = "migan::sepconv_pipedown_kernel<"
@@ -104,18 +93,17 @@ def test_fused_down(lib, pkg, small_grids, h, w, batch, cin, cout, dna, nb):
     4, 8 or 12 depthwise + FIR waves beside 8, 8 or 4 GEMM / epilogue waves (with 4 and 256 columns: the epilogue at the tile's end)"""
     if small_grids != 4:
         pytest.skip("this kernel's wave split is its own parameter")
-    lib.set_tuning("pipe", 15)
-    lib.set_tuning("pipe_dna", dna)
-    run_sepconv_case(lib, pkg, HostMem(), cin=cin, cout=cout, h=h, w=w, batch=batch, down=2, seed=11)
+    with knobs(lib, pipe=15, pipe_dna=dna):
+        run_sepconv_case(lib, pkg, HostMem(), cin=cin, cout=cout, h=h, w=w, batch=batch, down=2, seed=11)
     if (cin, dna) == (128, 8):
         dna = 4                                         # (no 8 + 8 instantiation for 128 -> 256: two registers short)
     assert lib.last_kernel() == DOWN + f"{cout}, {cin}, 2, {dna}, {nb}>", lib.last_kernel()
 
 
 def test_fused_down_off_takes_the_two_kernel_form(lib, pkg):
-    lib.set_tuning("pipe", 7)
-    run_sepconv_case(lib, pkg, HostMem(), cin=64, cout=128, h=16, w=32, batch=2, down=2, seed=11)
-    assert lib.last_kernel().startswith("migan::sepconv_kernel<3,"), lib.last_kernel()
+    with knobs(lib, pipe=7):
+        run_sepconv_case(lib, pkg, HostMem(), cin=64, cout=128, h=16, w=32, batch=2, down=2, seed=11)
+        assert lib.last_kernel().startswith("migan::sepconv_kernel<3,"), lib.last_kernel()
 
 
 @pytest.mark.parametrize("cin,cout,h,w,batch", [(64, 128, 16, 32, 2), (128, 256, 24, 64, 2)])
@@ -123,15 +111,12 @@ def test_fused_down_equals_the_two_kernel_form_bit_for_bit(lib, pkg, cin, cout, 
     """since round 5 both forms of a down=2 layer evaluate the [1,3,3,1]^2 / 64 FIR separably (vertical (1,3)/8 and (3,1)/8
     partial sums, then the horizontal half) -- another rounding than the 16-tap sum of rounds 1-4, and the same one in both kernels.  The
     fused launch (sepconv_pipedown_kernel) and dwfir_kernel + pointwise GEMM must therefore stay in lockstep: same bits."""
-    lib.set_tuning("pipe", 15)
-    a = run_sepconv_case(lib, pkg, HostMem(), cin=cin, cout=cout, h=h, w=w, batch=batch, down=2, seed=13)
-    assert lib.last_kernel().startswith(DOWN), lib.last_kernel()
-    lib.set_tuning("pipe", 7)
-    try:
+    with knobs(lib, pipe=15):
+        a = run_sepconv_case(lib, pkg, HostMem(), cin=cin, cout=cout, h=h, w=w, batch=batch, down=2, seed=13)
+        assert lib.last_kernel().startswith(DOWN), lib.last_kernel()
+    with knobs(lib, pipe=7):
         b = run_sepconv_case(lib, pkg, HostMem(), cin=cin, cout=cout, h=h, w=w, batch=batch, down=2, seed=13)
         assert lib.last_kernel().startswith("migan::sepconv_kernel<3,"), lib.last_kernel()
-    finally:
-        lib.set_tuning("pipe", 15)
     assert np.array_equal(a, b)
 
 @pytest.mark.parametrize("h,w,batch", [(16, 32, 2), (8, 16, 3), (24, 16, 2)])

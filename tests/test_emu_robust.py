@@ -5,6 +5,7 @@ import importlib
 import pytest
 
 from tests.emu_util import emu_lib
+from tests.knobs import knobs
 from tests.robust_case import KINDS, check_kind
 from tests.sepconv_case import HostMem
 
@@ -32,12 +33,5 @@ def test_nan_mask_follows_the_oracle(pkg, lib, kw, min_tiles):
     oracle has them -- the 3x3 neighbourhood of the element, every output channel, spread by the FIR of the down / up layers"""
     from tests.sepconv_case import run_sepconv_case
     assert lib.nan_policy() == "propagate"
-    lib.set_tuning("pipe_min_tiles", min_tiles)
-    lib.set_tuning("w2_min_tiles", min_tiles)
-    lib.set_tuning("pipe_grid", 8 if min_tiles == 1 else 256)
-    try:
+    with knobs(lib, pipe_min_tiles=min_tiles, w2_min_tiles=min_tiles, **({"pipe_grid": 8} if min_tiles == 1 else {})):
         run_sepconv_case(lib, pkg, HostMem(), seed=13, nan_at=(0, 5, 7, 9), **kw)
-    finally:
-        lib.set_tuning("pipe_min_tiles", 256)
-        lib.set_tuning("w2_min_tiles", 256)
-        lib.set_tuning("pipe_grid", 256)

@@ -2,6 +2,7 @@
 C ABI: 16-bit activation storage (BASELINE configs[1]), 16-channel K-chunk tiles, two sub-batches, static weights,
 per-handle GEMM variants and persistent workgroups (in-process), the arbitrary-size forward and the
 uint8-in / uint8-out forward (N2)."""
+import contextlib
 import os
 
 import numpy as np
@@ -10,6 +11,7 @@ import pytest
 from oracle import migan_oracle as orc
 from oracle import migan_prepost as pp
 from tests.emu_util import aligned, emu_lib, from_storage, storage_close
+from tests.knobs import knobs
 from tests.sepconv_case import HostMem, run_sepconv_case
 
 
@@ -20,18 +22,9 @@ def lib():
 
 @pytest.fixture()
 def tuned(lib):
-    """set process-wide tuning knobs for one test, restore the defaults afterwards"""
-    changed = {}
-    defaults = dict(kc16=0, kc16_minw=3, w3=3, wide=3, nt256=1, persist_min=8192, persist_grid=512, streams=2, stagger=-1,
-                    small=1, small_max_wgs=512, small_kc=64, small_up32=1, small_dwfir=1, small_ksplit=1)
-
-    def set_(key, value):
-        changed[key] = True
-        lib.set_tuning(key, value)
-
-    yield set_
-    for k in changed:
-        lib.set_tuning(k, defaults[k])
+    """set process-wide tuning knobs for one test, put back what was there afterwards"""
+    with contextlib.ExitStack() as stack:
+        yield lambda key, value: stack.enter_context(knobs(lib, **{key: value}))
 
 
 def _sepconv(lib, pkg, **kw):
@@ -424,11 +417,8 @@ def test_forward_hw_vs_reference_goldens(pkg, lib, golden_dir):
 ])
 @pytest.mark.parametrize("wide", [2, 3])
 def test_sepconv_wide_tile_with_dedicated_mfma_waves(lib, pkg, storage, gemm, case, wide):
-    lib.set_tuning("wide", wide)          # 3: + LDS-DMA staging (fp32 storage; other storage formats keep the register path)
-    try:
+    with knobs(lib, wide=wide):           # 3: + LDS-DMA staging (fp32 storage; other storage formats keep the register path)
         _sepconv(lib, pkg, storage=storage, gemm=gemm, **case)
-    finally:
-        lib.set_tuning("wide", 3)
 
 
 # ------------------------------------------------------------------------------------------------ FIR-up layers on the 256-column tile (round 4)
@@ -445,9 +435,6 @@ def test_fir_up_on_the_wide_tile(lib, pkg, case):
     """up=2 SeparableConv2d with Cout % 256 == 0 (fp32 storage, f16x2 GEMM): sepconv_wide_kernel<..., UP>; off -> the 128-column kernel"""
     _sepconv(lib, pkg, storage="f32", gemm=2, up=2, **case)
     assert lib.last_kernel() == WIDE_UP, lib.last_kernel()
-    lib.set_tuning("wide_up", 0)
-    try:
+    with knobs(lib, wide_up=0):
         _sepconv(lib, pkg, storage="f32", gemm=2, up=2, **case)
         assert lib.last_kernel().startswith("migan::sepconv_kernel<2, "), lib.last_kernel()
-    finally:
-        lib.set_tuning("wide_up", 1)

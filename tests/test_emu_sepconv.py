@@ -7,6 +7,7 @@ import pytest
 
 from oracle import migan_oracle as orc
 from tests.emu_util import aligned, emu_lib, nchw, nhwc, ptr
+from tests.knobs import knobs
 
 
 @pytest.fixture(scope="module")
@@ -30,11 +31,8 @@ def variant(request, lib):
         return
     gemm, persist = name.split("+persist")
     _GEMM["code"] = {"f32": 0, "bf16x3": 1, "f16x2": 2}[gemm]
-    lib.set_tuning("persist_min", 2)
-    lib.set_tuning("persist_grid", int(persist))
-    yield name
-    lib.set_tuning("persist_min", 8192)
-    lib.set_tuning("persist_grid", 512)
+    with knobs(lib, persist_min=2, persist_grid=int(persist)):
+        yield name
     _GEMM["code"] = -1
 
 

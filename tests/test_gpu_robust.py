@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from oracle import migan_torch_cpu as torc
+from tests.knobs import knobs
 from tests.robust_case import KINDS, check_kind
 from tests.sepconv_case import CudaMem
 
@@ -81,13 +82,8 @@ NAN_CASES = [dict(cin=64, cout=64, h=32, batch=2), dict(cin=64, cout=128, h=16, 
 def test_nan_operator_mask_follows_the_oracle(pkg, dev, default_lib, kw, min_tiles):
     """one NaN input element: the output is NaN exactly where the oracle's is (the 3x3 neighbourhood, every output channel, FIR spread)"""
     from tests.sepconv_case import run_sepconv_case
-    default_lib.set_tuning("pipe_min_tiles", min_tiles)
-    default_lib.set_tuning("w2_min_tiles", min_tiles)
-    try:
+    with knobs(default_lib, pipe_min_tiles=min_tiles, w2_min_tiles=min_tiles):
         run_sepconv_case(default_lib, pkg, CudaMem(dev), seed=13, nan_at=(0, 5, 7, 9), **kw)
-    finally:
-        default_lib.set_tuning("pipe_min_tiles", 256)
-        default_lib.set_tuning("w2_min_tiles", 256)
 
 
 def test_nan_generator_mask_matches_the_reference_with_several_bad_pixels(pkg, dev):

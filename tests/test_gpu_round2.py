@@ -1,6 +1,8 @@
 """Round-2 parity tests on a real MI355X, through the C ABI: 16-bit activation storage (BASELINE configs[1]), 16-channel
 K-chunk tiles, GEMM variants per handle (in-process), two-stream sub-batches, static weights, the arbitrary-size
 forward, the uint8-in / uint8-out forward (N2) and a batch of 32 distinct images."""
+import contextlib
+
 import numpy as np
 import pytest
 import torch
@@ -8,6 +10,7 @@ import torch
 from oracle import migan_oracle as orc
 from oracle import migan_prepost as pp
 from oracle import migan_torch_cpu as torc
+from tests.knobs import knobs
 from tests.sepconv_case import CudaMem, run_sepconv_case
 
 pytestmark = pytest.mark.gpu
@@ -24,17 +27,8 @@ def dev():
 @pytest.fixture()
 def tuned(pkg):
     lib = pkg.load_library()
-    changed = {}
-    defaults = dict(kc16=0, kc16_minw=3, w3=3, wide=3, nt256=1, persist_min=8192, persist_grid=512, streams=2, stagger=-1,
-                    small=1, small_max_wgs=512, small_kc=64, small_up32=1, small_dwfir=1, small_ksplit=1, pipe=15, wide_up=1)
-
-    def set_(key, value):
-        changed[key] = True
-        lib.set_tuning(key, value)
-
-    yield set_
-    for k in changed:
-        lib.set_tuning(k, defaults[k])
+    with contextlib.ExitStack() as stack:
+        yield lambda key, value: stack.enter_context(knobs(lib, **{key: value}))
 
 
 def _model(pkg, res, seed, dev, regime="export", **kw):

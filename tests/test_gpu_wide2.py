@@ -4,6 +4,7 @@ entry migan_sepconv_forward: against the numpy oracle at the layer sizes of miga
 import numpy as np
 import pytest
 
+from tests.knobs import knobs
 from tests.sepconv_case import CudaMem, run_sepconv_case
 
 pytestmark = pytest.mark.gpu
@@ -26,12 +27,8 @@ def mem():
 # both forms of the weight-plane ring (tuning w2 = 1: 16-channel halves, 2: whole 32-channel chunks, the default)
 @pytest.fixture(autouse=True, params=[1, 2])
 def restore(request, lib):
-    default = 2
-    lib.set_tuning("w2", request.param)
-    yield
-    lib.set_tuning("w2", default)
-    lib.set_tuning("w2_min_tiles", 256)
-    lib.set_tuning("pipe_grid", 256)
+    with knobs(lib, w2=request.param):
+        yield
 
 
 # (cin, cout, h, w, batch): encoder.b128.conv1 / synthesis.b64.conv2 / encoder.b32.conv1 of migan-512 at batch 4..32, a non-square size,
@@ -40,17 +37,16 @@ def restore(request, lib):
                                                 (256, 256, 64, 64, 9)])
 @pytest.mark.parametrize("noise", [False, True])
 def test_plain_layers(lib, pkg, mem, cin, cout, h, w, batch, noise):
-    lib.set_tuning("w2_min_tiles", 1)
-    run_sepconv_case(lib, pkg, mem, cin=cin, cout=cout, h=h, w=w, batch=batch, noise=noise, seed=31)
-    assert lib.last_kernel().startswith(W2), lib.last_kernel()
+    with knobs(lib, w2_min_tiles=1):
+        run_sepconv_case(lib, pkg, mem, cin=cin, cout=cout, h=h, w=w, batch=batch, noise=noise, seed=31)
+        assert lib.last_kernel().startswith(W2), lib.last_kernel()
 
 
 @pytest.mark.parametrize("grid", [8, 64, 256])
 def test_any_number_of_tiles_per_workgroup(lib, pkg, mem, grid):
-    lib.set_tuning("w2_min_tiles", 1)
-    lib.set_tuning("pipe_grid", grid)
-    run_sepconv_case(lib, pkg, mem, cin=256, cout=256, h=64, w=64, batch=5, noise=True, seed=33)
-    assert lib.last_kernel().startswith(W2), lib.last_kernel()
+    with knobs(lib, w2_min_tiles=1, pipe_grid=grid):
+        run_sepconv_case(lib, pkg, mem, cin=256, cout=256, h=64, w=64, batch=5, noise=True, seed=33)
+        assert lib.last_kernel().startswith(W2), lib.last_kernel()
 
 
 @pytest.mark.parametrize("noise", [True, False])          # (False: the act1g epilogue without the noise term -- ADVICE round 5)
@@ -60,9 +56,9 @@ def test_bit_identical_to_the_128_pixel_tile_and_run_to_run(lib, pkg, mem, cin, 
     assert lib.last_kernel().startswith(W2), lib.last_kernel()
     a2 = run_sepconv_case(lib, pkg, mem, cin=cin, cout=cout, h=h, w=h, batch=batch, noise=noise, seed=35)
     assert np.array_equal(a, a2)
-    lib.set_tuning("w2", 0)
-    b = run_sepconv_case(lib, pkg, mem, cin=cin, cout=cout, h=h, w=h, batch=batch, noise=noise, seed=35)
-    assert lib.last_kernel().startswith("migan::sepconv_wide_kernel<"), lib.last_kernel()
+    with knobs(lib, w2=0):
+        b = run_sepconv_case(lib, pkg, mem, cin=cin, cout=cout, h=h, w=h, batch=batch, noise=noise, seed=35)
+        assert lib.last_kernel().startswith("migan::sepconv_wide_kernel<"), lib.last_kernel()
     assert np.array_equal(a, b)
 
 
@@ -72,12 +68,9 @@ def test_pointwise_half_of_a_down2_layer(lib, pkg, mem, cin, cout, h, batch):
     and bit for bit against the 128-column pointwise tiles"""
     a = run_sepconv_case(lib, pkg, mem, cin=cin, cout=cout, h=h, w=h, batch=batch, down=2, seed=39)
     assert lib.last_kernel() == "migan::sepconv_wide2_kernel<3>", lib.last_kernel()
-    lib.set_tuning("w2_pw", 0)
-    try:
+    with knobs(lib, w2_pw=0):
         b = run_sepconv_case(lib, pkg, mem, cin=cin, cout=cout, h=h, w=h, batch=batch, down=2, seed=39)
         assert lib.last_kernel().startswith("migan::sepconv_kernel<3,"), lib.last_kernel()
-    finally:
-        lib.set_tuning("w2_pw", 1)
     assert np.array_equal(a, b)
 
 
@@ -98,8 +91,8 @@ def test_generator_any_size_with_and_without_the_256_pixel_tile(lib, pkg):
     with torch.no_grad():                                 # (default threshold: 60 tiles x 6 images >= 256 > 60 x 2)
         y2 = m.forward_any_size(x2)
         y12 = m.forward_any_size(x2.repeat(6, 1, 1, 1))
-        lib.set_tuning("w2", 0)
-        y12_off = m.forward_any_size(x2.repeat(6, 1, 1, 1))
+        with knobs(lib, w2=0):
+            y12_off = m.forward_any_size(x2.repeat(6, 1, 1, 1))
     assert bool(torch.isfinite(y12).all())
     assert torch.equal(y12, y2.repeat(6, 1, 1, 1))
     assert torch.equal(y12, y12_off)

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from tests.emu_util import aligned, emu_lib
+from tests.knobs import knobs
 
 
 @pytest.fixture(scope="module")
@@ -65,8 +66,7 @@ def test_a_failed_plan_is_not_cached(pkg, lib):
 def test_sub_batch_stagger_is_clamped_to_an_existing_launch(pkg, lib, pct):
     """stagger_pct = 100 used to index one past the last launch: the event the next sub-batch waits on was never recorded"""
     res = 8
-    lib.set_tuning("stagger_pct", pct)
-    try:
+    with knobs(lib, stagger_pct=pct):
         h, sd, keep = _bind(pkg, lib, res, seed=6)
         x = pkg.synth.make_input(16, res, seed=6)
         outs = []
@@ -78,8 +78,6 @@ def test_sub_batch_stagger_is_clamped_to_an_existing_launch(pkg, lib, pct):
             h.forward(xa.ctypes.data, y.ctypes.data, 16, ws.ctypes.data, need)
             outs.append(y.copy())
         np.testing.assert_array_equal(outs[0], outs[1])
-    finally:
-        lib.set_tuning("stagger_pct", 22)
 
 
 def test_default_gemm_name_resolves_per_storage_format(pkg, lib):
