@@ -774,12 +774,13 @@ inline void launch_torgb(const RgbArgs& a, rt::stream_t stream, int stv = 0) {
 
 enum Role { R_DW_W, R_DW_B, R_PW_W, R_RGB_W, R_RGB_B, R_FIR_DOWN, R_FIR_UP, R_FILTER_CONST, R_NOISE_CONST, R_NOISE_STRENGTH };
 
+// one state_dict entry of either model (role: Role here, CmRole in comodgan_host.hpp)
 struct Slot {
   std::string name;
   int64_t shape[4] = {0, 0, 0, 0};
   int ndim = 0;
   bool is_buffer = false;
-  Role role = R_DW_W;
+  int role = 0;
   const float* ptr = nullptr;
   size_t numel() const {
     size_t n = 1;
@@ -787,6 +788,41 @@ struct Slot {
     return n;
   }
 };
+
+inline int slot_index(const std::vector<Slot>& slots, const std::string& n) {
+  for (size_t i = 0; i < slots.size(); ++i)
+    if (slots[i].name == n) return (int)i;
+  return -1;
+}
+inline void add_slot(std::vector<Slot>& slots, const std::string& n, std::initializer_list<int64_t> shp, bool is_buf, int role) {
+  Slot s;
+  s.name = n;
+  s.ndim = (int)shp.size();
+  int i = 0;
+  for (auto v : shp) s.shape[i++] = v;
+  s.is_buffer = is_buf;
+  s.role = role;
+  slots.push_back(s);
+}
+// bodies of migan_weight_info / comodgan_weight_info and of the lookup + shape check of *_set_weight
+inline void slot_info(const std::vector<Slot>& slots, int index, const char** name, int64_t shape[4], int* ndim, int* is_buffer) {
+  MIGAN_CHECK(index >= 0 && index < (int)slots.size(), MIGAN_EINVAL, "weight index out of range");
+  const Slot& s = slots[index];
+  if (name) *name = s.name.c_str();
+  if (shape)
+    for (int i = 0; i < 4; ++i) shape[i] = s.shape[i];
+  if (ndim) *ndim = s.ndim;
+  if (is_buffer) *is_buffer = s.is_buffer ? 1 : 0;
+}
+inline Slot& slot_of_key(std::vector<Slot>& slots, const char* name) {
+  const int i = slot_index(slots, name);
+  MIGAN_CHECK(i >= 0, MIGAN_EINVAL, std::string("unexpected key in state_dict: ") + name);
+  return slots[i];
+}
+inline void check_slot_shape(const Slot& s, const char* name, const int64_t* shape, int ndim) {
+  MIGAN_CHECK(ndim == s.ndim, MIGAN_EINVAL, std::string("size mismatch for ") + name);
+  for (int d = 0; d < ndim; ++d) MIGAN_CHECK(shape && shape[d] == s.shape[d], MIGAN_EINVAL, std::string("size mismatch for ") + name);
+}
 
 inline int channels_at(int res) {
   const int c = 32768 / res;
@@ -858,20 +894,9 @@ struct migan_handle {
   rt::stream_t prepared_stream{};
   unsigned long long weight_epoch = 1, prepared_epoch = 0;
 
-  int slot_index(const std::string& n) const {
-    for (size_t i = 0; i < slots.size(); ++i)
-      if (slots[i].name == n) return (int)i;
-    return -1;
-  }
+  int slot_index(const std::string& n) const { return migan::slot_index(slots, n); }
   void add_slot(const std::string& n, std::initializer_list<int64_t> shp, bool is_buf, migan::Role role) {
-    migan::Slot s;
-    s.name = n;
-    s.ndim = (int)shp.size();
-    int i = 0;
-    for (auto v : shp) s.shape[i++] = v;
-    s.is_buffer = is_buf;
-    s.role = role;
-    slots.push_back(s);
+    migan::add_slot(slots, n, shp, is_buf, role);
   }
   void add_sepconv_slots(const std::string& p, int cin, int cout, int res_out, bool down, bool up, bool noise) {
     using namespace migan;
@@ -1506,25 +1531,16 @@ int migan_num_weights(const migan_handle* h, int* n) {
 int migan_weight_info(const migan_handle* h, int index, const char** name, int64_t shape[4], int* ndim, int* is_buffer) {
   MIGAN_API_BEGIN
   MIGAN_CHECK(h, MIGAN_EINVAL, "null handle");
-  MIGAN_CHECK(index >= 0 && index < (int)h->slots.size(), MIGAN_EINVAL, "weight index out of range");
-  const migan::Slot& s = h->slots[index];
-  if (name) *name = s.name.c_str();
-  if (shape)
-    for (int i = 0; i < 4; ++i) shape[i] = s.shape[i];
-  if (ndim) *ndim = s.ndim;
-  if (is_buffer) *is_buffer = s.is_buffer ? 1 : 0;
+  migan::slot_info(h->slots, index, name, shape, ndim, is_buffer);
   MIGAN_API_END
 }
 
 int migan_set_weight(migan_handle* h, const char* name, const void* dev_ptr, const int64_t* shape, int ndim) {
   MIGAN_API_BEGIN
   MIGAN_CHECK(h && name, MIGAN_EINVAL, "null argument");
-  const int i = h->slot_index(name);
-  MIGAN_CHECK(i >= 0, MIGAN_EINVAL, std::string("unexpected key in state_dict: ") + name);
-  migan::Slot& s = h->slots[i];
+  migan::Slot& s = migan::slot_of_key(h->slots, name);
   MIGAN_CHECK(dev_ptr != nullptr, MIGAN_EINVAL, std::string("null pointer for ") + name);
-  MIGAN_CHECK(ndim == s.ndim, MIGAN_EINVAL, std::string("size mismatch for ") + name);
-  for (int d = 0; d < ndim; ++d) MIGAN_CHECK(shape && shape[d] == s.shape[d], MIGAN_EINVAL, std::string("size mismatch for ") + name);
+  migan::check_slot_shape(s, name, shape, ndim);
   MIGAN_CHECK((reinterpret_cast<uintptr_t>(dev_ptr) & 15) == 0 || s.numel() < 4, MIGAN_EINVAL,
               std::string("tensor must be 16-byte aligned: ") + name);
   s.ptr = static_cast<const float*>(dev_ptr);

@@ -249,3 +249,38 @@ def test_assume_static_weights_skips_the_weight_preparation():
     y5 = fwd()
     assert np.abs(y5 - y1).max() <= 2e-5 * max(1.0, np.abs(y1).max())
     h.close()
+
+
+def test_forced_form_changed_between_two_forwards_plans_again(monkeypatch):
+    """The plan (launch list, timing events, workspace size) is keyed on the forced kernel forms: after COMODGAN_UP4 changes
+    between two forwards of one handle and batch, the timed forward, its timings and launches() are all those of the new
+    form (one conv0 launch becomes four), never a mix of the cached plan and the launches actually made."""
+    lib = emu_lib()
+    g, cfg, sd, x, z = case("r32_c128_psi")
+    monkeypatch.delenv("COMODGAN_UP4", raising=False)
+    h = hb.CoModGANHandle(lib, cfg.resolution, cfg.num_ws, cfg.ch_base, cfg.ch_max)
+    keep = {k: aligned(v) for k, v in sd.items()}
+    for name, shape, _ in h.weights():
+        h.set_weight(name, keep[name].ctypes.data, shape)
+    h.commit()
+    n = x.shape[0]
+    xa, za = aligned(x), aligned(z)
+
+    def timed_forward():
+        nbytes = h.workspace_bytes(n)
+        ws = np.zeros(nbytes // 4 + 64, dtype=np.float32)
+        wsv = ws[(256 - ws.ctypes.data % 256) % 256 // 4:]
+        y = aligned(np.zeros((n, 3, cfg.resolution, cfg.resolution), np.float32))
+        ms = h.forward(xa.ctypes.data, za.ctypes.data, y.ctypes.data, n, wsv.ctypes.data, nbytes, truncation_psi=float(g["psi"]), timed=True)
+        return y.copy(), ms, h.launches()
+
+    y1, ms1, info1 = timed_forward()
+    blocks = [8, 16, 32]
+    assert len(ms1) == len(info1)
+    assert [i["layer"] for i in info1 if ".conv0.phase" in i["layer"]] == [f"synthesis.b{r}.conv0.phases" for r in blocks]
+    monkeypatch.setenv("COMODGAN_UP4", "0")
+    y4, ms4, info4 = timed_forward()
+    assert len(ms4) == len(info4) == len(info1) + 3 * len(blocks)
+    assert [i["layer"] for i in info4 if ".conv0.phase" in i["layer"]] == [f"synthesis.b{r}.conv0.phase{p}" for r in blocks for p in range(4)]
+    assert np.abs(y4 - y1).max() <= 1e-3 and np.abs(y4 - g["y"]).max() <= 1e-3
+    h.close()
