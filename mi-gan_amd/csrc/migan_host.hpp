@@ -684,7 +684,9 @@ struct SepLaunch {
 // The kernel family of a launch, first match: pipelined persistent form, 256 x 256 tile, 128 x 256 wide tile, sepconv_kernel table.
 // n_decide: the batch the kernel FORM is chosen for (0 = a.B); grids are sized for a.B, the batch actually launched.  The per-launch timing run
 // launches the whole batch at once but must time the forms the production forward -- sub-batches on staggered streams -- launches.
-inline SepLaunch resolve_sepconv(Geo g, const SepArgs& a, int n_decide = 0) {
+// out_dead: no later launch reads a.y (Launch::out_dead); a form whose fused ToRGB tail can run without writing the feature map gets y = nullptr and
+// skips that store, every other form keeps the pointer and stores.  The network output is the same bits either way.
+inline SepLaunch resolve_sepconv(Geo g, const SepArgs& a, int n_decide = 0, bool out_dead = false) {
   const bool fused_rgb = a.trgb_w != nullptr;
   const int nd = n_decide > 0 ? n_decide : a.B;
   const unsigned pipe_grid = (unsigned)tuning().pipe_grid;
@@ -692,6 +694,7 @@ inline SepLaunch resolve_sepconv(Geo g, const SepArgs& a, int n_decide = 0) {
     MIGAN_CHECK(a.wsplit != nullptr, MIGAN_EINVAL, "internal: the pipelined kernel needs the fp16 weight planes");
     SepLaunch l{pe->fn, pe->name, 0, (unsigned)pipe_threads(pe->na), pe->lds_bytes, a};
     l.args.nchunks = a.CO / pe->NT;                      // (FIR-up: 64-column chunks, see pick_pipe)
+    if (out_dead && pe->torgb) l.args.y = nullptr;       // sepconv_pipe_kernel<MODE_NORMAL, ..., TORGB = true, ...>: finish_block tests p.y
     l.grid = std::min((unsigned)(g.tiles_x * g.tiles_y * l.args.nchunks * a.B), pipe_grid);
     return l;
   }
@@ -717,9 +720,9 @@ inline SepLaunch resolve_sepconv(Geo g, const SepArgs& a, int n_decide = 0) {
   return SepLaunch{k.fn, k.name, grid_of(g, a.B, fused_rgb), (unsigned)kThreads, g.lds_bytes, a};
 }
 // returns the symbol it launched
-inline const char* launch_sepconv(const Geo& g, const SepArgs& a, rt::stream_t stream, int n_decide = 0) {
+inline const char* launch_sepconv(const Geo& g, const SepArgs& a, rt::stream_t stream, int n_decide = 0, bool out_dead = false) {
   prepare_kernels();
-  const SepLaunch l = resolve_sepconv(g, a, n_decide);
+  const SepLaunch l = resolve_sepconv(g, a, n_decide, out_dead);
   rt_check(rt::launch(l.fn, l.args, l.grid, l.threads, l.lds_bytes, stream), l.name);
   return last_kernel_ref() = l.name;
 }
@@ -843,6 +846,7 @@ struct Launch {
   bool narrow = false;               // fewer than 64 channels on either side (resolutions above 512): narrow_sepconv_kernel<mode, fromrgb>
   int mode = MODE_NORMAL;            // (narrow launches: the SeparableConv2d's down / up)
   bool fromrgb = false;
+  bool out_dead = false;             // ToRGB is fused into this launch and no later launch reads out_buf: the feature map need not be written
   Geo g;
   std::vector<Geo> g_small;          // small-tile variants of g, smallest tile first: the first one whose tile count for the launch is at
                                      // most tuning().small_max_wgs runs instead of g
@@ -1193,6 +1197,19 @@ inline void migan_handle::build_plan(migan::Plan& P, int H, int W) const {
   for (Launch& L : P.launches)
     if (L.noise_plane_off >= 0) L.noise_plane_off += (long long)wbytes;
   P.shared_bytes = wbytes + noise_bytes;
+  // A launch with the ToRGB tail fused in hands its feature map to that tail in registers; where no later launch reads the map from the
+  // workspace either (the last SeparableConv2d of the generator), writing it is traffic for nothing.  Debug plans keep every tensor.
+  if (!debug)
+    for (size_t i = 0; i < P.launches.size(); ++i) {
+      Launch& L = P.launches[i];
+      if (L.is_rgb || L.is_dwfir || L.narrow || L.w_trgb < 0 || !L.g.torgb || L.g.nchunks != 1 || L.out_buf < 0) continue;
+      bool read_later = false;
+      for (size_t j = i + 1; j < P.launches.size(); ++j) {
+        const Launch& N = P.launches[j];
+        read_later = read_later || N.in_buf == L.out_buf || N.skip_buf == L.out_buf || N.imgprev_buf == L.out_buf;
+      }
+      L.out_dead = !read_later;
+    }
   // the next sub-batch starts when the previous one is about a fifth of its launches in (measured on MI355X, migan-512 and
   // migan-256, batch 32: +6 % at launch 8..12 of 46 / 40, nothing at 4 or 20; profiles/r02_streams_stagger_sweep.txt)
   P.stagger = (int)P.launches.size() * tuning().stagger_pct / 100;
@@ -1311,7 +1328,7 @@ inline void migan_handle::run_range(const migan::Plan& P, const float* x, float*
       }
       const Geo& G = *Gp;
       fill_geo(a, G);
-      L.kernel_last = launch_sepconv(G, a, stream, nd);
+      L.kernel_last = launch_sepconv(G, a, stream, nd, L.out_dead);
     }
     if (timed) rt_check(rt::event_record(events[2 * li + 1], stream), "hipEventRecord");
     if (!timed && (int)li == mid_after) rt_check(rt::event_record(ev_mid[part], stream), "hipEventRecord");

@@ -722,18 +722,40 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(pipe_threads(NA), (NA + kPipeBWaves) / 4) 
 #pragma unroll
       for (int q = 0; q < 4; ++q) tv[q] = ld4(t_s + ((q & 1) ? trd1 : trd0) + q * 8 * 32);
     };
+    // The last layer of a generator: the ToRGB tail below takes the feature map from registers and no later launch reads it, so the host
+    // passes y = nullptr (migan_host.hpp, Launch::out_dead) and the map is never written.  A kernel argument: one scalar per workgroup.
+    // The four values of a block are finished first and the stores sit together behind that one uniform branch: no load -> use pair spans
+    // a store that may or may not have been issued, so the waits in front of the noise values stay counted on both paths.
+    const bool store_y = !TORGB || p.y != nullptr;
     auto finish_block = [&](int j) {
       char* yb = reinterpret_cast<char*>(p.y) + (size_t)pb0 * img_out_bytes;
+      if constexpr (TORGB) {
+        const unsigned col = (unsigned)(pn0 + cbk * (NT / 2) + j * 32 + q4 * 4);
+        f4 v[4];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        f4 v = tv[q] * acc_scale + MIGAN_FMUL_RN(nz[q], ns);        // product rounded first, reference :166
-        v = act4(v);
-        const unsigned pix = pix0 + (unsigned)((q >> 1) * p.WO + (q & 1) * 8);
-        Io<0>::st(yb, (pix * (unsigned)p.CO + (unsigned)(pn0 + cbk * (NT / 2) + j * 32 + q4 * 4)) * 4u, v);
-        if constexpr (TORGB) {
+        for (int q = 0; q < 4; ++q) v[q] = act4(tv[q] * acc_scale + MIGAN_FMUL_RN(nz[q], ns));      // product rounded first, reference :166
+        if (store_y) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const unsigned pix = pix0 + (unsigned)((q >> 1) * p.WO + (q & 1) * 8);
+            Io<0>::st(yb, (pix * (unsigned)p.CO + col) * 4u, v[q]);
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
           float r0, r1, r2;
-          torgb_partial(v, tw[j][0], tw[j][1], tw[j][2], r0, r1, r2);
+          torgb_partial(v[q], tw[j][0], tw[j][1], tw[j][2], r0, r1, r2);
           rs[q][0] += r0; rs[q][1] += r1; rs[q][2] += r2;
+        }
+      } else {
+        // (the same arithmetic as above, value by value: the forms without ToRGB always store, and this order is the one their
+        // schedule was tuned and measured with -- written apart so that they compile to the code they had before the branch existed)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          f4 v = tv[q] * acc_scale + MIGAN_FMUL_RN(nz[q], ns);        // product rounded first, reference :166
+          v = act4(v);
+          const unsigned pix = pix0 + (unsigned)((q >> 1) * p.WO + (q & 1) * 8);
+          Io<0>::st(yb, (pix * (unsigned)p.CO + (unsigned)(pn0 + cbk * (NT / 2) + j * 32 + q4 * 4)) * 4u, v);
         }
       }
     };
