@@ -157,6 +157,31 @@ int migan_pipeline_pre(const void* image_chw_u8, const void* mask_u8, int height
 int migan_pipeline_post(void* image_chw_u8, const void* mask_u8, int height, int width, const int bbox[4], int resolution,
                         const void* y_nchw, const float* gauss25, void* scratch, void* stream);
 
+/* The same pipeline for a BATCH of images of different sizes around ONE generator forward, without a host synchronisation between
+ * the first and the last kernel: the boxes are computed on the device and stay there.  Each image gets exactly what the three
+ * calls above give it (same bbox, same x, byte-identical result for the same y).
+ *   items     HOST array of n items (read during the call only); any n >= 1, launches carry 32 items each
+ *   x_nchw    [n][4][R][R] fp32, the generator's input; y_nchw [n][3][R][R] fp32, its output
+ *   bbox_dev  DEVICE int[n][4], row i = {x_min, x_max, y_min, y_max} of item i: written by _pre, read by _post.  _post leaves an
+ *             item whose row does not lie inside its image or is smaller than 3x3 untouched (it cannot be refused on the host)
+ *   scratch   migan_pipeline_batch_scratch_bytes(items, n) bytes of device memory, the same for _pre and _post of one batch
+ *             (holds the resized masks between the two calls)
+ * A mask of another size than its image is resized first (nearest), like migan_pipeline_mask_resize.  Every side >= 3, fewer than
+ * 2^30 pixels per image.  Two items that name the same image (or overlapping memory) are UNDEFINED: _post writes the images in
+ * place, in no order. */
+typedef struct migan_pipeline_item {
+  void* image_chw_u8;          /* [3][height][width], written in place by _post */
+  const void* mask_u8;         /* [mask_height][mask_width], 255 = known pixel */
+  int height, width, mask_height, mask_width;
+} migan_pipeline_item;
+int migan_pipeline_batch_scratch_bytes(const migan_pipeline_item* items, int n, size_t* bytes);
+/* resize masks where needed -> row / column flags -> boxes -> network input */
+int migan_pipeline_batch_pre(const migan_pipeline_item* items, int n, int resolution, int padding, void* x_nchw, int* bbox_dev,
+                             void* scratch, void* stream);
+/* 3x3 max-pool + 5x5 blur of the mask, resize of y to the crop, blend: one kernel.  gauss25 as in migan_pipeline_post */
+int migan_pipeline_batch_post(const migan_pipeline_item* items, int n, int resolution, const void* y_nchw, const int* bbox_dev,
+                              const float* gauss25, void* scratch, void* stream);
+
 /* ---- measurement and debugging ---------------------------------------------------------- */
 
 /* The forward is a fixed sequence of kernel launches (one per SeparableConv2d, plus un-fused

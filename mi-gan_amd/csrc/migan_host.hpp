@@ -1879,6 +1879,17 @@ static void migan_pipeline_check_bbox(const int bbox[4], int height, int width) 
   MIGAN_CHECK(bbox[0] >= 0 && bbox[1] <= width && bbox[2] >= 0 && bbox[3] <= height && bbox[1] - bbox[0] >= 3 && bbox[3] - bbox[2] >= 3,
               MIGAN_EINVAL, "bbox = {x_min, x_max, y_min, y_max} must lie inside the image and be at least 3x3");
 }
+// the module's 5x5 weight buffer, or GaussianSmoothing(3, 5, 1) (:63-85) computed here
+static void migan_pipeline_gauss(const float* gauss25, float out[25]) {
+  if (gauss25) {
+    for (int i = 0; i < 25; ++i) out[i] = gauss25[i];
+    return;
+  }
+  float g[5], sum = 0.0f;
+  for (int i = 0; i < 5; ++i) { const float t = ((float)i - 2.0f) / 2.0f; g[i] = (float)(1.0 / std::sqrt(2.0 * M_PI)) * std::exp(-(t * t)); }
+  for (int i = 0; i < 25; ++i) { out[i] = g[i / 5] * g[i % 5]; sum += out[i]; }
+  for (int i = 0; i < 25; ++i) out[i] /= sum;
+}
 int migan_pipeline_scratch_bytes(int height, int width, size_t* bytes) {
   MIGAN_API_BEGIN
   MIGAN_CHECK(bytes && height > 0 && width > 0, MIGAN_EINVAL, "bad argument");
@@ -1897,7 +1908,7 @@ int migan_pipeline_mask_resize(const void* mask_u8, int mask_height, int mask_wi
   MIGAN_API_END
 }
 // get_masked_bbox (:132-231).  The per-row / per-column "contains a pixel below 255" flags are computed on the device, copied to
-// the host (this call synchronises `stream`), and the box arithmetic -- a dozen integer min/max, the reference's own order -- runs here.
+// the host (this call synchronises `stream`), and the box arithmetic (pipe_box) runs here.
 int migan_pipeline_bbox(const void* mask_u8, int height, int width, int resolution, int padding, void* scratch, int bbox[4], void* stream) {
   MIGAN_API_BEGIN
   using namespace migan;
@@ -1912,18 +1923,7 @@ int migan_pipeline_bbox(const void* mask_u8, int height, int width, int resoluti
   int x_min = width, x_max = 0, y_min = height, y_max = 0;                         // :149-152 (min over [..., w], max over [..., 0])
   for (int x = 0; x < width; ++x) if (f[x]) { x_min = std::min(x_min, x); x_max = std::max(x_max, x); }
   for (int y = 0; y < height; ++y) if (f[width + y]) { y_min = std::min(y_min, y); y_max = std::max(y_max, y); }
-  x_min = std::min(x_min, x_max); x_max = std::max(x_min, x_max);                  // :154-172
-  y_min = std::min(y_min, y_max); y_max = std::max(y_min, y_max);
-  const int cnt_x = (x_min + x_max) / 2, cnt_y = (y_min + y_max) / 2;              // :174-175
-  int crop = std::max(x_max - x_min, y_max - y_min) + 2 * padding;                 // :177-180
-  crop = std::max(crop, resolution);                                               // :181-184
-  const int off = crop / 2;                                                        // :186
-  x_min = std::max(cnt_x - off, 0); x_max = std::min(cnt_x + off, width);          // :187-202
-  y_min = std::max(cnt_y - off, 0); y_max = std::min(cnt_y + off, height);
-  const int xe = std::max(crop - (x_max - x_min), 0), ye = std::max(crop - (y_max - y_min), 0);   // :204-211
-  x_min = std::max(x_min - xe, 0); x_max = std::min(x_max + xe, width);            // :213-229
-  y_min = std::max(y_min - ye, 0); y_max = std::min(y_max + ye, height);
-  bbox[0] = x_min; bbox[1] = x_max; bbox[2] = y_min; bbox[3] = y_max;
+  pipe_box(x_min, x_max, y_min, y_max, width, height, resolution, padding, bbox);  // :154-229 (migan_pipeline.hpp)
   MIGAN_API_END
 }
 // preprocess (:233-239) of image[:, y_min:y_max, x_min:x_max] -> the network input x [1][4][R][R]
@@ -1952,20 +1952,119 @@ int migan_pipeline_post(void* image_chw_u8, const void* mask_u8, int height, int
   a.image = (unsigned char*)image_chw_u8; a.mask = (const unsigned char*)mask_u8; a.y = (const float*)y_nchw;
   a.pooled = (unsigned char*)scratch + align256((size_t)(height + width) * sizeof(int));
   a.H = height; a.W = width; a.R = resolution; a.x_min = bbox[0]; a.x_max = bbox[1]; a.y_min = bbox[2]; a.y_max = bbox[3];
-  if (gauss25) {
-    for (int i = 0; i < 25; ++i) a.gauss[i] = gauss25[i];
-  } else {                                                                         // GaussianSmoothing(3, 5, 1) (:63-85)
-    float g[5], sum = 0.0f;
-    for (int i = 0; i < 5; ++i) { const float t = ((float)i - 2.0f) / 2.0f; g[i] = (float)(1.0 / std::sqrt(2.0 * M_PI)) * std::exp(-(t * t)); }
-    for (int i = 0; i < 25; ++i) { a.gauss[i] = g[i / 5] * g[i % 5]; sum += a.gauss[i]; }
-    for (int i = 0; i < 25; ++i) a.gauss[i] /= sum;
-  }
+  migan_pipeline_gauss(gauss25, a.gauss);
   const unsigned grid = (unsigned)cdiv((bbox[1] - bbox[0]) * (bbox[3] - bbox[2]), kThreads);
   rt_check(rt::launch(pipe_maxpool_kernel, a, grid, kThreads, 0, (rt::stream_t)stream), "migan::pipe_maxpool_kernel");
   rt_check(rt::launch(pipe_post_kernel, a, grid, kThreads, 0, (rt::stream_t)stream), "migan::pipe_post_kernel");
   MIGAN_API_END
 }
 
+
+// ---- the batch form of the deployed pipeline: n images of different sizes, the box stays on the device ----
+// Scratch of a batch: per item its H + W flags, and the nearest resize of its mask when that has another size.  No pooled-mask
+// plane (pipe_post_batch_kernel keeps it in LDS).  One layout for _scratch_bytes, _pre and _post; it also checks the items.
+static size_t migan_pipeline_batch_plan(const migan_pipeline_item* items, int n, bool need_pointers, void* scratch,
+                                        std::vector<migan::PipeBatchItem>* out) {
+  using namespace migan;
+  MIGAN_CHECK(items != nullptr && n >= 1, MIGAN_EINVAL, "the batch needs at least one item");
+  size_t bytes = 0;
+  if (out) out->resize((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    const migan_pipeline_item& it = items[i];
+    MIGAN_CHECK(!need_pointers || (it.image_chw_u8 && it.mask_u8), MIGAN_EINVAL, "null image or mask in item " + std::to_string(i));
+    MIGAN_CHECK(it.height >= 3 && it.width >= 3 && (unsigned long long)it.height * it.width < (1ull << 30), MIGAN_EINVAL,
+                "item " + std::to_string(i) + ": image must be at least 3x3 (reflect padding of the 5x5 blur) and below 2^30 pixels");
+    MIGAN_CHECK(it.mask_height > 0 && it.mask_width > 0 && (unsigned long long)it.mask_height * it.mask_width < (1ull << 30), MIGAN_EINVAL,
+                "item " + std::to_string(i) + ": bad mask size");
+    const bool resize = it.mask_height != it.height || it.mask_width != it.width;
+    if (out) {
+      PipeBatchItem& b = (*out)[(size_t)i];
+      b.image = (unsigned char*)it.image_chw_u8; b.mask_src = (const unsigned char*)it.mask_u8;
+      b.flags = (int*)((char*)scratch + bytes);
+      b.mask_resized = resize ? (unsigned char*)scratch + bytes + align256((size_t)(it.height + it.width) * sizeof(int)) : nullptr;
+      b.H = it.height; b.W = it.width; b.mh = it.mask_height; b.mw = it.mask_width;
+    }
+    bytes += align256((size_t)(it.height + it.width) * sizeof(int)) + (resize ? align256((size_t)it.height * it.width) : 0);
+  }
+  return bytes;
+}
+// one kernel over all items, kPipeBatchMax (and fewer than 2^31 workgroups) per launch: tiles(item) workgroups for each
+extern "C++" template <class Tiles>
+static void migan_pipeline_batch_run(void (*kernel)(const migan::PipeBatchArgs), const char* name, const migan::PipeBatchArgs& proto,
+                                     const std::vector<migan::PipeBatchItem>& items, Tiles tiles, size_t lds, void* stream) {
+  using namespace migan;
+  const size_t plane = (size_t)proto.R * proto.R;
+  for (size_t i0 = 0; i0 < items.size();) {
+    PipeBatchArgs a = proto;
+    unsigned long long total = 0;
+    int k = 0;
+    for (; k < kPipeBatchMax && i0 + k < items.size(); ++k) {
+      const unsigned long long t = tiles(items[i0 + k]);
+      if (k > 0 && total + t > 0x7fffffffull) break;
+      a.item[k] = items[i0 + k];
+      a.first[k] = (int)total;
+      total += t;
+    }
+    a.first[k] = (int)total;
+    a.n = k;
+    if (a.x) a.x += i0 * 4 * plane;
+    if (a.y) a.y += i0 * 3 * plane;
+    a.bbox += i0 * 4;
+    if (total) rt_check(rt::launch(kernel, a, (unsigned)total, kThreads, lds, (rt::stream_t)stream), name);
+    i0 += (size_t)k;
+  }
+}
+static void migan_pipeline_batch_check(int resolution, const int* bbox_dev, const void* scratch) {
+  MIGAN_CHECK(resolution >= 8 && (resolution & (resolution - 1)) == 0, MIGAN_EINVAL, "resolution must be a power of two >= 8");
+  MIGAN_CHECK(bbox_dev && scratch, MIGAN_EINVAL, "null bbox or scratch");
+}
+int migan_pipeline_batch_scratch_bytes(const migan_pipeline_item* items, int n, size_t* bytes) {
+  MIGAN_API_BEGIN
+  MIGAN_CHECK(bytes, MIGAN_EINVAL, "bad argument");
+  *bytes = migan_pipeline_batch_plan(items, n, false, nullptr, nullptr);
+  MIGAN_API_END
+}
+// mask resize where needed -> flags -> boxes -> network input, all on `stream`, nothing read back
+int migan_pipeline_batch_pre(const migan_pipeline_item* items, int n, int resolution, int padding, void* x_nchw, int* bbox_dev,
+                             void* scratch, void* stream) {
+  MIGAN_API_BEGIN
+  using namespace migan;
+  migan_pipeline_batch_check(resolution, bbox_dev, scratch);
+  MIGAN_CHECK(x_nchw && padding >= 0, MIGAN_EINVAL, "bad argument");
+  std::vector<PipeBatchItem> its;
+  migan_pipeline_batch_plan(items, n, true, scratch, &its);
+  PipeBatchArgs a{};
+  a.x = (float*)x_nchw; a.bbox = bbox_dev; a.R = resolution; a.padding = padding;
+  auto pixels = [](const PipeBatchItem& it) { return (unsigned long long)cdiv(it.H * it.W, kThreads); };
+  migan_pipeline_batch_run(pipe_mask_resize_batch_kernel, "migan::pipe_mask_resize_batch_kernel", a, its,
+                           [&](const PipeBatchItem& it) { return it.mask_resized ? pixels(it) : 0ull; }, 0, stream);
+  migan_pipeline_batch_run(pipe_flags_clear_batch_kernel, "migan::pipe_flags_clear_batch_kernel", a, its,
+                           [](const PipeBatchItem& it) { return (unsigned long long)cdiv(it.H + it.W, kThreads); }, 0, stream);
+  migan_pipeline_batch_run(pipe_flags_batch_kernel, "migan::pipe_flags_batch_kernel", a, its, pixels, 0, stream);
+  migan_pipeline_batch_run(pipe_bbox_batch_kernel, "migan::pipe_bbox_batch_kernel", a, its, [](const PipeBatchItem&) { return 1ull; },
+                           4 * kThreads * sizeof(int), stream);
+  const unsigned long long per_item = (unsigned long long)cdiv(resolution * resolution, kThreads);
+  migan_pipeline_batch_run(pipe_pre_batch_kernel, "migan::pipe_pre_batch_kernel", a, its, [=](const PipeBatchItem&) { return per_item; }, 0, stream);
+  MIGAN_API_END
+}
+// postprocess (:241-250) and the paste back (:263) of every item, in place; the crop of item i is row i of bbox_dev
+int migan_pipeline_batch_post(const migan_pipeline_item* items, int n, int resolution, const void* y_nchw, const int* bbox_dev,
+                              const float* gauss25, void* scratch, void* stream) {
+  MIGAN_API_BEGIN
+  using namespace migan;
+  migan_pipeline_batch_check(resolution, bbox_dev, scratch);
+  MIGAN_CHECK(y_nchw, MIGAN_EINVAL, "null tensor");
+  std::vector<PipeBatchItem> its;
+  migan_pipeline_batch_plan(items, n, true, scratch, &its);
+  PipeBatchArgs a{};
+  a.y = (const float*)y_nchw; a.bbox = const_cast<int*>(bbox_dev); a.R = resolution;
+  migan_pipeline_gauss(gauss25, a.gauss);
+  // the crop is on the device: the grid covers each item's whole image, the workgroups past the crop's tiles leave at once
+  migan_pipeline_batch_run(pipe_post_batch_kernel, "migan::pipe_post_batch_kernel", a, its,
+                           [](const PipeBatchItem& it) { return (unsigned long long)cdiv(it.W, kPostTW) * (unsigned long long)cdiv(it.H, kPostTH); },
+                           (size_t)kPostLdsBytes, stream);
+  MIGAN_API_END
+}
 
 #ifdef MIGAN_PHASE_PROF
 // debug builds only: cumulative cycles of thread 0 per phase [prologue, S1, S2, MFMA, acc->LDS, epilogue, -, -, #workgroups]

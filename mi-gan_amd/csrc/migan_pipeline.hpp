@@ -9,7 +9,15 @@
 //   F.interpolate(mode="nearest"): src = min(floor(dst * scale), in - 1)
 //   torchvision's tensor resize rounds a uint8 image back with torch.round (half to even) -> rintf
 // Compiled for the product and (tests/emu) for the CPU emulator.
+//
+// Two forms: one image per call with the box on the host (PipeArgs; migan_pipeline_bbox / _pre / _post), and a batch of up to
+// kPipeBatchMax images of different sizes per launch with the box kept on the device (PipeBatchArgs; migan_pipeline_batch_pre /
+// _post): 1-D grids, workgroup -> (item, tile) through the prefix table in the argument, no host synchronisation in between.
 #pragma once
+
+#ifndef MIGAN_HOST_DEVICE          // (the CPU emulator build is host code throughout)
+#define MIGAN_HOST_DEVICE
+#endif
 
 namespace migan {
 
@@ -24,6 +32,27 @@ struct PipeArgs {
   int x_min, x_max, y_min, y_max;
   float gauss[25];             // GaussianSmoothing(kernel_size=5, sigma=1) weights, row major (:63-85)
 };
+
+// get_masked_bbox (:149-229) from the first / last masked column and row (x_min = W, x_max = 0, y_min = H, y_max = 0 when nothing is
+// masked: min over [..., w], max over [..., 0]): a dozen integer min/max in the reference's own order.  The ONE statement of it: the
+// host calls it in migan_pipeline_bbox, thread 0 of pipe_bbox_batch_kernel on the device.  box = {x_min, x_max, y_min, y_max}
+MIGAN_HOST_DEVICE inline void pipe_box(int x_min, int x_max, int y_min, int y_max, int width, int height, int resolution, int padding,
+                                       int box[4]) {
+  auto lo = [](int a, int b) { return a < b ? a : b; };
+  auto hi = [](int a, int b) { return a > b ? a : b; };
+  x_min = lo(x_min, x_max); x_max = hi(x_min, x_max);                              // :154-172
+  y_min = lo(y_min, y_max); y_max = hi(y_min, y_max);
+  const int cnt_x = (x_min + x_max) / 2, cnt_y = (y_min + y_max) / 2;              // :174-175
+  int crop = hi(x_max - x_min, y_max - y_min) + 2 * padding;                       // :177-180
+  crop = hi(crop, resolution);                                                     // :181-184
+  const int off = crop / 2;                                                        // :186
+  x_min = hi(cnt_x - off, 0); x_max = lo(cnt_x + off, width);                      // :187-202
+  y_min = hi(cnt_y - off, 0); y_max = lo(cnt_y + off, height);
+  const int xe = hi(crop - (x_max - x_min), 0), ye = hi(crop - (y_max - y_min), 0);   // :204-211
+  x_min = hi(x_min - xe, 0); x_max = lo(x_max + xe, width);                        // :213-229
+  y_min = hi(y_min - ye, 0); y_max = lo(y_max + ye, height);
+  box[0] = x_min; box[1] = x_max; box[2] = y_min; box[3] = y_max;
+}
 
 MIGAN_DEVICE MIGAN_INLINE void bilinear_coord(int dst, float scale, int in, int& i0, int& i1, float& l0, float& l1) {
   float src = scale * ((float)dst + 0.5f) - 0.5f;
@@ -57,25 +86,25 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_flags_kernel(const PipeArgs p
 }
 
 // MIGAN_Pipeline.forward's first line (:256): tvF.resize(mask, image size, NEAREST) = F.interpolate(mode="nearest").
-// args: mask = source [y_max][x_max] (its height / width ride in y_max / x_max), pooled = destination [H][W]
-MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_mask_resize_kernel(const PipeArgs p) {
-  const int i = (int)(blockIdx.x * kThreads + threadIdx.x);
-  if (i >= p.H * p.W) return;
-  const int oy = i / p.W, ox = i % p.W, ih = p.y_max, iw = p.x_max;
-  int sy = (int)floorf((float)oy * ((float)ih / (float)p.H)), sx = (int)floorf((float)ox * ((float)iw / (float)p.W));
+// pixel i of dst [H][W] from src [ih][iw]
+MIGAN_DEVICE MIGAN_INLINE void pipe_mask_resize_pixel(const unsigned char* src, int ih, int iw, unsigned char* dst, int H, int W, int i) {
+  if (i >= H * W) return;
+  const int oy = i / W, ox = i % W;
+  int sy = (int)floorf((float)oy * ((float)ih / (float)H)), sx = (int)floorf((float)ox * ((float)iw / (float)W));
   sy = sy < ih - 1 ? sy : ih - 1;
   sx = sx < iw - 1 ? sx : iw - 1;
-  p.pooled[i] = p.mask[(size_t)sy * iw + sx];
+  dst[i] = src[(size_t)sy * iw + sx];
 }
 
 // preprocess (:233-239) of the crop [y_min, y_max) x [x_min, x_max): bilinear resize of the uint8 image (rounded back to uint8 as
-// torchvision does), nearest resize of the mask, x = cat([mask / 255 - 0.5, (image * 2 / 255 - 1) * mask / 255])
-MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_pre_kernel(const PipeArgs p) {
-  const int i = (int)(blockIdx.x * kThreads + threadIdx.x);
-  if (i >= p.R * p.R) return;
-  const int oy = i / p.R, ox = i % p.R;
-  const int ch = p.y_max - p.y_min, cw = p.x_max - p.x_min;
-  const float sy = (float)ch / (float)p.R, sx = (float)cw / (float)p.R;
+// torchvision does), nearest resize of the mask, x = cat([mask / 255 - 0.5, (image * 2 / 255 - 1) * mask / 255]).  Element i of each
+// plane of x [4][R][R]
+MIGAN_DEVICE MIGAN_INLINE void pipe_pre_pixel(const unsigned char* image, const unsigned char* mask, float* x, int H, int W, int R,
+                                              int x_min, int x_max, int y_min, int y_max, int i) {
+  if (i >= R * R) return;
+  const int oy = i / R, ox = i % R;
+  const int ch = y_max - y_min, cw = x_max - x_min;
+  const float sy = (float)ch / (float)R, sx = (float)cw / (float)R;
   int y0, y1, x0, x1;
   float l0y, l1y, l0x, l1x;
   bilinear_coord(oy, sy, ch, y0, y1, l0y, l1y);
@@ -83,19 +112,60 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_pre_kernel(const PipeArgs p) 
   int ny = (int)floorf((float)oy * sy), nx = (int)floorf((float)ox * sx);
   ny = ny < ch - 1 ? ny : ch - 1;
   nx = nx < cw - 1 ? nx : cw - 1;
-  const float m = (float)p.mask[(size_t)(p.y_min + ny) * p.W + p.x_min + nx] / 255.0f;
-  const size_t plane = (size_t)p.H * p.W, oplane = (size_t)p.R * p.R;
-  p.x[i] = m - 0.5f;
+  const float m = (float)mask[(size_t)(y_min + ny) * W + x_min + nx] / 255.0f;
+  const size_t plane = (size_t)H * W, oplane = (size_t)R * R;
+  x[i] = m - 0.5f;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const unsigned char* q = p.image + c * plane;
-    const float p00 = (float)q[(size_t)(p.y_min + y0) * p.W + p.x_min + x0], p01 = (float)q[(size_t)(p.y_min + y0) * p.W + p.x_min + x1];
-    const float p10 = (float)q[(size_t)(p.y_min + y1) * p.W + p.x_min + x0], p11 = (float)q[(size_t)(p.y_min + y1) * p.W + p.x_min + x1];
+    const unsigned char* q = image + c * plane;
+    const float p00 = (float)q[(size_t)(y_min + y0) * W + x_min + x0], p01 = (float)q[(size_t)(y_min + y0) * W + x_min + x1];
+    const float p10 = (float)q[(size_t)(y_min + y1) * W + x_min + x0], p11 = (float)q[(size_t)(y_min + y1) * W + x_min + x1];
     float v = rintf(bilinear_mix(p00, p01, p10, p11, l0x, l1x, l0y, l1y));          // torch.round, then .to(uint8)
     v = (float)(unsigned char)(int)v;
     v = MIGAN_FSUB_RN(MIGAN_FMUL_RN(v, 2.0f) / 255.0f, 1.0f);                        // image.float() * 2 / 255 - 1
-    p.x[(c + 1) * oplane + i] = MIGAN_FMUL_RN(v, m);
+    x[(c + 1) * oplane + i] = MIGAN_FMUL_RN(v, m);
   }
+}
+
+// F.pad(mode='reflect') (:114) of coordinate v into [0, n)
+MIGAN_DEVICE MIGAN_INLINE int pipe_reflect(int v, int n) { return v < 0 ? -v : (v >= n ? 2 * n - 2 - v : v); }
+
+// postprocess (:241-250) + the paste back (:263) of crop pixel (py, px), given acc = the 5x5 gaussian of the max-pooled mask there
+// (the 25 products summed in fp64, see pipe_post_kernel): generator output -> [0, 255], bilinear resize to the crop,
+// composed = image * mask + output * (1 - mask), clamp, truncate to uint8
+MIGAN_DEVICE MIGAN_INLINE void pipe_post_pixel(unsigned char* image, const float* y, int H, int W, int R, int x_min, int y_min, int cw,
+                                               int ch, int py, int px, double acc) {
+  const float mk = (float)acc / 255.0f;
+  // generator output resized to the crop
+  const float sy = (float)R / (float)ch, sx = (float)R / (float)cw;
+  int y0, y1, x0, x1;
+  float l0y, l1y, l0x, l1x;
+  bilinear_coord(py, sy, R, y0, y1, l0y, l1y);
+  bilinear_coord(px, sx, R, x0, x1, l0x, l1x);
+  const size_t plane = (size_t)H * W, oplane = (size_t)R * R;
+  const size_t at = (size_t)(y_min + py) * W + x_min + px;
+  auto to255 = [](float v) {
+    float t = MIGAN_FMUL_RN(MIGAN_FADD_RN(MIGAN_FMUL_RN(v, 0.5f), 0.5f), 255.0f);    // ((y * 0.5 + 0.5) * 255)
+    return fminf(fmaxf(t, 0.0f), 255.0f);
+  };
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float* q = y + c * oplane;
+    const float o = bilinear_mix(to255(q[y0 * R + x0]), to255(q[y0 * R + x1]), to255(q[y1 * R + x0]), to255(q[y1 * R + x1]), l0x, l1x, l0y, l1y);
+    const float img = (float)image[c * plane + at];
+    float v = MIGAN_FADD_RN(MIGAN_FMUL_RN(img, mk), MIGAN_FMUL_RN(o, MIGAN_FSUB_RN(1.0f, mk)));
+    v = fminf(fmaxf(v, 0.0f), 255.0f);
+    image[c * plane + at] = (unsigned char)(int)v;
+  }
+}
+
+// args: mask = source [y_max][x_max] (its height / width ride in y_max / x_max), pooled = destination [H][W]
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_mask_resize_kernel(const PipeArgs p) {
+  pipe_mask_resize_pixel(p.mask, p.y_max, p.x_max, p.pooled, p.H, p.W, (int)(blockIdx.x * kThreads + threadIdx.x));
+}
+
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_pre_kernel(const PipeArgs p) {
+  pipe_pre_pixel(p.image, p.mask, p.x, p.H, p.W, p.R, p.x_min, p.x_max, p.y_min, p.y_max, (int)(blockIdx.x * kThreads + threadIdx.x));
 }
 
 // F.max_pool2d(mask, 3, stride=1, padding=1) of the cropped mask (:246): neighbours outside the crop do not count
@@ -115,8 +185,8 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_maxpool_kernel(const PipeArgs
   p.pooled[i] = (unsigned char)m;
 }
 
-// postprocess (:241-250) + the paste back (:263): generator output -> [0, 255], bilinear resize to the crop, feathered mask
-// (gaussian 5x5 on the max-pooled mask, reflect padding), composed = image * mask + output * (1 - mask), clamp, truncate to uint8
+// postprocess (:241-250) + the paste back (:263): feathered mask (gaussian 5x5 on the max-pooled mask, reflect padding), then
+// pipe_post_pixel
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_post_kernel(const PipeArgs p) {
   const int i = (int)(blockIdx.x * kThreads + threadIdx.x);
   const int ch = p.y_max - p.y_min, cw = p.x_max - p.x_min;
@@ -127,36 +197,179 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_post_kernel(const PipeArgs p)
   // reference's host); a plain fp32 running sum gives 254.99998 there and the truncation below would darken every known pixel by 1.
   double acc = 0.0;
   for (int ky = 0; ky < 5; ++ky) {
-    int yy = py + ky - 2;
-    yy = yy < 0 ? -yy : (yy >= ch ? 2 * ch - 2 - yy : yy);                          // F.pad(mode='reflect') (:114)
+    const int yy = pipe_reflect(py + ky - 2, ch);
     for (int kx = 0; kx < 5; ++kx) {
-      int xx = px + kx - 2;
-      xx = xx < 0 ? -xx : (xx >= cw ? 2 * cw - 2 - xx : xx);
+      const int xx = pipe_reflect(px + kx - 2, cw);
       acc += (double)p.gauss[ky * 5 + kx] * (double)p.pooled[yy * cw + xx];
     }
   }
-  const float mk = (float)acc / 255.0f;
-  // generator output resized to the crop
-  const float sy = (float)p.R / (float)ch, sx = (float)p.R / (float)cw;
-  int y0, y1, x0, x1;
-  float l0y, l1y, l0x, l1x;
-  bilinear_coord(py, sy, p.R, y0, y1, l0y, l1y);
-  bilinear_coord(px, sx, p.R, x0, x1, l0x, l1x);
-  const size_t plane = (size_t)p.H * p.W, oplane = (size_t)p.R * p.R;
-  const size_t at = (size_t)(p.y_min + py) * p.W + p.x_min + px;
-  auto to255 = [](float v) {
-    float t = MIGAN_FMUL_RN(MIGAN_FADD_RN(MIGAN_FMUL_RN(v, 0.5f), 0.5f), 255.0f);    // ((y * 0.5 + 0.5) * 255)
-    return fminf(fmaxf(t, 0.0f), 255.0f);
-  };
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float* q = p.y + c * oplane;
-    const float o = bilinear_mix(to255(q[y0 * p.R + x0]), to255(q[y0 * p.R + x1]), to255(q[y1 * p.R + x0]), to255(q[y1 * p.R + x1]), l0x, l1x, l0y, l1y);
-    const float img = (float)p.image[c * plane + at];
-    float v = MIGAN_FADD_RN(MIGAN_FMUL_RN(img, mk), MIGAN_FMUL_RN(o, MIGAN_FSUB_RN(1.0f, mk)));
-    v = fminf(fmaxf(v, 0.0f), 255.0f);
-    p.image[c * plane + at] = (unsigned char)(int)v;
+  pipe_post_pixel(p.image, p.y, p.H, p.W, p.R, p.x_min, p.y_min, cw, ch, py, px, acc);
+}
+
+// ---- the batch form: up to kPipeBatchMax images of different sizes per launch, box on the device ---------------------------------------
+// The item table travels BY VALUE in the kernel argument (48 bytes per item: about 1.8 KB of the 4 KB a launch may carry), so a
+// batch costs no table upload and no allocation.  Grids are 1-D: workgroup b works on item i with first[i] <= b < first[i + 1], as
+// tile b - first[i] of it; the host fills `first` per launch (each kernel has its own tile size).  No atomics, no host round trip.
+constexpr int kPipeBatchMax = 32;
+struct PipeBatchItem {
+  unsigned char* image;              // [3][H][W] uint8, post: read and written in place
+  const unsigned char* mask_src;     // the caller's mask [mh][mw]
+  unsigned char* mask_resized;       // its nearest resize to [H][W] in scratch, or null when (mh, mw) == (H, W)
+  int* flags;                        // [W] column flags then [H] row flags (scratch)
+  int H, W, mh, mw;
+};
+struct PipeBatchArgs {
+  PipeBatchItem item[kPipeBatchMax];
+  int first[kPipeBatchMax + 1];
+  float* x;                          // pre: network input [n][4][R][R]
+  const float* y;                    // post: network output [n][3][R][R]
+  int* bbox;                         // [n][4] = {x_min, x_max, y_min, y_max} per item: written by pipe_bbox_batch_kernel, read by pre / post
+  int n, R, padding;
+  float gauss[25];
+};
+static_assert(sizeof(PipeBatchArgs) <= 2048, "the batch argument must stay well under the 4 KB kernel-argument limit");
+
+// wave-uniform: a handful of scalar compares on the argument
+MIGAN_DEVICE MIGAN_INLINE int pipe_batch_item(const PipeBatchArgs& p, int b) {
+  int i = 0;
+  while (i + 1 < p.n && b >= p.first[i + 1]) ++i;
+  return i;
+}
+MIGAN_DEVICE MIGAN_INLINE const unsigned char* pipe_batch_mask(const PipeBatchItem& it) {
+  return it.mask_resized ? it.mask_resized : it.mask_src;
+}
+
+// tiles of kThreads pixels of the items whose mask has another size than their image (the others have no tile)
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_mask_resize_batch_kernel(const PipeBatchArgs p) {
+  const int k = pipe_batch_item(p, (int)blockIdx.x);
+  const PipeBatchItem& it = p.item[k];
+  pipe_mask_resize_pixel(it.mask_src, it.mh, it.mw, it.mask_resized, it.H, it.W, ((int)blockIdx.x - p.first[k]) * kThreads + (int)threadIdx.x);
+}
+
+// tiles of kThreads of the H + W flags of each item
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_flags_clear_batch_kernel(const PipeBatchArgs p) {
+  const int k = pipe_batch_item(p, (int)blockIdx.x);
+  const PipeBatchItem& it = p.item[k];
+  const int i = ((int)blockIdx.x - p.first[k]) * kThreads + (int)threadIdx.x;
+  if (i < it.H + it.W) it.flags[i] = 0;
+}
+// tiles of kThreads pixels of each item's mask
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_flags_batch_kernel(const PipeBatchArgs p) {
+  const int k = pipe_batch_item(p, (int)blockIdx.x);
+  const PipeBatchItem& it = p.item[k];
+  const int i = ((int)blockIdx.x - p.first[k]) * kThreads + (int)threadIdx.x;
+  if (i >= it.H * it.W) return;
+  if (pipe_batch_mask(it)[i] != 255) {
+    it.flags[i % it.W] = 1;                // (every writer stores the same value)
+    it.flags[it.W + i / it.W] = 1;
   }
+}
+
+// get_masked_bbox (:149-229), one workgroup per item: first / last flagged column and row per thread, min / max tree through LDS
+// (4 * kThreads ints of dynamic LDS), then thread 0 runs pipe_box and writes the item's row of bbox
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_bbox_batch_kernel(const PipeBatchArgs p) {
+  MIGAN_DYN_SMEM(smem);
+  int* red = reinterpret_cast<int*>(smem);                     // [x_min | x_max | y_min | y_max][kThreads]
+  const PipeBatchItem& it = p.item[blockIdx.x];
+  const int t = (int)threadIdx.x;
+  int x_min = it.W, x_max = 0, y_min = it.H, y_max = 0;        // :149-152 (min over [..., w], max over [..., 0])
+  for (int x = t; x < it.W; x += kThreads)
+    if (it.flags[x]) { x_min = x < x_min ? x : x_min; x_max = x > x_max ? x : x_max; }
+  for (int y = t; y < it.H; y += kThreads)
+    if (it.flags[it.W + y]) { y_min = y < y_min ? y : y_min; y_max = y > y_max ? y : y_max; }
+  red[t] = x_min; red[kThreads + t] = x_max; red[2 * kThreads + t] = y_min; red[3 * kThreads + t] = y_max;
+  __syncthreads();
+  for (int s = kThreads / 2; s > 0; s >>= 1) {
+    if (t < s) {
+      int *a = red + t, *b = red + t + s;
+      a[0] = b[0] < a[0] ? b[0] : a[0];
+      a[kThreads] = b[kThreads] > a[kThreads] ? b[kThreads] : a[kThreads];
+      a[2 * kThreads] = b[2 * kThreads] < a[2 * kThreads] ? b[2 * kThreads] : a[2 * kThreads];
+      a[3 * kThreads] = b[3 * kThreads] > a[3 * kThreads] ? b[3 * kThreads] : a[3 * kThreads];
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    int box[4];
+    pipe_box(red[0], red[kThreads], red[2 * kThreads], red[3 * kThreads], it.W, it.H, p.R, p.padding, box);
+    int* out = p.bbox + 4 * blockIdx.x;
+    out[0] = box[0]; out[1] = box[1]; out[2] = box[2]; out[3] = box[3];
+  }
+}
+
+// a box that pipe_pre_pixel / the post kernel may index with: inside the image and at least 3x3 (reflect padding of the 5x5 blur)
+MIGAN_DEVICE MIGAN_INLINE bool pipe_box_valid(const int* box, int H, int W) {
+  return box[0] >= 0 && box[1] <= W && box[2] >= 0 && box[3] <= H && box[1] - box[0] >= 3 && box[3] - box[2] >= 3;
+}
+
+// cdiv(R * R, kThreads) tiles per item (first[i] = i * that), box read from device memory
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_pre_batch_kernel(const PipeBatchArgs p) {
+  const int k = pipe_batch_item(p, (int)blockIdx.x);
+  const PipeBatchItem& it = p.item[k];
+  const int* box = p.bbox + 4 * k;
+  if (!pipe_box_valid(box, it.H, it.W)) return;
+  pipe_pre_pixel(it.image, pipe_batch_mask(it), p.x + (size_t)k * 4 * p.R * p.R, it.H, it.W, p.R, box[0], box[1], box[2], box[3],
+                 ((int)blockIdx.x - p.first[k]) * kThreads + (int)threadIdx.x);
+}
+
+// pipe_maxpool_kernel + pipe_post_kernel in one pass, the pooled mask in LDS instead of scratch.  A workgroup owns a
+// kPostTW x kPostTH tile of crop pixels, one per thread (a wave = two rows of 32: coalesced rows in global memory; in LDS each half
+// wave reads 32 consecutive bytes = 8 dwords of one row, rows 9 dwords apart -> no bank conflict):
+//   1. mask window of the tile + 3 pixels of halo -> LDS, 0 outside the crop (max-pool neighbours outside the crop do not count)
+//   2. 3x3 max of it = the pooled mask of the tile + 2 pixels of halo -> LDS.  Entries outside the crop are never read: the blur
+//      reflects at the crop border, and a reflected coordinate lies within 2 of the coordinate it came from's tile
+//   3. 5x5 blur from LDS (same fp64 sum, same ky, kx order as pipe_post_kernel), then pipe_post_pixel
+// The crop is not known on the host: the grid has cdiv(W, TW) * cdiv(H, TH) workgroups per item, at least as many as the crop
+// has tiles; tile t is (t / ntx, t % ntx) of the CROP's ntx = cdiv(cw, TW) columns, and the surplus workgroups leave at once.
+constexpr int kPostTW = 32, kPostTH = 8;
+constexpr int kPostWW = kPostTW + 6, kPostWH = kPostTH + 6, kPostPW = kPostTW + 4, kPostPH = kPostTH + 4;
+constexpr int kPostWinBytes = (kPostWW * kPostWH + 15) / 16 * 16;
+constexpr int kPostLdsBytes = kPostWinBytes + (kPostPW * kPostPH + 15) / 16 * 16;
+static_assert(kPostTW * kPostTH == kThreads, "one thread per tile pixel");
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_post_batch_kernel(const PipeBatchArgs p) {
+  MIGAN_DYN_SMEM(smem);
+  unsigned char* win = reinterpret_cast<unsigned char*>(smem);       // [kPostWH][kPostWW]: crop rows ty0 - 3 ..., columns tx0 - 3 ...
+  unsigned char* pool = win + kPostWinBytes;                         // [kPostPH][kPostPW]: crop rows ty0 - 2 ..., columns tx0 - 2 ...
+  const int k = pipe_batch_item(p, (int)blockIdx.x);
+  const PipeBatchItem& it = p.item[k];
+  const int* box = p.bbox + 4 * k;
+  // the box came through device memory: one that does not fit the image is not touched (and nothing of the image is)
+  if (!pipe_box_valid(box, it.H, it.W)) return;
+  const int x_min = box[0], y_min = box[2], cw = box[1] - box[0], ch = box[3] - box[2];
+  const int tile = (int)blockIdx.x - p.first[k], ntx = (cw + kPostTW - 1) / kPostTW;
+  const int ty0 = tile / ntx * kPostTH, tx0 = tile % ntx * kPostTW;
+  if (ty0 >= ch) return;                                             // (workgroup-uniform, like the returns above)
+  const unsigned char* mask = pipe_batch_mask(it);
+  const int t = (int)threadIdx.x;
+  for (int e = t; e < kPostWH * kPostWW; e += kThreads) {
+    const int cy = ty0 - 3 + e / kPostWW, cx = tx0 - 3 + e % kPostWW;
+    win[e] = (cy >= 0 && cy < ch && cx >= 0 && cx < cw) ? mask[(size_t)(y_min + cy) * it.W + x_min + cx] : (unsigned char)0;
+  }
+  __syncthreads();
+  for (int e = t; e < kPostPH * kPostPW; e += kThreads) {
+    const unsigned char* w0 = win + e / kPostPW * kPostWW + e % kPostPW;
+    int m = 0;
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 3; ++dx) {
+        const int v = w0[dy * kPostWW + dx];
+        m = v > m ? v : m;
+      }
+    pool[e] = (unsigned char)m;
+  }
+  __syncthreads();
+  const int py = ty0 + t / kPostTW, px = tx0 + t % kPostTW;
+  if (py >= ch || px >= cw) return;
+  double acc = 0.0;
+  for (int ky = 0; ky < 5; ++ky) {
+    const int yy = pipe_reflect(py + ky - 2, ch) - (ty0 - 2);
+    for (int kx = 0; kx < 5; ++kx) {
+      const int xx = pipe_reflect(px + kx - 2, cw) - (tx0 - 2);
+      acc += (double)p.gauss[ky * 5 + kx] * (double)pool[yy * kPostPW + xx];
+    }
+  }
+  pipe_post_pixel(it.image, p.y + (size_t)k * 3 * p.R * p.R, it.H, it.W, p.R, x_min, y_min, cw, ch, py, px, acc);
 }
 #endif  // MIGAN_TEMPLATE_KERNELS_ONLY
 

@@ -6,6 +6,7 @@
 #include <string>
 
 #define MIGAN_DEVICE __device__
+#define MIGAN_HOST_DEVICE __host__ __device__      // one statement of a piece of integer arithmetic for the host plan and a kernel
 #define MIGAN_INLINE __forceinline__
 #define MIGAN_GLOBAL __global__
 #define MIGAN_LAUNCH_BOUNDS(threads, waves_per_simd) __launch_bounds__(threads, waves_per_simd)

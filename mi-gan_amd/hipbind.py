@@ -68,6 +68,7 @@ EXPORTS = (
     "migan_forward_timed", "migan_set_debug", "migan_debug_tensor", "migan_sepconv_forward",
     "migan_pack_input", "migan_compose_output",
     "migan_pipeline_mask_resize", "migan_pipeline_scratch_bytes", "migan_pipeline_bbox", "migan_pipeline_pre", "migan_pipeline_post",
+    "migan_pipeline_batch_scratch_bytes", "migan_pipeline_batch_pre", "migan_pipeline_batch_post",
     "migan_forward_split", "migan_forward_parts", "migan_set_tuning", "migan_get_tuning", "migan_tuning_key", "migan_last_error", "migan_last_kernel", "migan_nan_policy", "migan_backend", "migan_gemm_variant", "migan_version",
     # include/comodgan_hip.h
     "comodgan_create", "comodgan_destroy", "comodgan_num_weights", "comodgan_weight_info", "comodgan_set_weight",
@@ -75,6 +76,21 @@ EXPORTS = (
     "comodgan_num_launches",
     "comodgan_launch_info", "comodgan_forward_timed", "comodgan_set_debug", "comodgan_debug_tensor", "comodgan_set_truncation_cutoff",
 )
+
+
+class PipelineItem(C.Structure):
+    """struct migan_pipeline_item"""
+    _fields_ = [("image_chw_u8", C.c_void_p), ("mask_u8", C.c_void_p)] + [
+        (n, C.c_int) for n in ("height", "width", "mask_height", "mask_width")]
+
+
+def pipeline_items(items):
+    """[(image_ptr, mask_ptr, height, width, mask_height, mask_width), ...] -> a migan_pipeline_item array"""
+    arr = (PipelineItem * len(items))()
+    for a, (img, msk, h, w, mh, mw) in zip(arr, items):
+        a.image_chw_u8, a.mask_u8 = img or None, msk or None
+        a.height, a.width, a.mask_height, a.mask_width = int(h), int(w), int(mh), int(mw)
+    return arr
 
 
 class CoModGANConfig(C.Structure):
@@ -141,6 +157,9 @@ class MiganLib:
         L.migan_pipeline_bbox.argtypes = [vp, ci, ci, ci, ci, vp, C.POINTER(ci), vp]
         L.migan_pipeline_pre.argtypes = [vp, vp, ci, ci, C.POINTER(ci), ci, vp, vp]
         L.migan_pipeline_post.argtypes = [vp, vp, ci, ci, C.POINTER(ci), ci, vp, C.POINTER(C.c_float), vp, vp]
+        L.migan_pipeline_batch_scratch_bytes.argtypes = [C.POINTER(PipelineItem), ci, C.POINTER(C.c_size_t)]
+        L.migan_pipeline_batch_pre.argtypes = [C.POINTER(PipelineItem), ci, ci, ci, vp, vp, vp, vp]
+        L.migan_pipeline_batch_post.argtypes = [C.POINTER(PipelineItem), ci, ci, vp, vp, C.POINTER(C.c_float), vp, vp]
         L.migan_num_weights.argtypes = [vp, C.POINTER(ci)]
         L.migan_weight_info.argtypes = [vp, ci, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(ci), C.POINTER(ci)]
         L.migan_set_weight.argtypes = [vp, C.c_char_p, vp, C.POINTER(C.c_int64), ci]
@@ -270,6 +289,21 @@ class MiganLib:
         g = None if gauss25 is None else (C.c_float * 25)(*[float(v) for v in gauss25])
         self.check(self.lib.migan_pipeline_post(C.c_void_p(image_ptr), C.c_void_p(mask_ptr), int(height), int(width), box, int(resolution),
                                                 C.c_void_p(y_ptr), g, C.c_void_p(scratch_ptr), C.c_void_p(stream)))
+
+    # the batch form: `items` = [(image_ptr, mask_ptr, height, width, mask_height, mask_width), ...]; the boxes stay on the device
+    def pipeline_batch_scratch_bytes(self, items) -> int:
+        n = C.c_size_t()
+        self.check(self.lib.migan_pipeline_batch_scratch_bytes(pipeline_items(items), len(items), C.byref(n)))
+        return int(n.value)
+
+    def pipeline_batch_pre(self, items, resolution: int, padding: int, x_ptr: int, bbox_ptr: int, scratch_ptr: int, stream: int = 0) -> None:
+        self.check(self.lib.migan_pipeline_batch_pre(pipeline_items(items), len(items), int(resolution), int(padding), C.c_void_p(x_ptr),
+                                                     C.c_void_p(bbox_ptr), C.c_void_p(scratch_ptr), C.c_void_p(stream)))
+
+    def pipeline_batch_post(self, items, resolution: int, y_ptr: int, bbox_ptr: int, scratch_ptr: int, gauss25=None, stream: int = 0) -> None:
+        g = None if gauss25 is None else (C.c_float * 25)(*[float(v) for v in gauss25])
+        self.check(self.lib.migan_pipeline_batch_post(pipeline_items(items), len(items), int(resolution), C.c_void_p(y_ptr),
+                                                      C.c_void_p(bbox_ptr), g, C.c_void_p(scratch_ptr), C.c_void_p(stream)))
 
     def sepconv_forward(self, stream: int = 0, **kw) -> None:
         d = SepConvDesc()

@@ -53,7 +53,10 @@ class MIGAN_Pipeline(torch.nn.Module):
       image (1, 3, H, W) uint8, mask (1, 1, H, W) uint8 (255 = known pixel); the image is modified in place and returned.
 
     ``model_path`` is a reference ``migan_*.pt`` state dict, or an already built ``mi-gan_amd`` Generator.  A mask of another size is
-    resized to the image's size first (nearest), like the reference's first line (:256).  No CPU path."""
+    resized to the image's size first (nearest), like the reference's first line (:256).  No CPU path.
+
+    ``forward_batch(images, masks)`` is the same for N images of different sizes around ONE generator forward per ``max_batch``
+    images, with the boxes kept on the device (``migan_pipeline_batch_pre / _post``): no host synchronisation in between."""
 
     def __init__(self, model_path, resolution: int, padding: int = 128, device="cuda"):
         super().__init__()
@@ -76,7 +79,9 @@ class MIGAN_Pipeline(torch.nn.Module):
 
     def _scratch_for(self, lib, h: int, w: int, device) -> torch.Tensor:
         """scratch of the bbox / post kernels, one buffer per (device, stream): two streams running the pipeline never share it"""
-        need = lib.pipeline_scratch_bytes(h, w)
+        return self._scratch_bytes(lib.pipeline_scratch_bytes(h, w), device)
+
+    def _scratch_bytes(self, need: int, device) -> torch.Tensor:
         key = (device.index if device.index is not None else torch.cuda.current_device(), int(torch.cuda.current_stream(device).cuda_stream))
         if self._scratch is None:
             self._scratch = {}
@@ -138,3 +143,54 @@ class MIGAN_Pipeline(torch.nn.Module):
         lib.pipeline_post(image.data_ptr(), mask.data_ptr(), h, w, bbox, self.res, y.data_ptr(), scratch.data_ptr(),
                           gauss25=self._gauss, stream=stream)
         return image
+
+    @torch.no_grad()
+    def forward_batch(self, images, masks, *, max_batch: int = 32, return_bbox: bool = False):
+        """``forward`` for N images of different sizes: images[i] (1, 3, H_i, W_i) or (3, H_i, W_i) uint8, contiguous, masks[i]
+        (1, 1, h_i, w_i) or (h_i, w_i) uint8, all on one device.  Per chunk of at most ``max_batch`` images: masks resized where
+        needed -> boxes (on the device) -> x [n, 4, R, R] -> ONE ``self.model(x)`` -> blend, with no host synchronisation in
+        between.  The images are modified in place and returned as a list; with ``return_bbox`` also the int32 [N, 4] device tensor
+        of {x_min, x_max, y_min, y_max} rows.  Each image gets what ``forward`` gives it, up to the fp32 rounding by which the
+        generator at batch n differs from batch 1.  Two entries that share memory are undefined."""
+        images, masks = list(images), list(masks)
+        if len(images) != len(masks) or not images:
+            raise RuntimeError(f"expected as many masks as images and at least one, got {len(images)} images and {len(masks)} masks")
+        if int(max_batch) < 1:
+            raise RuntimeError(f"max_batch must be at least 1, got {max_batch}")
+        items, device = [], None
+        for image, mask in zip(images, masks):
+            if not (image.is_cuda and mask.is_cuda):
+                raise RuntimeError("mi-gan_amd.pipeline needs tensors on an MI355X (HIP) device; there is no CPU path")
+            if image.dtype != torch.uint8 or mask.dtype != torch.uint8:
+                raise RuntimeError("image and mask must be uint8 (reference create_onnx_pipeline.py:254-255)")
+            if not ((image.dim() == 4 and image.shape[0] == 1 and image.shape[1] == 3) or (image.dim() == 3 and image.shape[0] == 3)) \
+                    or not image.is_contiguous():
+                raise RuntimeError(f"expected a contiguous image (1, 3, H, W), got {list(image.shape)}")
+            if not ((mask.dim() == 4 and mask.shape[0] == 1 and mask.shape[1] == 1) or mask.dim() == 2):
+                raise RuntimeError(f"expected mask (1, 1, h, w), got {list(mask.shape)}")
+            device = image.device if device is None else device
+            if mask.device != device or image.device != device:
+                raise RuntimeError("image and mask must be on the same device")
+            mask = mask.contiguous()
+            items.append((image.data_ptr(), mask.data_ptr(), int(image.shape[-2]), int(image.shape[-1]), int(mask.shape[-2]),
+                          int(mask.shape[-1]), mask))                # (the contiguous mask stays alive until the kernels are queued)
+        lib = load_library()
+        bbox = torch.empty((len(items), 4), dtype=torch.int32, device=device)
+        with torch.cuda.device(device):                          # the handle-free entry points launch on the CURRENT device
+            stream = int(torch.cuda.current_stream(device).cuda_stream)
+            for i0 in range(0, len(items), int(max_batch)):
+                chunk = [it[:6] for it in items[i0:i0 + int(max_batch)]]
+                scratch = self._scratch_bytes(lib.pipeline_batch_scratch_bytes(chunk), device)
+                box = bbox[i0:i0 + len(chunk)]
+                # A last chunk of ONE image of a longer list runs the generator at batch 2 (its x twice): an image of a batch of two
+                # or more is bit-identical whatever the batch (INTEGRATION.md section 6), a batch-1 forward only to fp32 rounding --
+                # so the result of forward_batch does not depend on max_batch (max_batch=1 asks for batch 1 and gets it)
+                pad = 1 if len(chunk) == 1 and len(items) > 1 and int(max_batch) > 1 else 0
+                x = torch.empty((len(chunk) + pad, 4, self.res, self.res), dtype=torch.float32, device=device)
+                lib.pipeline_batch_pre(chunk, self.res, self.padding, x.data_ptr(), box.data_ptr(), scratch.data_ptr(), stream)
+                if pad:
+                    x[1].copy_(x[0])
+                y = self.model(x).contiguous()
+                lib.pipeline_batch_post(chunk, self.res, y.data_ptr(), box.data_ptr(), scratch.data_ptr(), gauss25=self._gauss,
+                                        stream=stream)
+        return (images, bbox) if return_bbox else images
