@@ -195,8 +195,8 @@ class Generator(nn.Module):
             self._dirty = False
         return self._handle
 
-    def _workspace(self, h: CoModGANHandle, batch: int, device: torch.device) -> torch.Tensor:
-        need = h.workspace_bytes(batch)
+    def _workspace(self, h: CoModGANHandle, batch: int, device: torch.device, samples: int = 1) -> torch.Tensor:
+        need = h.workspace_bytes(batch) if samples == 1 else h.workspace_bytes_samples(batch, samples)
         if self._ws is None or self._ws.device != device or self._ws.numel() < need:
             self._ws = None
             self._refreeze = True            # a new allocation holds no prepared weight planes (even at a recycled address)
@@ -245,6 +245,55 @@ class Generator(nn.Module):
         y = torch.empty((n, 3, r, r), dtype=torch.float32, device=x.device)
         ms = h.forward(x.data_ptr(), z.data_ptr(), y.data_ptr(), n, ws.data_ptr(), ws.numel(), float(truncation_psi), noise_mode,
                        None if noise is None else noise.data_ptr(), self._stream(x), timed=_timed)
+        return (y, ms) if _timed else y
+
+    def forward_samples(self, x: torch.Tensor, z: Optional[torch.Tensor] = None, samples: Optional[int] = None, truncation_psi: float = 1,
+                        truncation_cutoff=None, noise_mode: str = "random", _timed: bool = False):
+        """Several completions per image from one encoder pass (no reference equivalent).  x: [N,4,R,R]; z: [N,S,z_dim], or None with
+        ``samples=S`` (drawn with torch.randn) -> [N,S,3,R,R].  ``forward_samples(x, z)[i, s]`` is what
+        ``forward(x.repeat_interleave(S, 0), z.reshape(N * S, -1))[i * S + s]`` gives with the same options, but the encoder, which never
+        sees z, runs once per image; the mapping network, the styles and the synthesis network run once per sample."""
+        assert noise_mode in ["random", "const", "none"]         # stylegan.py:280
+        if truncation_cutoff is not None and (int(truncation_cutoff) != truncation_cutoff or truncation_cutoff < 0):
+            raise ValueError(f"truncation_cutoff must be a non-negative integer or None, got {truncation_cutoff!r}")
+        r = self.img_resolution
+        if x.dim() != 4 or x.shape[1] != 4 or x.shape[2] != r or x.shape[3] != r:
+            raise RuntimeError(f"expected input of shape [N, 4, {r}, {r}] (mask-0.5, img*mask), got {list(x.shape)}")
+        if x.dtype != torch.float32:
+            raise RuntimeError(f"Input type ({x.dtype}) and weight type (torch.float32) should be the same")
+        n = x.shape[0]
+        if n == 0:
+            raise RuntimeError("empty batch")
+        if samples is not None and (int(samples) != samples or samples < 1):
+            raise ValueError(f"samples must be a positive integer or None, got {samples!r}")
+        if z is None:
+            if samples is None:
+                raise ValueError("forward_samples needs z of shape [N, S, z_dim], or samples=S to draw it")
+        else:
+            if z.dim() != 3 or z.shape[0] != n or z.shape[1] < 1 or z.shape[2] != self.z_dim:
+                raise RuntimeError(f"expected z of shape [{n}, S, {self.z_dim}] (S latents per image), got {list(z.shape)}")
+            if samples is not None and int(samples) != z.shape[1]:
+                raise ValueError(f"samples={samples} contradicts z of shape {list(z.shape)}")
+        s = int(samples) if z is None else int(z.shape[1])
+        h = self._engine(x)
+        x = x.contiguous()
+        if z is None:
+            z = torch.randn([n, s, self.z_dim]).to(x.device)
+        z = z.to(device=x.device, dtype=torch.float32).contiguous()
+        noise = None
+        if noise_mode == "random":
+            noise = torch.randn(n * s * h.noise_floats(), dtype=torch.float32, device=x.device)    # one draw per sample and layer
+        cutoff = None if truncation_cutoff is None else int(truncation_cutoff)
+        if cutoff != self._cutoff:                               # (part of the workspace layout: set before sizing it)
+            h.set_truncation_cutoff(cutoff)
+            self._cutoff = cutoff
+        ws = self._workspace(h, n, x.device, s)
+        if self._refreeze:                                       # as in forward(): the prepared weight planes do not depend on S
+            h.assume_static_weights(self._frozen)
+            self._refreeze = False
+        y = torch.empty((n, s, 3, r, r), dtype=torch.float32, device=x.device)
+        ms = h.forward_samples(x.data_ptr(), z.data_ptr(), y.data_ptr(), n, s, ws.data_ptr(), ws.numel(), float(truncation_psi), noise_mode,
+                               None if noise is None else noise.data_ptr(), self._stream(x), timed=_timed)
         return (y, ms) if _timed else y
 
     def forward_timed(self, x: torch.Tensor, z: torch.Tensor, noise_mode: str = "const"):

@@ -6,6 +6,7 @@
 #pragma once
 
 #include "../../include/comodgan_hip.h"
+#include "../../include/comodgan_samples_hip.h"
 
 namespace migan {
 
@@ -203,7 +204,10 @@ struct CmPlanKey {
   int batch = 0, trunc_cutoff = -1;  // batch 0: nothing planned
   bool debug = false;
   CmForced forced;
-  bool operator==(const CmPlanKey& o) const { return batch == o.batch && debug == o.debug && trunc_cutoff == o.trunc_cutoff && forced == o.forced; }
+  int samples = 1;                   // completions per image (comodgan_forward_samples); batch counts images
+  bool operator==(const CmPlanKey& o) const {
+    return batch == o.batch && samples == o.samples && debug == o.debug && trunc_cutoff == o.trunc_cutoff && forced == o.forced;
+  }
 };
 
 }  // namespace migan
@@ -238,9 +242,10 @@ struct comodgan_handle {
     for (int res = 8; res <= cfg.resolution; res *= 2) n += 2 * (size_t)res * res;
     return n;
   }
-  // Workspace bytes of a forward at this batch.  Sizes the network again unless the cached plan was made for the same batch, debug
-  // flag, truncation cutoff and forced kernel forms: infos / debug_tensors / events can never belong to another launch sequence.
-  size_t ensure_planned(int batch) const;
+  // Workspace bytes of a forward at this batch (images) and sample count.  Sizes the network again unless the cached plan was made
+  // for the same batch, samples, debug flag, truncation cutoff and forced kernel forms: infos / debug_tensors / events can never
+  // belong to another launch sequence.
+  size_t ensure_planned(int batch, int samples = 1) const;
 };
 
 // Mirror of mi-gan_amd/comodgan_schema.py::entries (the state_dict's registration order) and, from the same loops, the network as
@@ -322,7 +327,12 @@ struct CmNoise { const float* plane = nullptr; long long bstride = 0; };   // a 
 struct CmWalk {
   comodgan_handle& h;
   const CmNet& net;
-  const int B;
+  // An S-samples forward (comodgan_forward_samples) runs what depends on x only -- the encoder and the fc at the head of
+  // synthesis.b4 -- at batch N, and the mapping network, the affine / style launches and the synthesis network at batch
+  // B = N * S (image-major: sample s of image i is row i * S + s).  nb is the batch of the section being walked: conv(), dense(),
+  // act_out() and emit() take it from there.  The reported figures of a launch are per input image: x nb / N.
+  const int N, S, B;
+  int nb;
   const CmForced forced;
   const bool sizing;
   // a launching walk's tensors and options (a sizing walk's size and launch list depend on none of them)
@@ -345,8 +355,8 @@ struct CmWalk {
   float *bufA = nullptr, *bufB = nullptr, *tmp = nullptr, *img[2] = {}, *feat[16] = {};
   float *wlat = nullptr, *wraw = nullptr, *w0 = nullptr;
 
-  CmWalk(comodgan_handle& handle, int batch, const CmForced& f, bool size_only)
-      : h(handle), net(handle.net), B(batch), forced(f), sizing(size_only) {}
+  CmWalk(comodgan_handle& handle, int batch, int samples, const CmForced& f, bool size_only)
+      : h(handle), net(handle.net), N(batch), S(samples), B(batch * samples), nb(batch), forced(f), sizing(size_only) {}
 
   float* alloc(size_t bytes) {
     const size_t off = cursor;
@@ -366,15 +376,16 @@ struct CmWalk {
     h.debug_tensors.push_back(t);
   }
   float* act_out(const char* name, float* pingpong, int res, int c) {
-    float* p = h.debug ? alloc((size_t)res * res * c * B * 4) : pingpong;
-    reg_debug(name, "", p, {B, res, res, c});
+    float* p = h.debug ? alloc((size_t)res * res * c * nb * 4) : pingpong;
+    reg_debug(name, "", p, {nb, res, res, c});
     return p;
   }
   template <class Kernel, class Args>
   void emit(const char* layer, const char* suffix, const char* kname, double flops, double mfma, double bytes, Kernel kernel, const Args& args,
             unsigned grid, size_t lds) {
     if (sizing) {
-      h.infos.push_back(CmInfo{std::string(layer) + suffix, kname, flops, mfma, bytes});
+      const double per_image = (double)nb / N;          // 1, or S for what runs once per sample
+      h.infos.push_back(CmInfo{std::string(layer) + suffix, kname, flops * per_image, mfma * per_image, bytes * per_image});
     } else {
       if (timed) rt_check(rt::event_record(h.events[2 * nlaunch], stream), "hipEventRecord");
       if (!skip_launch) rt_check(rt::launch(kernel, args, grid, kThreads, lds, cur_stream), kname);
@@ -405,11 +416,11 @@ struct CmWalk {
       p.wn2 = mod ? alloc((size_t)c.co * 4) : nullptr;
       CmWprepArgs q{};
       q.w = weight(c.w); q.amax = p.amax; q.wsq = p.wsq; q.wn2 = p.wn2; q.CO = c.co; q.CI = c.ci;
-      emit(c.name.c_str(), ".wprep", "migan::cm_wprep_kernel", 0, 0, 4.0 * c.co * c.ci * (mod ? 10 : 9) / B, cm_wprep_kernel, q, (unsigned)c.co,
+      emit(c.name.c_str(), ".wprep", "migan::cm_wprep_kernel", 0, 0, 4.0 * c.co * c.ci * (mod ? 10 : 9) / nb, cm_wprep_kernel, q, (unsigned)c.co,
            8 * sizeof(float));
       CmSplitArgs a{};
       a.src = q.w; a.amax = p.amax; a.dst = p.planes; a.CO = c.co; a.CI = c.ci;
-      emit(c.name.c_str(), ".split", "migan::cm_split_conv_kernel", 0, 0, 8.0 * c.co * c.ci * 9 / B, cm_split_conv_kernel, a,
+      emit(c.name.c_str(), ".split", "migan::cm_split_conv_kernel", 0, 0, 8.0 * c.co * c.ci * 9 / nb, cm_split_conv_kernel, a,
            grid1d((size_t)c.co * c.ci), 4 * sizeof(float));
     }
     skip_launch = false;
@@ -429,15 +440,15 @@ struct CmWalk {
     a.x = xin; a.w = weight(L.w); a.b = weight(L.b);
     a.add = add; a.lerp0 = lerp0; a.y = out; a.y_raw = lerp0 ? out_raw : nullptr;
     a.wgain = lr_multi / std::sqrt((float)K); a.bgain = lr_multi; a.psi = psi;
-    a.N = B; a.K = K; a.K1 = K; a.O = O; a.act = true; a.norm = norm; a.in_c = in_c; a.out_c = out_c;
-    emit(L.name.c_str(), "", "migan::cm_dense_kernel", 2.0 * K * O, 0, 4.0 * ((double)K * O / B + K + O), cm_dense_kernel, a, (unsigned)cdiv(O, 8), 0);
+    a.N = nb; a.K = K; a.K1 = K; a.O = O; a.act = true; a.norm = norm; a.in_c = in_c; a.out_c = out_c;
+    emit(L.name.c_str(), "", "migan::cm_dense_kernel", 2.0 * K * O, 0, 4.0 * ((double)K * O / nb + K + O), cm_dense_kernel, a, (unsigned)cdiv(O, 8), 0);
   }
   // 3x3 convolution net.convs[index] from xin ([H][Wd]) to out ([HO][WO]).  raw: a transposed-convolution launch, cm_fir_kernel<1> finishes the layer
   // (bias, noise, activation).  A modulated layer takes its input scales and demodulation coefficients from its style job.
   void conv(int index, const char* suffix, int mode, int phase, const float* xin, float* out, int H, int Wd, int HO, int WO,
             const CmNoise& nz = CmNoise{}, bool raw = false) {
     const CmConvL& L = net.convs[index];
-    CmConvGeo g = cm_conv_geometry(mode, phase, H, Wd, HO, WO, L.ci, L.co, B, forced);
+    CmConvGeo g = cm_conv_geometry(mode, phase, H, Wd, HO, WO, L.ci, L.co, nb, forced);
     CmConvArgs& a = g.a;
     a.x = xin; a.y = out; a.wsplit = conv_ws[index].planes;
     if (L.job >= 0) { a.sa = job_ws[L.job].sa; a.coef = job_ws[L.job].coef; }
@@ -466,16 +477,19 @@ struct CmWalk {
       max_act = std::max(max_act, (size_t)res * res * h.channels(res));
       max_tmp = std::max(max_tmp, (size_t)(res + 1) * (res + 1) * h.channels(res));
     }
+    // the ping-pong buffers serve the encoder (batch N) and the synthesis network (batch B >= N): sized for the larger tenant;
+    // the skip tensors feat[] are the encoder's, at batch N
     bufA = h.debug ? nullptr : alloc(max_act * B * 4);
     bufB = h.debug ? nullptr : alloc(max_act * B * 4);
     tmp = alloc(max_tmp * B * 4);
     for (float*& im : img) im = h.debug ? nullptr : alloc((size_t)3 * R * R * B * 4);
-    for (int res = R; res >= 4; res /= 2) feat[ilog2(res)] = alloc((size_t)res * res * h.channels(res) * B * 4);
+    for (int res = R; res >= 4; res /= 2) feat[ilog2(res)] = alloc((size_t)res * res * h.channels(res) * N * 4);
   }
 
   // ---------------------------------------------------------------- mapping (stylegan.py:396-439)
   void mapping() {
     const comodgan_config& cfg = h.cfg;
+    nb = B;
     float* m0 = alloc((size_t)B * cfg.w_dim * 4);
     float* m1 = alloc((size_t)B * cfg.w_dim * 4);
     wlat = alloc((size_t)B * cfg.w_dim * 4);
@@ -516,39 +530,41 @@ struct CmWalk {
   // ---------------------------------------------------------------- encoder (comodgan.py:192-204)
   void encoder() {
     const int R = h.cfg.resolution, c0 = h.channels(R), c4 = h.channels(4);
-    w0 = alloc((size_t)B * h.cfg.w0_dim * 4);
-    float* cur = h.debug ? alloc((size_t)R * R * c0 * B * 4) : bufA;
+    nb = N;
+    w0 = alloc((size_t)N * h.cfg.w0_dim * 4);
+    float* cur = h.debug ? alloc((size_t)R * R * c0 * N * 4) : bufA;
     CmFromRgbArgs a{};
-    a.x = x; a.w = weight(net.fromrgb.w); a.b = weight(net.fromrgb.b); a.y = cur; a.wgain = 0.5f; a.B = B; a.R = R; a.C = c0;
+    a.x = x; a.w = weight(net.fromrgb.w); a.b = weight(net.fromrgb.b); a.y = cur; a.wgain = 0.5f; a.B = N; a.R = R; a.C = c0;
     emit(net.fromrgb.name.c_str(), "", "migan::cm_fromrgb_kernel", 2.0 * 4 * c0 * R * R, 0, 4.0 * (4 + c0) * R * R, cm_fromrgb_kernel, a,
-         grid1d((size_t)B * R * R * (c0 / 4) / 8), 0);      // 8 pixels per thread: the weights are read once per thread
+         grid1d((size_t)N * R * R * (c0 / 4) / 8), 0);      // 8 pixels per thread: the weights are read once per thread
     for (const CmEncBlock& blk : net.enc) {
       const CmConvL& conv0 = net.convs[blk.conv0];
       const CmConvL& conv1 = net.convs[blk.conv1];
       const int res = blk.res, c = conv0.co;
       float* f = feat[ilog2(res)];
-      reg_debug(conv0.name.c_str(), "", f, {B, res, res, c});
+      reg_debug(conv0.name.c_str(), "", f, {N, res, res, c});
       conv(blk.conv0, "", CM_CONV_NORMAL, 0, cur, f, res, res, res, res);
       CmFirArgs a{};
-      a.x = f; a.y = tmp; a.B = B; a.H = res; a.W = res; a.C = c; a.HO = res + 1; a.WO = res + 1; a.pad = 2; a.fs = 0.125f;
+      a.x = f; a.y = tmp; a.B = N; a.H = res; a.W = res; a.C = c; a.HO = res + 1; a.WO = res + 1; a.pad = 2; a.fs = 0.125f;
       emit(conv1.name.c_str(), ".fir", "migan::cm_fir_kernel<0>", 2.0 * 16 * c * (res + 1) * (res + 1), 0, 4.0 * c * (2.0 * res * res + 2 * res + 1),
-           cm_fir_kernel<0>, a, grid1d((size_t)B * cdiv(res + 1, 2) * cdiv(res + 1, 4) * (c / 4)), 0);
+           cm_fir_kernel<0>, a, grid1d((size_t)N * cdiv(res + 1, 2) * cdiv(res + 1, 4) * (c / 4)), 0);
       float* out = act_out(conv1.name.c_str(), bufA, res / 2, conv1.co);
       conv(blk.conv1, "", CM_CONV_DOWN, 0, tmp, out, res + 1, res + 1, res / 2, res / 2);
       cur = out;
     }
     const CmConvL& b4 = net.convs[net.enc_b4];
-    reg_debug(b4.name.c_str(), "", feat[2], {B, 4, 4, c4});
+    reg_debug(b4.name.c_str(), "", feat[2], {N, 4, 4, c4});
     conv(net.enc_b4, "", CM_CONV_NORMAL, 0, cur, feat[2], 4, 4, 4, 4);
     // fc over feat.flatten(1) of the NCHW tensor (comodgan.py:106): the kernel permutes the K index to our NHWC storage
     dense(net.enc_fc, feat[2], c4 * 16, h.cfg.w0_dim, w0, 1.0f, false, c4, 0, nullptr, nullptr);
-    reg_debug(net.enc_fc.name.c_str(), "", w0, {B, h.cfg.w0_dim});
+    reg_debug(net.enc_fc.name.c_str(), "", w0, {N, h.cfg.w0_dim});
   }
 
   // ---------------------------------------------------------------- affine + style jobs, ahead of the synthesis blocks
   void styles() {
     const int wl = h.cfg.w_dim + h.cfg.w0_dim;
     const bool cut = psi != 1.0f && h.trunc_cutoff >= 0;
+    nb = B;
     job_ws.assign(net.jobs.size(), JobWs{});
     // every affine layer (styles = affine(cat([w, w0])), stylegan.py:282,337) in one launch
     CmDenseMultiArgs a{};
@@ -564,7 +580,14 @@ struct CmWalk {
     a.blk0[a.njobs] = ablk;
     a.x = wlat; a.x_alt = wraw; a.x2 = w0; a.wgain = 1.0f / std::sqrt((float)wl); a.N = B; a.K = wl; a.K1 = h.cfg.w_dim;
     if (side) rt_check(rt::stream_wait_event(stream, h.ev_map), "hipStreamWaitEvent");     // w from the mapping stream
-    emit("synthesis.affine", "", "migan::cm_dense_multi_kernel", afl, 0, 2.0 * afl / B, cm_dense_multi_kernel, a, (unsigned)ablk, 0);
+    // x / x_alt (the latents) are per sample, x2 = w0 per image: with S > 1 the launch that maps row b to image b / S
+    if (S == 1) {
+      emit("synthesis.affine", "", "migan::cm_dense_multi_kernel", afl, 0, 2.0 * afl / B, cm_dense_multi_kernel, a, (unsigned)ablk, 0);
+    } else {
+      CmDenseMultiSamplesArgs as{};
+      as.m = a; as.S = S;
+      emit("synthesis.affine", "", "migan::cm_dense_multi_samples_kernel", afl, 0, 2.0 * afl / B, cm_dense_multi_samples_kernel, as, (unsigned)ablk, 0);
+    }
     // every style computation (input scales + demodulation coefficients of the modulated convs, modulated ToRGB weights) in one
     // launch: inputs are the affine outputs above and the per-tensor weight statistics
     CmStyleMultiArgs sm{};
@@ -610,8 +633,19 @@ struct CmWalk {
     static const char* const kPhase[4] = {".phase0", ".phase1", ".phase2", ".phase3"};
     const int R = h.cfg.resolution, c4 = h.channels(4);
     // b4 (comodgan.py:232-257): x = fc(w0).view(N, C, 4, 4) + feat[4]; conv; torgb
+    // x4 depends on the image only: the fc runs at batch N; with S > 1 into a buffer of its own, from which cm_bcast_kernel writes the
+    // per-sample tensor the convolution reads (its input addressing stays as it is)
     float* x4 = act_out(net.syn_fc.name.c_str(), bufA, 4, c4);
-    dense(net.syn_fc, w0, h.cfg.w0_dim, c4 * 16, x4, 1.0f, false, 0, c4, feat[2], nullptr);
+    float* x4n = S == 1 ? x4 : alloc((size_t)16 * c4 * N * 4);
+    nb = N;
+    dense(net.syn_fc, w0, h.cfg.w0_dim, c4 * 16, x4n, 1.0f, false, 0, c4, feat[2], nullptr);
+    nb = B;
+    if (S != 1) {
+      CmBcastArgs bc{};
+      bc.x = x4n; bc.y = x4; bc.N = N; bc.S = S; bc.M = 16 * c4;
+      emit(net.syn_fc.name.c_str(), ".samples", "migan::cm_bcast_kernel", 0, 0, 4.0 * 16 * c4 * (1.0 + 1.0 / S), cm_bcast_kernel, bc,
+           grid1d((size_t)B * 4 * c4), 0);
+    }
     const CmConvL& b4 = net.convs[net.syn_b4];
     const CmNoise nz4 = noise_of(b4);
     float* xcur = act_out(b4.name.c_str(), bufB, 4, c4);
@@ -636,8 +670,18 @@ struct CmWalk {
       a.x = tmp; a.y = x0; a.skip = feat[ilog2(res)]; a.bias = weight(conv0.b); a.noise = nz0.plane;
       a.noise_strength = weight(conv0.noise_strength); a.noise_bstride = nz0.bstride;
       a.B = B; a.H = res + 1; a.W = res + 1; a.C = co; a.HO = res; a.WO = res; a.pad = 1; a.fs = 0.25f;
-      emit(conv0.name.c_str(), ".fir", "migan::cm_fir_kernel<1>", 2.0 * 16 * co * res * res, 0, 4.0 * co * ((res + 1.0) * (res + 1.0) + 2.0 * res * res),
-           cm_fir_kernel<1>, a, grid1d((size_t)B * (res / 2) * cdiv(res, 4) * (co / 4)), 0);
+      const double fir_fl = 2.0 * 16 * co * res * res;
+      const unsigned fir_grid = grid1d((size_t)B * (res / 2) * cdiv(res, 4) * (co / 4));
+      if (S == 1) {
+        emit(conv0.name.c_str(), ".fir", "migan::cm_fir_kernel<1>", fir_fl, 0, 4.0 * co * ((res + 1.0) * (res + 1.0) + 2.0 * res * res),
+             cm_fir_kernel<1>, a, fir_grid, 0);
+      } else {
+        // the skip tensor is the encoder's, [N]: sample b reads image b / S (the S reads of a skip pixel counted once)
+        CmFirSamplesArgs as{};
+        as.f = a; as.S = S;
+        emit(conv0.name.c_str(), ".fir", "migan::cm_fir_samples_kernel", fir_fl, 0,
+             4.0 * co * ((res + 1.0) * (res + 1.0) + (1.0 + 1.0 / S) * res * res), cm_fir_samples_kernel, as, fir_grid, 0);
+      }
       const CmNoise nz1 = noise_of(conv1);
       float* x1 = act_out(conv1.name.c_str(), bufB, res, co);
       conv(blk.conv1, "", CM_CONV_NORMAL, 0, x0, x1, res, res, res, res, nz1);
@@ -670,12 +714,12 @@ struct CmWalk {
 
 }  // namespace migan
 
-inline size_t comodgan_handle::ensure_planned(int batch) const {
-  const migan::CmPlanKey key{batch, trunc_cutoff, debug, migan::cm_read_forced()};
+inline size_t comodgan_handle::ensure_planned(int batch, int samples) const {
+  const migan::CmPlanKey key{batch, trunc_cutoff, debug, migan::cm_read_forced(), samples};
   if (!(key == planned)) {
     comodgan_handle* m = const_cast<comodgan_handle*>(this);      // the queries of the C ABI take a const handle; the plan is a cache
     m->planned = migan::CmPlanKey{};                              // (nothing planned if the walk throws)
-    m->planned_need = migan::CmWalk(*m, batch, key.forced, true).run(nullptr, nullptr);
+    m->planned_need = migan::CmWalk(*m, batch, samples, key.forced, true).run(nullptr, nullptr);
     m->planned = key;
   }
   return planned_need;
@@ -792,19 +836,26 @@ int comodgan_noise_floats(const comodgan_handle* h, size_t* floats_per_image) {
   MIGAN_API_END
 }
 
-static int comodgan_forward_impl(comodgan_handle* h, const void* x, const void* z, void* y, int batch, float psi, int noise_mode,
+// samples >= 1 and batch * samples fits an int, or MIGAN_EINVAL naming the argument
+static void comodgan_check_samples(int batch, int samples) {
+  MIGAN_CHECK(samples >= 1, MIGAN_EINVAL, "samples must be >= 1");
+  MIGAN_CHECK((long long)batch * samples <= (long long)INT_MAX, MIGAN_EINVAL, "batch * samples does not fit an int");
+}
+
+static int comodgan_forward_impl(comodgan_handle* h, const void* x, const void* z, void* y, int batch, int samples, float psi, int noise_mode,
                                  const void* noise, void* ws, size_t ws_bytes, void* stream, float* ms, int n_ms) {
   MIGAN_API_BEGIN
   using namespace migan;
   MIGAN_CHECK(h, MIGAN_EINVAL, "null handle");
   MIGAN_CHECK(h->committed, MIGAN_ESTATE, "comodgan_forward before comodgan_commit");
   MIGAN_CHECK(x && z && y && batch > 0, MIGAN_EINVAL, "null tensor or empty batch");
+  comodgan_check_samples(batch, samples);
   MIGAN_CHECK(noise_mode == COMODGAN_NOISE_NONE || noise_mode == COMODGAN_NOISE_CONST || noise_mode == COMODGAN_NOISE_RANDOM, MIGAN_EINVAL,
               "noise_mode must be none, const or random");
   MIGAN_CHECK(noise_mode != COMODGAN_NOISE_RANDOM || noise != nullptr, MIGAN_EINVAL, "noise_mode random needs the noise tensor");
   MIGAN_CHECK(ws != nullptr && ((uintptr_t)ws % 256) == 0, MIGAN_EINVAL, "null or misaligned workspace (256 bytes)");
   MIGAN_CHECK(((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0 && ((uintptr_t)z % 4) == 0, MIGAN_EINVAL, "misaligned tensor");
-  const size_t need = h->ensure_planned(batch);
+  const size_t need = h->ensure_planned(batch, samples);
   MIGAN_CHECK(ws_bytes >= need, MIGAN_EINVAL, "workspace too small for this batch");
   if (ms) {
     MIGAN_CHECK(n_ms >= (int)h->infos.size(), MIGAN_EINVAL, "launch_ms array too small");
@@ -815,7 +866,7 @@ static int comodgan_forward_impl(comodgan_handle* h, const void* x, const void* 
     }
   }
   DeviceGuard guard(h->device);
-  CmWalk walk(*h, batch, h->planned.forced, false);      // the forced forms the plan was just checked against
+  CmWalk walk(*h, batch, samples, h->planned.forced, false);      // the forced forms the plan was just checked against
   walk.x = (const float*)x; walk.z = (const float*)z; walk.y = (float*)y; walk.noise = (const float*)noise;
   walk.psi = psi; walk.noise_mode = noise_mode; walk.stream = (rt::stream_t)stream;
   walk.run(ws, ms);
@@ -824,7 +875,29 @@ static int comodgan_forward_impl(comodgan_handle* h, const void* x, const void* 
 
 int comodgan_forward(comodgan_handle* h, const void* x, const void* z, void* y, int batch, float psi, int noise_mode, const void* noise,
                      void* ws, size_t ws_bytes, void* stream) {
-  return comodgan_forward_impl(h, x, z, y, batch, psi, noise_mode, noise, ws, ws_bytes, stream, nullptr, 0);
+  return comodgan_forward_impl(h, x, z, y, batch, 1, psi, noise_mode, noise, ws, ws_bytes, stream, nullptr, 0);
+}
+
+int comodgan_forward_samples(comodgan_handle* h, const void* x, const void* z, void* y, int batch, int samples, float psi, int noise_mode,
+                             const void* noise, void* ws, size_t ws_bytes, void* stream) {
+  return comodgan_forward_impl(h, x, z, y, batch, samples, psi, noise_mode, noise, ws, ws_bytes, stream, nullptr, 0);
+}
+
+int comodgan_forward_samples_timed(comodgan_handle* h, const void* x, const void* z, void* y, int batch, int samples, float psi, int noise_mode,
+                                   const void* noise, void* ws, size_t ws_bytes, void* stream, float* launch_ms, int n_launch_ms) {
+  if (!launch_ms) {
+    migan::last_error_ref() = "null launch_ms";
+    return MIGAN_EINVAL;
+  }
+  return comodgan_forward_impl(h, x, z, y, batch, samples, psi, noise_mode, noise, ws, ws_bytes, stream, launch_ms, n_launch_ms);
+}
+
+int comodgan_workspace_bytes_samples(const comodgan_handle* h, int batch, int samples, size_t* bytes) {
+  MIGAN_API_BEGIN
+  MIGAN_CHECK(h && bytes && batch > 0, MIGAN_EINVAL, "bad argument");
+  comodgan_check_samples(batch, samples);
+  *bytes = h->ensure_planned(batch, samples);
+  MIGAN_API_END
 }
 
 int comodgan_forward_timed(comodgan_handle* h, const void* x, const void* z, void* y, int batch, float psi, int noise_mode, const void* noise,
@@ -833,13 +906,13 @@ int comodgan_forward_timed(comodgan_handle* h, const void* x, const void* z, voi
     migan::last_error_ref() = "null launch_ms";
     return MIGAN_EINVAL;
   }
-  return comodgan_forward_impl(h, x, z, y, batch, psi, noise_mode, noise, ws, ws_bytes, stream, launch_ms, n_launch_ms);
+  return comodgan_forward_impl(h, x, z, y, batch, 1, psi, noise_mode, noise, ws, ws_bytes, stream, launch_ms, n_launch_ms);
 }
 
 int comodgan_num_launches(const comodgan_handle* h, int* n) {
   MIGAN_API_BEGIN
   MIGAN_CHECK(h && n, MIGAN_EINVAL, "null argument");
-  h->ensure_planned(std::max(h->planned.batch, 1));      // the launches of the last planned batch, in the forms forced now
+  h->ensure_planned(std::max(h->planned.batch, 1), h->planned.samples);      // the launches of the plan made last, in the forms forced now
   *n = (int)h->infos.size();
   MIGAN_API_END
 }
@@ -848,7 +921,7 @@ int comodgan_launch_info(const comodgan_handle* h, int index, const char** layer
                          double* bytes) {
   MIGAN_API_BEGIN
   MIGAN_CHECK(h, MIGAN_EINVAL, "null handle");
-  h->ensure_planned(std::max(h->planned.batch, 1));
+  h->ensure_planned(std::max(h->planned.batch, 1), h->planned.samples);
   MIGAN_CHECK(index >= 0 && index < (int)h->infos.size(), MIGAN_EINVAL, "launch index out of range");
   const migan::CmInfo& L = h->infos[index];
   if (layer) *layer = L.layer.c_str();
@@ -875,10 +948,16 @@ int comodgan_set_debug(comodgan_handle* h, int keep) {
 }
 
 int comodgan_debug_tensor(const comodgan_handle* h, int batch, const char* layer, size_t* byte_offset, int64_t shape[4], int* ndim) {
+  return comodgan_debug_tensor_samples(h, batch, 1, layer, byte_offset, shape, ndim);
+}
+
+int comodgan_debug_tensor_samples(const comodgan_handle* h, int batch, int samples, const char* layer, size_t* byte_offset, int64_t shape[4],
+                                  int* ndim) {
   MIGAN_API_BEGIN
-  MIGAN_CHECK(h && layer && byte_offset && shape && ndim, MIGAN_EINVAL, "null argument");
+  MIGAN_CHECK(h && layer && byte_offset && shape && ndim && batch > 0, MIGAN_EINVAL, "null argument or empty batch");
   MIGAN_CHECK(h->debug, MIGAN_ESTATE, "comodgan_set_debug(h, 1) first");
-  h->ensure_planned(batch);
+  comodgan_check_samples(batch, samples);
+  h->ensure_planned(batch, samples);
   for (const auto& t : h->debug_tensors) {
     if (t.name != layer) continue;
     *byte_offset = t.offset;

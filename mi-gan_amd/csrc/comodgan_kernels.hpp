@@ -24,6 +24,8 @@
 //                       wave per SIMD, 128x128 wave tiles, accumulators in AGPRs), chosen per launch by the host.
 //   cm_fir_kernel<0>    upfirdn2d [1,3,3,1] FIR with pad 2 in front of the strided convolution (conv2d_resample down path)
 //   cm_fir_kernel<1>    upfirdn2d FIR (gain 4) behind the transposed convolution + noise/bias/activation/skip epilogue
+//   cm_fir_samples_kernel, cm_dense_multi_samples_kernel, cm_bcast_kernel   the three places of an S-samples forward
+//                       (comodgan_forward_samples) where a per-sample launch reads a per-image operand: sample b -> image b / S
 //   cm_fromrgb_kernel   1x1 conv 4 -> C with bias and activation, NCHW planes -> NHWC
 //   cm_torgb_kernel     modulated 1x1 conv C -> 3 (no demodulation) + bias + 2x FIR upsample of the running image
 //   cm_dense_kernel     fully connected layers (mapping, affine, encoder fc, synthesis fc): weight streaming, fp32 FMA
@@ -646,7 +648,9 @@ struct CmDenseArgs {
   int N, K, K1, O;
   int act, norm, in_c, out_c;
 };
-MIGAN_DEVICE MIGAN_INLINE void cm_dense_block(const CmDenseArgs& p, int block) {
+// SAMP (the affine launch of an S-samples forward): x is per sample, x2 per image -- row n of x2 is n / S.
+template <bool SAMP = false>
+MIGAN_DEVICE MIGAN_INLINE void cm_dense_block(const CmDenseArgs& p, int block, int S = 1) {
   constexpr int RP = 8;                      // batch rows per pass over the weights (16 spills)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int o0 = (block * 4 + wave) * 2;
@@ -690,7 +694,7 @@ MIGAN_DEVICE MIGAN_INLINE void cm_dense_block(const CmDenseArgs& p, int block) {
         for (int r = 0; r < RP; ++r) {
           const int n = n0 + r;
           float xv = 0.0f;
-          if (n < p.N) xv = (k < p.K1) ? p.x[(size_t)n * p.K1 + k] : p.x2[(size_t)n * K2 + (k - p.K1)];
+          if (n < p.N) xv = (k < p.K1) ? p.x[(size_t)n * p.K1 + k] : p.x2[(size_t)(SAMP ? n / S : n) * K2 + (k - p.K1)];
           acc[0][r] += xv * w0;
           acc[1][r] += xv * w1;
           nrm[r] += xv * xv;
@@ -756,6 +760,40 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_dense_multi_kernel(const CmDens
   a.x = ((p.alt_mask >> j) & 1ull) ? p.x_alt : p.x; a.x2 = p.x2; a.w = p.w[j]; a.b = p.b[j]; a.y = p.y[j];
   a.wgain = p.wgain; a.bgain = 1.0f; a.psi = 1.0f; a.N = p.N; a.K = p.K; a.K1 = p.K1; a.O = p.O[j];
   cm_dense_block(a, (int)blockIdx.x - p.blk0[j]);
+}
+// The same launch of an S-samples forward (comodgan_forward_samples): N = images x S rows of x / x_alt (the latents, one per
+// sample, image-major) against the global code x2 of N / S images.  A symbol of its own, so that the launch above keeps its
+// arguments and its code.
+struct CmDenseMultiSamplesArgs {
+  CmDenseMultiArgs m;
+  int S;
+};
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_dense_multi_samples_kernel(const CmDenseMultiSamplesArgs q) {
+  const CmDenseMultiArgs& p = q.m;
+  int j = 0;
+  while (j + 1 < p.njobs && (int)blockIdx.x >= p.blk0[j + 1]) ++j;
+  CmDenseArgs a{};
+  a.x = ((p.alt_mask >> j) & 1ull) ? p.x_alt : p.x; a.x2 = p.x2; a.w = p.w[j]; a.b = p.b[j]; a.y = p.y[j];
+  a.wgain = p.wgain; a.bgain = 1.0f; a.psi = 1.0f; a.N = p.N; a.K = p.K; a.K1 = p.K1; a.O = p.O[j];
+  cm_dense_block<true>(a, (int)blockIdx.x - p.blk0[j], q.S);
+}
+
+// Head of synthesis.b4 of an S-samples forward: x4 = fc(w0) + feat[4] depends on the image only and is computed at batch N;
+// this copies it to the [N * S][4][4][C] tensor cm_conv_kernel reads (image-major: rows i * S ... i * S + S - 1 = image i).
+// 32 KB per sample at 512 channels.
+struct CmBcastArgs {
+  const float* x;      // [N][M]
+  float* y;            // [N * S][M]
+  int N, S, M;         // M: floats per image, a multiple of 4
+};
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_bcast_kernel(const CmBcastArgs p) {
+  const int mq = p.M >> 2;
+  const size_t total = (size_t)p.N * p.S * mq;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int q = (int)(i % mq);
+    const int b = (int)(i / mq);
+    st4(p.y + (size_t)b * p.M + q * 4, ld4(p.x + (size_t)(b / p.S) * p.M + q * 4));
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -886,6 +924,93 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_fir_kernel(const CmFirArgs p) {
           v = act4(v + bias4);
           if (p.skip) v = v + sk[r][c];
         }
+        st4o(p.y + o, v);
+      }
+    }
+  }
+}
+
+// cm_fir_kernel<1> of an S-samples forward (comodgan_forward_samples): x, y and the noise are per sample ([B = N * S], image-major),
+// the skip tensor is the encoder's, per image ([N][HO][WO][C]): sample b reads the skip pixels of image b / S.  A kernel of its own,
+// so that cm_fir_kernel<1> keeps its arguments and its code; the same 2 x 4 block per thread, the skip and noise loads ahead of the
+// window loads and no load behind a store.  The flat index carries the sample right above the channel quad -- (image, block row,
+// block column, sample, quad) -- so the S samples of an image that share a 2 x 4 block of skip pixels sit in adjacent lane groups of
+// one workgroup or of two consecutive ones: the first brings the pixels in, the others find them in the vector cache or in L2 (a
+// plain load, not the read-once form of the per-image kernel).  Every other access is that kernel's, at the sample's batch index.
+struct CmFirSamplesArgs {
+  CmFirArgs f;                 // B = N * S; skip: [N]
+  int S;
+};
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_fir_samples_kernel(const CmFirSamplesArgs q) {
+  const CmFirArgs& p = q.f;
+  const int S = q.S;
+  const int qn = p.C >> 2;
+  const int nbx = (p.WO + 3) >> 2, nby = (p.HO + 1) >> 1;
+  const size_t total = (size_t)p.B * nby * nbx * qn;
+  const float f0 = p.fs, f1 = 3.0f * p.fs;
+  const float ns = p.noise ? p.noise_strength[0] : 0.0f;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int c4 = (int)(i % qn);
+    size_t blk = i / qn;
+    const int smp = (int)(blk % S); blk /= S;
+    const int bx = (int)(blk % nbx); blk /= nbx;
+    const int by = (int)(blk % nby);
+    const int bi = (int)(blk / nby);                             // image: batch index of the skip tensor
+    const int b = bi * S + smp;                                  // sample: batch index of x, y and the noise
+    const int x0 = bx * 4, y0 = by * 2;
+    const float* xb = p.x + (size_t)b * p.H * p.W * p.C + c4 * 4;
+    // the skip tensor and the noise plane of the 2 x 4 output block are requested first, so that they travel with
+    // the 35 window loads instead of after the arithmetic that needs them last
+    f4 sk[2][4];
+    float nz[2][4];
+    const f4 bias4 = ld4(p.bias + c4 * 4);                       // (read here, not between the stores below: a load behind a store waits for that store)
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int oy = y0 + r, ox = x0 + c;
+        const bool ok = oy < p.HO && ox < p.WO;
+        sk[r][c] = f4{0.f, 0.f, 0.f, 0.f};
+        nz[r][c] = 0.0f;
+        if (ok && p.skip) sk[r][c] = ld4(p.skip + (((size_t)bi * p.HO + oy) * p.WO + ox) * p.C + c4 * 4);
+        if (ok && p.noise) nz[r][c] = p.noise[(size_t)b * p.noise_bstride + (size_t)oy * p.WO + ox];
+      }
+    f4 acc[2][4];
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc[r][c] = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < 5; ++r) {
+      const int iy = y0 - p.pad + r;
+      const bool yok = iy >= 0 && iy < p.H;
+      f4 v[7];
+#pragma unroll
+      for (int c = 0; c < 7; ++c) {
+        const int ix = x0 - p.pad + c;
+        v[c] = f4{0.f, 0.f, 0.f, 0.f};
+        if (yok && ix >= 0 && ix < p.W) v[c] = ld4(xb + ((size_t)iy * p.W + ix) * p.C);
+      }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const f4 h = (v[c] + v[c + 3]) * f0 + (v[c + 1] + v[c + 2]) * f1;
+        if (r < 4) acc[0][c] = acc[0][c] + h * ((r == 0 || r == 3) ? f0 : f1);
+        if (r > 0) acc[1][c] = acc[1][c] + h * ((r == 1 || r == 4) ? f0 : f1);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int oy = y0 + r;
+      if (oy >= p.HO) continue;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int ox = x0 + c;
+        if (ox >= p.WO) continue;
+        const size_t o = (((size_t)b * p.HO + oy) * p.WO + ox) * p.C + c4 * 4;
+        f4 v = acc[r][c];
+        if (p.noise) v = v + MIGAN_FMUL_RN(nz[r][c], ns);
+        v = act4(v + bias4);
+        if (p.skip) v = v + sk[r][c];
         st4o(p.y + o, v);
       }
     }

@@ -76,6 +76,9 @@ EXPORTS = (
     "comodgan_num_launches",
     "comodgan_launch_info", "comodgan_forward_timed", "comodgan_set_debug", "comodgan_debug_tensor", "comodgan_set_truncation_cutoff",
 )
+# include/comodgan_samples_hip.h
+SAMPLES_EXPORTS = ("comodgan_workspace_bytes_samples", "comodgan_forward_samples", "comodgan_forward_samples_timed",
+                   "comodgan_debug_tensor_samples")
 
 
 class PipelineItem(C.Structure):
@@ -137,7 +140,7 @@ class MiganLib:
         except OSError as e:  # pragma: no cover - depends on the machine
             raise MiganError(f"cannot load {self.path}: {e}") from e
         L = self.lib
-        for name in EXPORTS:
+        for name in EXPORTS + SAMPLES_EXPORTS:
             if not hasattr(L, name):
                 raise MiganError(f"{self.path} does not export {name}")
         vp, ci = C.c_void_p, C.c_int
@@ -196,6 +199,10 @@ class MiganLib:
         L.comodgan_set_debug.argtypes = [vp, ci]
         L.comodgan_set_truncation_cutoff.argtypes = [vp, ci]
         L.comodgan_debug_tensor.argtypes = [vp, ci, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64), C.POINTER(ci)]
+        L.comodgan_workspace_bytes_samples.argtypes = [vp, ci, ci, C.POINTER(C.c_size_t)]
+        L.comodgan_forward_samples.argtypes = [vp, vp, vp, vp, ci, ci, C.c_float, ci, vp, vp, C.c_size_t, vp]
+        L.comodgan_forward_samples_timed.argtypes = [vp, vp, vp, vp, ci, ci, C.c_float, ci, vp, vp, C.c_size_t, vp, fp, ci]
+        L.comodgan_debug_tensor_samples.argtypes = [vp, ci, ci, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64), C.POINTER(ci)]
         L.migan_last_error.restype = C.c_char_p
         L.migan_last_kernel.restype = C.c_char_p
         L.migan_nan_policy.restype = C.c_char_p
@@ -206,7 +213,7 @@ class MiganLib:
         if not allow_test_backend and L.migan_backend().decode() != PRODUCT_BACKEND:
             raise MiganError(f"{self.path} reports backend {L.migan_backend().decode()!r}, not {PRODUCT_BACKEND!r}: only the gfx950 HIP "
                              f"library is a product backend (the CPU emulator build is test infrastructure)")
-        for name in EXPORTS:
+        for name in EXPORTS + SAMPLES_EXPORTS:
             if name not in ("migan_last_error", "migan_last_kernel", "migan_nan_policy", "migan_backend", "migan_gemm_variant", "migan_tuning_key"):
                 getattr(L, name).restype = ci
 
@@ -491,6 +498,11 @@ class CoModGANHandle:
         self.lib.check(self.lib.lib.comodgan_workspace_bytes(self._h, int(batch), C.byref(n)))
         return int(n.value)
 
+    def workspace_bytes_samples(self, batch: int, samples: int) -> int:
+        n = C.c_size_t()
+        self.lib.check(self.lib.lib.comodgan_workspace_bytes_samples(self._h, int(batch), int(samples), C.byref(n)))
+        return int(n.value)
+
     def noise_floats(self) -> int:
         n = C.c_size_t()
         self.lib.check(self.lib.lib.comodgan_noise_floats(self._h, C.byref(n)))
@@ -511,6 +523,23 @@ class CoModGANHandle:
         n = len(self.launches())
         ms = (C.c_float * n)()
         self.lib.check(self.lib.lib.comodgan_forward_timed(*args, ms, n))
+        return [float(v) for v in ms]
+
+    def forward_samples(self, x_ptr: int, z_ptr: int, y_ptr: int, batch: int, samples: int, ws_ptr: int, ws_bytes: int,
+                        truncation_psi: float = 1.0, noise_mode: str = "const", noise_ptr: Optional[int] = None, stream: int = 0,
+                        timed: bool = False):
+        """x [batch,4,R,R], z [batch*samples,z_dim] -> y [batch*samples,3,R,R] (image-major): the encoder once per image"""
+        if noise_mode not in NOISE_MODES:
+            raise AssertionError(noise_mode)             # stylegan.py:280
+        args = [self._h, C.c_void_p(x_ptr), C.c_void_p(z_ptr), C.c_void_p(y_ptr), int(batch), int(samples), C.c_float(truncation_psi),
+                NOISE_MODES[noise_mode], C.c_void_p(noise_ptr), C.c_void_p(ws_ptr), C.c_size_t(ws_bytes), C.c_void_p(stream)]
+        if not timed:
+            self.lib.check(self.lib.lib.comodgan_forward_samples(*args))
+            return None
+        self.workspace_bytes_samples(batch, samples)     # launches() describes the plan made last: make it this one
+        n = len(self.launches())
+        ms = (C.c_float * n)()
+        self.lib.check(self.lib.lib.comodgan_forward_samples_timed(*args, ms, n))
         return [float(v) for v in ms]
 
     def launches(self) -> List[Dict]:
@@ -538,6 +567,14 @@ class CoModGANHandle:
         shape = (C.c_int64 * 4)()
         nd = C.c_int()
         self.lib.check(self.lib.lib.comodgan_debug_tensor(self._h, int(batch), layer.encode(), C.byref(off), shape, C.byref(nd)))
+        return int(off.value), tuple(int(shape[k]) for k in range(nd.value))
+
+    def debug_tensor_samples(self, batch: int, samples: int, layer: str) -> Tuple[int, Tuple[int, ...]]:
+        off = C.c_size_t()
+        shape = (C.c_int64 * 4)()
+        nd = C.c_int()
+        self.lib.check(self.lib.lib.comodgan_debug_tensor_samples(self._h, int(batch), int(samples), layer.encode(), C.byref(off), shape,
+                                                                  C.byref(nd)))
         return int(off.value), tuple(int(shape[k]) for k in range(nd.value))
 
 
