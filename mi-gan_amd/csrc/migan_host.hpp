@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/migan_hip.h"
+#include "../../include/migan_pipeline_samples_hip.h"
 #include "migan_table.hpp"
 
 namespace migan {
@@ -2063,6 +2064,47 @@ int migan_pipeline_batch_post(const migan_pipeline_item* items, int n, int resol
   migan_pipeline_batch_run(pipe_post_batch_kernel, "migan::pipe_post_batch_kernel", a, its,
                            [](const PipeBatchItem& it) { return (unsigned long long)cdiv(it.W, kPostTW) * (unsigned long long)cdiv(it.H, kPostTH); },
                            (size_t)kPostLdsBytes, stream);
+  MIGAN_API_END
+}
+// the same for `samples` generator outputs per item, out of place: item i and y rows i * samples ... -> outs[i] = [samples][3][H][W].
+// Its own argument (PipeSamplesArgs: the mask pointer resolved here, the destination with the item), kPipeSamplesMax items (and
+// fewer than 2^31 workgroups) per launch, one workgroup per kPostTW x kPostTH tile of each IMAGE
+int migan_pipeline_batch_post_samples(const migan_pipeline_item* items, int n, int samples, int resolution, const void* y_nchw,
+                                      const int* bbox_dev, const float* gauss25, void* scratch, void* const* outs, void* stream) {
+  MIGAN_API_BEGIN
+  using namespace migan;
+  migan_pipeline_batch_check(resolution, bbox_dev, scratch);
+  MIGAN_CHECK(y_nchw, MIGAN_EINVAL, "null tensor");
+  MIGAN_CHECK(samples >= 1, MIGAN_EINVAL, "samples must be at least 1");
+  MIGAN_CHECK(outs != nullptr, MIGAN_EINVAL, "null outs");
+  std::vector<PipeBatchItem> its;
+  migan_pipeline_batch_plan(items, n, true, scratch, &its);
+  for (int i = 0; i < n; ++i) MIGAN_CHECK(outs[i] != nullptr, MIGAN_EINVAL, "null destination of item " + std::to_string(i));
+  PipeSamplesArgs proto{};
+  proto.y = (const float*)y_nchw; proto.bbox = bbox_dev; proto.R = resolution; proto.S = samples;
+  migan_pipeline_gauss(gauss25, proto.gauss);
+  const size_t plane = (size_t)resolution * resolution;
+  for (size_t i0 = 0; i0 < its.size();) {
+    PipeSamplesArgs a = proto;
+    unsigned long long total = 0;
+    int k = 0;
+    for (; k < kPipeSamplesMax && i0 + k < its.size(); ++k) {
+      const PipeBatchItem& it = its[i0 + k];
+      const unsigned long long t = (unsigned long long)cdiv(it.W, kPostTW) * (unsigned long long)cdiv(it.H, kPostTH);
+      if (k > 0 && total + t > 0x7fffffffull) break;
+      a.item[k] = PipeSamplesItem{it.image, it.mask_resized ? it.mask_resized : it.mask_src, (unsigned char*)outs[i0 + k], it.H, it.W};
+      a.first[k] = (int)total;
+      total += t;
+    }
+    a.first[k] = (int)total;
+    a.n = k;
+    a.y += i0 * (size_t)samples * 3 * plane;
+    a.bbox += i0 * 4;
+    if (total)
+      rt_check(rt::launch(pipe_post_samples_kernel, a, (unsigned)total, kThreads, (size_t)kPostLdsBytes, (rt::stream_t)stream),
+               "migan::pipe_post_samples_kernel");
+    i0 += (size_t)k;
+  }
   MIGAN_API_END
 }
 

@@ -13,6 +13,8 @@
 // Two forms: one image per call with the box on the host (PipeArgs; migan_pipeline_bbox / _pre / _post), and a batch of up to
 // kPipeBatchMax images of different sizes per launch with the box kept on the device (PipeBatchArgs; migan_pipeline_batch_pre /
 // _post): 1-D grids, workgroup -> (item, tile) through the prefix table in the argument, no host synchronisation in between.
+// The batch form's post step also exists out of place, for S generator outputs per image (PipeSamplesArgs;
+// migan_pipeline_batch_post_samples).
 #pragma once
 
 #ifndef MIGAN_HOST_DEVICE          // (the CPU emulator build is host code throughout)
@@ -132,30 +134,49 @@ MIGAN_DEVICE MIGAN_INLINE int pipe_reflect(int v, int n) { return v < 0 ? -v : (
 
 // postprocess (:241-250) + the paste back (:263) of crop pixel (py, px), given acc = the 5x5 gaussian of the max-pooled mask there
 // (the 25 products summed in fp64, see pipe_post_kernel): generator output -> [0, 255], bilinear resize to the crop,
-// composed = image * mask + output * (1 - mask), clamp, truncate to uint8
-MIGAN_DEVICE MIGAN_INLINE void pipe_post_pixel(unsigned char* image, const float* y, int H, int W, int R, int x_min, int y_min, int cw,
-                                               int ch, int py, int px, double acc) {
-  const float mk = (float)acc / 255.0f;
+// composed = image * mask + output * (1 - mask), clamp, truncate to uint8.  In three parts, so that a kernel that writes several
+// generator outputs for one pixel (pipe_post_samples_kernel) states the same arithmetic: what depends on the pixel alone
+// (pipe_post_coord), the four taps of one channel of a generator output (pipe_post_taps), the result byte (pipe_post_byte).
+struct PipePostCoord {
+  float mk;                          // the feathered mask in [0, 1]
+  int y0, y1, x0, x1;                // bilinear taps in the generator output
+  float l0y, l1y, l0x, l1x;
+};
+MIGAN_DEVICE MIGAN_INLINE PipePostCoord pipe_post_coord(int R, int cw, int ch, int py, int px, double acc) {
+  PipePostCoord k;
+  k.mk = (float)acc / 255.0f;
   // generator output resized to the crop
   const float sy = (float)R / (float)ch, sx = (float)R / (float)cw;
-  int y0, y1, x0, x1;
-  float l0y, l1y, l0x, l1x;
-  bilinear_coord(py, sy, R, y0, y1, l0y, l1y);
-  bilinear_coord(px, sx, R, x0, x1, l0x, l1x);
-  const size_t plane = (size_t)H * W, oplane = (size_t)R * R;
-  const size_t at = (size_t)(y_min + py) * W + x_min + px;
+  bilinear_coord(py, sy, R, k.y0, k.y1, k.l0y, k.l1y);
+  bilinear_coord(px, sx, R, k.x0, k.x1, k.l0x, k.l1x);
+  return k;
+}
+// the four taps of channel plane q [R][R] of a generator output, in bilinear_mix's order
+MIGAN_DEVICE MIGAN_INLINE void pipe_post_taps(const float* q, int R, const PipePostCoord& k, float t[4]) {
+  t[0] = q[k.y0 * R + k.x0]; t[1] = q[k.y0 * R + k.x1]; t[2] = q[k.y1 * R + k.x0]; t[3] = q[k.y1 * R + k.x1];
+}
+// taps of one channel + the image's byte there -> the result byte
+MIGAN_DEVICE MIGAN_INLINE unsigned char pipe_post_byte(const float t[4], const PipePostCoord& k, unsigned char image_byte) {
   auto to255 = [](float v) {
     float t = MIGAN_FMUL_RN(MIGAN_FADD_RN(MIGAN_FMUL_RN(v, 0.5f), 0.5f), 255.0f);    // ((y * 0.5 + 0.5) * 255)
     return fminf(fmaxf(t, 0.0f), 255.0f);
   };
+  const float o = bilinear_mix(to255(t[0]), to255(t[1]), to255(t[2]), to255(t[3]), k.l0x, k.l1x, k.l0y, k.l1y);
+  const float img = (float)image_byte;
+  float v = MIGAN_FADD_RN(MIGAN_FMUL_RN(img, k.mk), MIGAN_FMUL_RN(o, MIGAN_FSUB_RN(1.0f, k.mk)));
+  v = fminf(fmaxf(v, 0.0f), 255.0f);
+  return (unsigned char)(int)v;
+}
+MIGAN_DEVICE MIGAN_INLINE void pipe_post_pixel(unsigned char* image, const float* y, int H, int W, int R, int x_min, int y_min, int cw,
+                                               int ch, int py, int px, double acc) {
+  const PipePostCoord k = pipe_post_coord(R, cw, ch, py, px, acc);
+  const size_t plane = (size_t)H * W, oplane = (size_t)R * R;
+  const size_t at = (size_t)(y_min + py) * W + x_min + px;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const float* q = y + c * oplane;
-    const float o = bilinear_mix(to255(q[y0 * R + x0]), to255(q[y0 * R + x1]), to255(q[y1 * R + x0]), to255(q[y1 * R + x1]), l0x, l1x, l0y, l1y);
-    const float img = (float)image[c * plane + at];
-    float v = MIGAN_FADD_RN(MIGAN_FMUL_RN(img, mk), MIGAN_FMUL_RN(o, MIGAN_FSUB_RN(1.0f, mk)));
-    v = fminf(fmaxf(v, 0.0f), 255.0f);
-    image[c * plane + at] = (unsigned char)(int)v;
+    float t[4];
+    pipe_post_taps(y + c * oplane, R, k, t);
+    image[c * plane + at] = pipe_post_byte(t, k, image[c * plane + at]);
   }
 }
 
@@ -370,6 +391,113 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_post_batch_kernel(const PipeB
     }
   }
   pipe_post_pixel(it.image, p.y + (size_t)k * 3 * p.R * p.R, it.H, it.W, p.R, x_min, y_min, cw, ch, py, px, acc);
+}
+
+// ---- several completions per image, written out of place ---------------------------------------------------------------------------
+// pipe_post_batch_kernel for S generator outputs per item (y rows k * S ... k * S + S - 1), into a destination [S][3][H][W] of its
+// own: the image is only read.  Inside the box, sample s gets the byte pipe_post_batch_kernel would store for its y row; outside,
+// and everywhere when the box does not fit the image, the image's byte.  Every destination byte is written once, by one thread.
+//
+// The tiles are those of the IMAGE (tile t = (t / ntx, t % ntx) of ntx = cdiv(W, TW) columns), one pixel per thread, so the same
+// grid as pipe_post_batch_kernel's has no surplus workgroups: a tile that misses the box copies.  A tile that meets the box runs
+// the same three LDS steps around its own origin, (ty0, tx0) in crop coordinates, which may now be negative: window and pooled
+// entries outside the crop are filled as before and never read, since a reflected coordinate lies inside the crop and within 2 of
+// the pixel it came from.  What depends on the pixel alone -- the 25 fp64 products, the bilinear coordinates and weights, the three
+// image bytes -- is computed once, then the samples are looped over.
+// The item table is its own (32 bytes per item: no flags, no mask size, the mask pointer already resolved).
+constexpr int kPipeSamplesMax = 32;
+struct PipeSamplesItem {
+  const unsigned char* image;        // [3][H][W] uint8, read only
+  const unsigned char* mask;         // [H][W]: the caller's mask, or its nearest resize in scratch
+  unsigned char* out;                // [S][3][H][W] uint8
+  int H, W;
+};
+struct PipeSamplesArgs {
+  PipeSamplesItem item[kPipeSamplesMax];
+  int first[kPipeSamplesMax + 1];
+  const float* y;                    // [n * S][3][R][R], row k * S + s = sample s of item k
+  const int* bbox;                   // [n][4], as PipeBatchArgs::bbox
+  int n, R, S;
+  float gauss[25];
+};
+static_assert(sizeof(PipeSamplesArgs) <= 2048, "the samples argument must stay well under the 4 KB kernel-argument limit");
+
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_post_samples_kernel(const PipeSamplesArgs p) {
+  MIGAN_DYN_SMEM(smem);
+  unsigned char* win = reinterpret_cast<unsigned char*>(smem);       // [kPostWH][kPostWW]: crop rows ty0 - 3 ..., columns tx0 - 3 ...
+  unsigned char* pool = win + kPostWinBytes;                         // [kPostPH][kPostPW]: crop rows ty0 - 2 ..., columns tx0 - 2 ...
+  int k = 0;
+  while (k + 1 < p.n && (int)blockIdx.x >= p.first[k + 1]) ++k;      // (wave-uniform, as pipe_batch_item)
+  const PipeSamplesItem& it = p.item[k];
+  const int* box = p.bbox + 4 * k;
+  // the box came through device memory: one that does not fit the image is an empty crop here, and every tile copies
+  const bool valid = pipe_box_valid(box, it.H, it.W);
+  const int x_min = valid ? box[0] : 0, y_min = valid ? box[2] : 0, cw = valid ? box[1] - box[0] : 0, ch = valid ? box[3] - box[2] : 0;
+  const int tile = (int)blockIdx.x - p.first[k], ntx = (it.W + kPostTW - 1) / kPostTW;
+  const int iy0 = tile / ntx * kPostTH, ix0 = tile % ntx * kPostTW;  // the tile's origin in the image ...
+  const int ty0 = iy0 - y_min, tx0 = ix0 - x_min;                    // ... and in the crop
+  // workgroup-uniform: the tile has a pixel inside the crop
+  const bool blend = ty0 < ch && ty0 + kPostTH > 0 && tx0 < cw && tx0 + kPostTW > 0;
+  const int t = (int)threadIdx.x;
+  if (blend) {
+    for (int e = t; e < kPostWH * kPostWW; e += kThreads) {
+      const int cy = ty0 - 3 + e / kPostWW, cx = tx0 - 3 + e % kPostWW;
+      win[e] = (cy >= 0 && cy < ch && cx >= 0 && cx < cw) ? it.mask[(size_t)(y_min + cy) * it.W + x_min + cx] : (unsigned char)0;
+    }
+    __syncthreads();
+    for (int e = t; e < kPostPH * kPostPW; e += kThreads) {
+      const unsigned char* w0 = win + e / kPostPW * kPostWW + e % kPostPW;
+      int m = 0;
+#pragma unroll
+      for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+          const int v = w0[dy * kPostWW + dx];
+          m = v > m ? v : m;
+        }
+      pool[e] = (unsigned char)m;
+    }
+    __syncthreads();
+  }
+  const int row = iy0 + t / kPostTW, col = ix0 + t % kPostTW;
+  if (row >= it.H || col >= it.W) return;
+  const size_t plane = (size_t)it.H * it.W, at = (size_t)row * it.W + col;
+  const unsigned char img[3] = {it.image[at], it.image[plane + at], it.image[2 * plane + at]};
+  const int py = row - y_min, px = col - x_min;
+  if (!blend || py < 0 || py >= ch || px < 0 || px >= cw) {
+    for (int s = 0; s < p.S; ++s) {
+      unsigned char* o = it.out + (size_t)s * 3 * plane + at;
+      o[0] = img[0]; o[plane] = img[1]; o[2 * plane] = img[2];
+    }
+    return;
+  }
+  double acc = 0.0;
+  for (int ky = 0; ky < 5; ++ky) {
+    const int yy = pipe_reflect(py + ky - 2, ch) - (ty0 - 2);
+    for (int kx = 0; kx < 5; ++kx) {
+      const int xx = pipe_reflect(px + kx - 2, cw) - (tx0 - 2);
+      acc += (double)p.gauss[ky * 5 + kx] * (double)pool[yy * kPostPW + xx];
+    }
+  }
+  const PipePostCoord c = pipe_post_coord(p.R, cw, ch, py, px, acc);
+  const size_t oplane3 = (size_t)3 * p.R * p.R;
+  const float* y = p.y + (size_t)k * p.S * oplane3;
+  const size_t oplane = (size_t)p.R * p.R;
+  for (int s = 0; s < p.S; ++s) {
+    unsigned char* o = it.out + (size_t)s * 3 * plane + at;
+    // The blend of pipe_post_byte, img * mk + o * (1 - mk), is contracted by the compiler into one rounded product and an FMA, and
+    // which product stays exact follows from where the two are computed.  img * mk does not depend on the sample: lifted out of
+    // this loop it would be the rounded one, the other way round than in pipe_post_pixel, and a result next to an integer would
+    // differ from pipe_post_batch_kernel's by one.  With mk opaque in every pass both products are formed here, as there.
+    PipePostCoord cs = c;
+    MIGAN_OPAQUE_F(cs.mk);
+#pragma unroll
+    for (int ch3 = 0; ch3 < 3; ++ch3) {
+      float t[4];
+      pipe_post_taps(y + ((size_t)s * 3 + ch3) * oplane, p.R, cs, t);
+      o[ch3 * plane] = pipe_post_byte(t, cs, img[ch3]);
+    }
+  }
 }
 #endif  // MIGAN_TEMPLATE_KERNELS_ONLY
 

@@ -79,6 +79,8 @@ EXPORTS = (
 # include/comodgan_samples_hip.h
 SAMPLES_EXPORTS = ("comodgan_workspace_bytes_samples", "comodgan_forward_samples", "comodgan_forward_samples_timed",
                    "comodgan_debug_tensor_samples")
+# include/migan_pipeline_samples_hip.h
+PIPELINE_SAMPLES_EXPORTS = ("migan_pipeline_batch_post_samples",)
 
 
 class PipelineItem(C.Structure):
@@ -140,7 +142,7 @@ class MiganLib:
         except OSError as e:  # pragma: no cover - depends on the machine
             raise MiganError(f"cannot load {self.path}: {e}") from e
         L = self.lib
-        for name in EXPORTS + SAMPLES_EXPORTS:
+        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS:
             if not hasattr(L, name):
                 raise MiganError(f"{self.path} does not export {name}")
         vp, ci = C.c_void_p, C.c_int
@@ -163,6 +165,7 @@ class MiganLib:
         L.migan_pipeline_batch_scratch_bytes.argtypes = [C.POINTER(PipelineItem), ci, C.POINTER(C.c_size_t)]
         L.migan_pipeline_batch_pre.argtypes = [C.POINTER(PipelineItem), ci, ci, ci, vp, vp, vp, vp]
         L.migan_pipeline_batch_post.argtypes = [C.POINTER(PipelineItem), ci, ci, vp, vp, C.POINTER(C.c_float), vp, vp]
+        L.migan_pipeline_batch_post_samples.argtypes = [C.POINTER(PipelineItem), ci, ci, ci, vp, vp, C.POINTER(C.c_float), vp, C.POINTER(vp), vp]
         L.migan_num_weights.argtypes = [vp, C.POINTER(ci)]
         L.migan_weight_info.argtypes = [vp, ci, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(ci), C.POINTER(ci)]
         L.migan_set_weight.argtypes = [vp, C.c_char_p, vp, C.POINTER(C.c_int64), ci]
@@ -213,7 +216,7 @@ class MiganLib:
         if not allow_test_backend and L.migan_backend().decode() != PRODUCT_BACKEND:
             raise MiganError(f"{self.path} reports backend {L.migan_backend().decode()!r}, not {PRODUCT_BACKEND!r}: only the gfx950 HIP "
                              f"library is a product backend (the CPU emulator build is test infrastructure)")
-        for name in EXPORTS + SAMPLES_EXPORTS:
+        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS:
             if name not in ("migan_last_error", "migan_last_kernel", "migan_nan_policy", "migan_backend", "migan_gemm_variant", "migan_tuning_key"):
                 getattr(L, name).restype = ci
 
@@ -311,6 +314,18 @@ class MiganLib:
         g = None if gauss25 is None else (C.c_float * 25)(*[float(v) for v in gauss25])
         self.check(self.lib.migan_pipeline_batch_post(pipeline_items(items), len(items), int(resolution), C.c_void_p(y_ptr),
                                                       C.c_void_p(bbox_ptr), g, C.c_void_p(scratch_ptr), C.c_void_p(stream)))
+
+    def pipeline_batch_post_samples(self, items, samples: int, resolution: int, y_ptr: int, bbox_ptr: int, scratch_ptr: int, out_ptrs,
+                                    gauss25=None, stream: int = 0) -> None:
+        """include/migan_pipeline_samples_hip.h: y [len(items) * samples, 3, R, R] -> out_ptrs[i] = [samples, 3, H_i, W_i] uint8, out of
+        place (the images are only read); out_ptrs has one entry per item (None passes a null table through)"""
+        g = None if gauss25 is None else (C.c_float * 25)(*[float(v) for v in gauss25])
+        outs = None if out_ptrs is None else (C.c_void_p * max(1, len(out_ptrs)))(*[p or None for p in out_ptrs])
+        if outs is not None and len(out_ptrs) != len(items):
+            raise ValueError(f"expected one destination per item, got {len(out_ptrs)} for {len(items)} items")
+        self.check(self.lib.migan_pipeline_batch_post_samples(pipeline_items(items), len(items), int(samples), int(resolution),
+                                                              C.c_void_p(y_ptr), C.c_void_p(bbox_ptr), g, C.c_void_p(scratch_ptr), outs,
+                                                              C.c_void_p(stream)))
 
     def sepconv_forward(self, stream: int = 0, **kw) -> None:
         d = SepConvDesc()

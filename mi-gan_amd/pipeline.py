@@ -52,11 +52,16 @@ class MIGAN_Pipeline(torch.nn.Module):
 
       image (1, 3, H, W) uint8, mask (1, 1, H, W) uint8 (255 = known pixel); the image is modified in place and returned.
 
-    ``model_path`` is a reference ``migan_*.pt`` state dict, or an already built ``mi-gan_amd`` Generator.  A mask of another size is
-    resized to the image's size first (nearest), like the reference's first line (:256).  No CPU path.
+    ``model_path`` is a reference ``migan_*.pt`` state dict, or an already built module: a ``mi-gan_amd`` Generator, or a
+    ``comodgan.Generator`` of the pipeline's resolution (x [N, 4, R, R] -> y [N, 3, R, R]; ``forward_samples`` then gives several
+    completions per image).  A mask of another size is resized to the image's size first (nearest), like the reference's first line
+    (:256).  No CPU path.
 
     ``forward_batch(images, masks)`` is the same for N images of different sizes around ONE generator forward per ``max_batch``
-    images, with the boxes kept on the device (``migan_pipeline_batch_pre / _post``): no host synchronisation in between."""
+    images, with the boxes kept on the device (``migan_pipeline_batch_pre / _post``): no host synchronisation in between.
+
+    ``forward_samples(images, masks, z)`` leaves the images as they are and returns S completions of each, [S, 3, H_i, W_i], from one
+    pass over the image per chunk (``migan_pipeline_batch_post_samples``)."""
 
     def __init__(self, model_path, resolution: int, padding: int = 128, device="cuda"):
         super().__init__()
@@ -144,19 +149,9 @@ class MIGAN_Pipeline(torch.nn.Module):
                           gauss25=self._gauss, stream=stream)
         return image
 
-    @torch.no_grad()
-    def forward_batch(self, images, masks, *, max_batch: int = 32, return_bbox: bool = False):
-        """``forward`` for N images of different sizes: images[i] (1, 3, H_i, W_i) or (3, H_i, W_i) uint8, contiguous, masks[i]
-        (1, 1, h_i, w_i) or (h_i, w_i) uint8, all on one device.  Per chunk of at most ``max_batch`` images: masks resized where
-        needed -> boxes (on the device) -> x [n, 4, R, R] -> ONE ``self.model(x)`` -> blend, with no host synchronisation in
-        between.  The images are modified in place and returned as a list; with ``return_bbox`` also the int32 [N, 4] device tensor
-        of {x_min, x_max, y_min, y_max} rows.  Each image gets what ``forward`` gives it, up to the fp32 rounding by which the
-        generator at batch n differs from batch 1.  Two entries that share memory are undefined."""
-        images, masks = list(images), list(masks)
-        if len(images) != len(masks) or not images:
-            raise RuntimeError(f"expected as many masks as images and at least one, got {len(images)} images and {len(masks)} masks")
-        if int(max_batch) < 1:
-            raise RuntimeError(f"max_batch must be at least 1, got {max_batch}")
+    @staticmethod
+    def _batch_items(images, masks):
+        """the per-image input checks of forward_batch / forward_samples -> [(image ptr, mask ptr, H, W, h, w, the contiguous mask), ...], device"""
         items, device = [], None
         for image, mask in zip(images, masks):
             if not (image.is_cuda and mask.is_cuda):
@@ -174,6 +169,22 @@ class MIGAN_Pipeline(torch.nn.Module):
             mask = mask.contiguous()
             items.append((image.data_ptr(), mask.data_ptr(), int(image.shape[-2]), int(image.shape[-1]), int(mask.shape[-2]),
                           int(mask.shape[-1]), mask))                # (the contiguous mask stays alive until the kernels are queued)
+        return items, device
+
+    @torch.no_grad()
+    def forward_batch(self, images, masks, *, max_batch: int = 32, return_bbox: bool = False):
+        """``forward`` for N images of different sizes: images[i] (1, 3, H_i, W_i) or (3, H_i, W_i) uint8, contiguous, masks[i]
+        (1, 1, h_i, w_i) or (h_i, w_i) uint8, all on one device.  Per chunk of at most ``max_batch`` images: masks resized where
+        needed -> boxes (on the device) -> x [n, 4, R, R] -> ONE ``self.model(x)`` -> blend, with no host synchronisation in
+        between.  The images are modified in place and returned as a list; with ``return_bbox`` also the int32 [N, 4] device tensor
+        of {x_min, x_max, y_min, y_max} rows.  Each image gets what ``forward`` gives it, up to the fp32 rounding by which the
+        generator at batch n differs from batch 1.  Two entries that share memory are undefined."""
+        images, masks = list(images), list(masks)
+        if len(images) != len(masks) or not images:
+            raise RuntimeError(f"expected as many masks as images and at least one, got {len(images)} images and {len(masks)} masks")
+        if int(max_batch) < 1:
+            raise RuntimeError(f"max_batch must be at least 1, got {max_batch}")
+        items, device = self._batch_items(images, masks)
         lib = load_library()
         bbox = torch.empty((len(items), 4), dtype=torch.int32, device=device)
         with torch.cuda.device(device):                          # the handle-free entry points launch on the CURRENT device
@@ -194,3 +205,82 @@ class MIGAN_Pipeline(torch.nn.Module):
                 lib.pipeline_batch_post(chunk, self.res, y.data_ptr(), box.data_ptr(), scratch.data_ptr(), gauss25=self._gauss,
                                         stream=stream)
         return (images, bbox) if return_bbox else images
+
+    @torch.no_grad()
+    def forward_samples(self, images, masks, z=None, samples=None, *, max_rows: int = 32, return_bbox: bool = False, **model_kwargs):
+        """S completions per image, written OUT OF PLACE: images and masks as for ``forward_batch`` and not modified -> a list of
+        uint8 tensors [S, 3, H_i, W_i] (views of one allocation), with ``return_bbox`` also the int32 [N, 4] device tensor of boxes.
+
+        A model with a ``forward_samples`` method (``comodgan.Generator``): ``z`` [N, S, z_dim], or ``samples=S`` draws it;
+        ``model_kwargs`` (truncation_psi, truncation_cutoff, noise_mode) go to the model unchanged.  Per chunk of ``max_rows // S``
+        images: boxes and x once per image -> ``model.forward_samples(x, z)``: the encoder once per image, [n * S, 3, R, R] ->
+        ``migan_pipeline_batch_post_samples``: each image read once, its feathered mask built once, S images written.  No host
+        synchronisation in between.
+
+        Any other model (the MI-GAN generator) gives one completion: ``z`` must be None and S is 1; ``self.model(x)`` runs on
+        ``forward_batch``'s chunks (``max_rows`` images, a lone last chunk at batch 2), so ``forward_samples(images, masks)[i][0]``
+        holds the bytes ``forward_batch`` writes into a copy of images[i].
+
+        Inside its box, sample s of image i is what ``forward_batch`` gives a copy of the image for that generator output; outside
+        it is the image.  An image whose mask yields no usable box is returned as S plain copies."""
+        images, masks = list(images), list(masks)
+        if len(images) != len(masks) or not images:
+            raise RuntimeError(f"expected as many masks as images and at least one, got {len(images)} images and {len(masks)} masks")
+        if int(max_rows) < 1:
+            raise RuntimeError(f"max_rows must be at least 1, got {max_rows}")
+        items, device = self._batch_items(images, masks)
+        n_img, max_rows = len(items), int(max_rows)
+        sampler = getattr(self.model, "forward_samples", None)
+        if samples is not None and (int(samples) != samples or samples < 1):
+            raise ValueError(f"samples must be a positive integer or None, got {samples!r}")
+        if sampler is None:
+            if z is not None or (samples is not None and int(samples) != 1) or model_kwargs:
+                raise ValueError(f"{type(self.model).__name__} has no forward_samples: it gives one completion per image, so z must be None, "
+                                 f"samples None or 1, and there are no model options")
+            s, per_chunk = 1, max_rows
+        else:
+            if z is None:
+                if samples is None:
+                    raise ValueError("forward_samples needs z of shape [N, S, z_dim], or samples=S to draw it")
+                s = int(samples)
+                z = torch.randn([n_img, s, self.model.z_dim]).to(device)
+            else:
+                if not z.is_cuda or z.device != device:
+                    raise RuntimeError("mi-gan_amd.pipeline needs tensors on an MI355X (HIP) device; there is no CPU path (z must be on the images' device)")
+                if not z.is_floating_point():
+                    raise RuntimeError(f"z must be a floating-point tensor, got {z.dtype}")
+                if z.dim() != 3 or z.shape[0] != n_img or z.shape[1] < 1:
+                    raise ValueError(f"expected z of shape [{n_img}, S, z_dim] (S latents for each of the {n_img} images), got {list(z.shape)}")
+                if samples is not None and int(samples) != z.shape[1]:
+                    raise ValueError(f"samples={samples} contradicts z of shape {list(z.shape)}")
+                s = int(z.shape[1])
+            if s > max_rows:
+                raise ValueError(f"{s} samples per image do not fit max_rows={max_rows} generator rows per chunk: raise max_rows")
+            per_chunk = max_rows // s
+        lib = load_library()
+        bbox = torch.empty((n_img, 4), dtype=torch.int32, device=device)
+        sizes = [3 * it[2] * it[3] for it in items]
+        flat = torch.empty(s * sum(sizes), dtype=torch.uint8, device=device)       # all S x N outputs; the list holds views
+        outs, at = [], 0
+        for it, size in zip(items, sizes):
+            outs.append(flat[at:at + s * size].view(s, 3, it[2], it[3]))
+            at += s * size
+        with torch.cuda.device(device):                          # the handle-free entry points launch on the CURRENT device
+            stream = int(torch.cuda.current_stream(device).cuda_stream)
+            for i0 in range(0, n_img, per_chunk):
+                chunk = [it[:6] for it in items[i0:i0 + per_chunk]]
+                scratch = self._scratch_bytes(lib.pipeline_batch_scratch_bytes(chunk), device)
+                box = bbox[i0:i0 + len(chunk)]
+                # (without a sampler: forward_batch's rule for a lone last chunk, so that the bytes are forward_batch's)
+                pad = 1 if sampler is None and len(chunk) == 1 and n_img > 1 and per_chunk > 1 else 0
+                x = torch.empty((len(chunk) + pad, 4, self.res, self.res), dtype=torch.float32, device=device)
+                lib.pipeline_batch_pre(chunk, self.res, self.padding, x.data_ptr(), box.data_ptr(), scratch.data_ptr(), stream)
+                if pad:
+                    x[1].copy_(x[0])
+                if sampler is None:
+                    y = self.model(x).contiguous()
+                else:
+                    y = sampler(x, z[i0:i0 + len(chunk)], **model_kwargs).reshape(len(chunk) * s, 3, self.res, self.res).contiguous()
+                lib.pipeline_batch_post_samples(chunk, s, self.res, y.data_ptr(), box.data_ptr(), scratch.data_ptr(),
+                                                [o.data_ptr() for o in outs[i0:i0 + len(chunk)]], gauss25=self._gauss, stream=stream)
+        return (outs, bbox) if return_bbox else outs
