@@ -6,11 +6,13 @@ scripts/demo.py:95-106 assembles ``comodgan-256|512`` -- keeps the reference's c
 (comodgan.py:435-455), but ``Generator.forward`` is one call into the MI355X HIP library through the C ABI
 (include/comodgan_hip.h).  PyTorch is used for device memory, streams and drawing ``z`` / the per-pixel noise of
 ``noise_mode='random'`` only.  There is no CPU or pure-PyTorch path: a CPU tensor, a missing libmigan_hip.so or
-a missing GPU raises.  Not supported: autograd, ``c`` (class conditioning: c_dim = 0 in every reference config),
-``truncation_cutoff``, ``return_intermediate_outs``.
+a missing GPU raises.  ``Encoder(use_fp16_before_res=)`` / ``Synthesis(use_fp16_after_res=)`` mark half-precision blocks as
+in the reference: their 3x3 convolutions take fp16 operands (fp32 accumulation and storage).  Not supported: autograd,
+``c`` (class conditioning: c_dim = 0 in every reference config), ``truncation_cutoff``, ``return_intermediate_outs``.
 """
 from __future__ import annotations
 
+import operator
 from typing import List, Optional, Tuple
 
 import torch
@@ -73,6 +75,19 @@ def _populate(root: nn.Module, prefix: str, cfg: cs.Config) -> None:
             node.register_buffer(parts[-1], t)
 
 
+def _fp16_res(name: str, value) -> Optional[int]:
+    """use_fp16_before_res / use_fp16_after_res: None (no half-precision block) or a non-negative integer resolution"""
+    if value is None:
+        return None
+    try:
+        res = None if isinstance(value, bool) else operator.index(value)
+    except TypeError:
+        res = None
+    if res is None or res < 0:
+        raise ValueError(f"{name} must be None or a non-negative integer, got {value!r}")
+    return res
+
+
 class Mapping(_Node):
     """stylegan.py:356-439 (c_dim = 0).  Parameter container; evaluated inside Generator.forward."""
 
@@ -87,8 +102,10 @@ class Mapping(_Node):
 class Encoder(_Node):
     """comodgan.py:114-204."""
 
-    def __init__(self, resolution: int = 256, ic_n: int = 4, oc_n: int = 1024, ch_base: int = 32768, ch_max: int = 512, **unused):
+    def __init__(self, resolution: int = 256, ic_n: int = 4, oc_n: int = 1024, ch_base: int = 32768, ch_max: int = 512,
+                 use_fp16_before_res: Optional[int] = None, **unused):
         super().__init__("Encoder")
+        self.use_fp16_before_res = _fp16_res("use_fp16_before_res", use_fp16_before_res)    # blocks b<res>, res > it (comodgan.py:148)
         if ic_n != 4:
             raise NotImplementedError("the inference path takes 4 input channels (mask, rgb)")
         cfg = cs.Config(resolution=resolution, ch_base=ch_base, ch_max=ch_max, w0_dim=oc_n)
@@ -101,8 +118,9 @@ class Synthesis(_Node):
     """comodgan.py:346-420."""
 
     def __init__(self, w_dim: int = 512, w0_dim: int = 1024, resolution: int = 256, rgb_n: int = 3, ch_base: int = 32768,
-                 ch_max: int = 512, **unused):
+                 ch_max: int = 512, use_fp16_after_res: Optional[int] = None, **unused):
         super().__init__("Synthesis")
+        self.use_fp16_after_res = _fp16_res("use_fp16_after_res", use_fp16_after_res)       # blocks b<res>, res > it (comodgan.py:384)
         if rgb_n != 3:
             raise NotImplementedError("rgb_n must be 3")
         cfg = cs.Config(resolution=resolution, ch_base=ch_base, ch_max=ch_max, w_dim=w_dim, w0_dim=w0_dim)
@@ -137,6 +155,7 @@ class Generator(nn.Module):
         self._frozen = False         # freeze_weights(): the caller's promise that parameters no longer change in place
         self._refreeze = True        # the handle has not been told yet
         self._cutoff: Optional[int] = None   # truncation_cutoff the handle was last told
+        self._fp16: Tuple[Optional[int], Optional[int]] = (None, None)   # half-precision blocks the handle was last told
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._invalidate())
 
     # ------------------------------------------------------------------ plumbing
@@ -181,6 +200,14 @@ class Generator(nn.Module):
             self._bound = None
             self._refreeze = True
             self._cutoff = None
+            self._fp16 = (None, None)
+        # half-precision blocks (the reference's constructor arguments, kept as attributes of the two sub-modules): their 3x3
+        # convolutions run with single fp16 operands.  Part of the plan, so the handle is told before the workspace is sized.
+        fp16 = (_fp16_res("use_fp16_before_res", self.encoder.use_fp16_before_res),
+                _fp16_res("use_fp16_after_res", self.synthesis.use_fp16_after_res))
+        if fp16 != self._fp16:
+            self._handle.set_fp16_blocks(*fp16)
+            self._fp16 = fp16
         tensors = self._tensors()
         ptrs = tuple(t.data_ptr() for t in tensors)
         if self._dirty or ptrs != self._bound:

@@ -7,6 +7,7 @@
 
 #include "../../include/comodgan_hip.h"
 #include "../../include/comodgan_samples_hip.h"
+#include "../../include/comodgan_fp16_hip.h"
 
 namespace migan {
 
@@ -27,8 +28,9 @@ struct CmDebugTensor {
 };
 
 typedef void (*CmConvFn)(const CmConvArgs);
-struct CmConvEntry { int NT, KC, nine, MTI; CmConvFn fn; const char* name; int up4 = 0; };
+struct CmConvEntry { int NT, KC, nine, MTI; CmConvFn fn; const char* name; int up4 = 0, f16 = 0; };
 #define CM_CONV_ENTRY(NT, KC, NIA, NINE, MTI) {NT, KC, NINE, MTI, cm_conv_kernel<NT, KC, NIA, NINE, MTI>, "migan::cm_conv_kernel<" #NT ", " #KC ", " #NIA ", " #NINE ", " #MTI ", false>"}
+#define CM_CONV_F16_ENTRY(NT, KC, NIA, NINE, MTI, UP4) {NT, KC, NINE, MTI, cm_conv_f16_kernel<NT, KC, NIA, NINE, MTI, UP4>, "migan::cm_conv_f16_kernel<" #NT ", " #KC ", " #NIA ", " #NINE ", " #MTI ", " #UP4 ">", UP4, 1}
 inline const std::vector<CmConvEntry>& cm_conv_table() {
   static const std::vector<CmConvEntry> t = {
       // 8 x 16 pixel tiles (MTI 2), 64 / 128 output channels: nine-tap unrolled K loop (plain: 10x18-pixel tile, 6 items per thread;
@@ -41,12 +43,18 @@ inline const std::vector<CmConvEntry>& cm_conv_table() {
       // all four transposed-convolution phases in one launch (nine taps, four accumulator sets)
       {64, 32, 1, 2, cm_conv_kernel<64, 32, 6, true, 2, true>, "migan::cm_conv_kernel<64, 32, 6, true, 2, true>", 1},
       {128, 32, 1, 2, cm_conv_kernel<128, 32, 6, true, 2, true>, "migan::cm_conv_kernel<128, 32, 6, true, 2, true>", 1},
+      // the single-plane form (half-precision blocks), one row per row above: same tiles, same prefetch registers
+      CM_CONV_F16_ENTRY(64, 32, 6, true, 2, false), CM_CONV_F16_ENTRY(128, 32, 6, true, 2, false),
+      CM_CONV_F16_ENTRY(64, 16, 9, true, 2, false), CM_CONV_F16_ENTRY(128, 16, 9, true, 2, false),
+      CM_CONV_F16_ENTRY(64, 32, 6, false, 2, false), CM_CONV_F16_ENTRY(128, 32, 6, false, 2, false),
+      CM_CONV_F16_ENTRY(256, 32, 11, true, 4, false), CM_CONV_F16_ENTRY(256, 16, 18, true, 4, false), CM_CONV_F16_ENTRY(256, 32, 11, false, 4, false),
+      CM_CONV_F16_ENTRY(64, 32, 6, true, 2, true), CM_CONV_F16_ENTRY(128, 32, 6, true, 2, true),
   };
   return t;
 }
-inline const CmConvEntry& cm_pick_conv(int NT, int KC, bool nine, int MTI, bool up4 = false) {
+inline const CmConvEntry& cm_pick_conv(int NT, int KC, bool nine, int MTI, bool up4 = false, bool f16 = false) {
   for (const auto& e : cm_conv_table())
-    if (e.NT == NT && e.KC == KC && (e.nine != 0) == nine && e.MTI == MTI && (e.up4 != 0) == up4) return e;
+    if (e.NT == NT && e.KC == KC && (e.nine != 0) == nine && e.MTI == MTI && (e.up4 != 0) == up4 && (e.f16 != 0) == f16) return e;
   throw Error(MIGAN_EINVAL, "internal: no cm_conv_kernel instantiation for this tile");
 }
 
@@ -91,7 +99,9 @@ struct CmConvGeo {
   unsigned grid;
   double flops, bytes;
 };
-inline CmConvGeo cm_conv_geometry(int mode, int phase, int H, int Wd, int HO, int WO, int ci, int co, int B, const CmForced& forced) {
+// f16: the single-plane form (a layer of a half-precision block): same tiles and tap lists on the narrower LDS rows.
+inline CmConvGeo cm_conv_geometry(int mode, int phase, int H, int Wd, int HO, int WO, int ci, int co, int B, const CmForced& forced,
+                                  bool f16 = false) {
   CmConvGeo g = CmConvGeo();      // all zero, the padding of the argument struct included
   CmConvArgs& a = g.a;
   const int ey = phase >> 1, ex = phase & 1;
@@ -148,7 +158,7 @@ inline CmConvGeo cm_conv_geometry(int mode, int phase, int H, int Wd, int HO, in
   if (mode == CM_CONV_UP4) NT = (forced.up4_wide && co % 128 == 0) ? 128 : 64;
   const int KC = mode == CM_CONV_DOWN ? 16 : 32;          // the (2GH+1)x33-pixel tile of the strided mode is staged 16 channels at a time
   a.tiles_y = cdiv(a.GHn, GH); a.tiles_x = cdiv(a.GWn, 16); a.nchunks = co / NT;
-  const size_t pitch = (size_t)4 * KC + 16;                // LDS row: both fp16 planes of KC channels + 16 bytes of padding
+  const size_t pitch = (size_t)(f16 ? 2 : 4) * KC + 16;    // LDS row: the fp16 planes (two; one in the single-plane form) of KC channels + 16 bytes of padding
   const size_t a_bytes = (size_t)a.IH * a.IW * pitch;
   a.off_b = (int)((a_bytes + 127) & ~(size_t)127);
   g.lds = std::max<size_t>((size_t)a.off_b + (size_t)2 * NT * pitch, (size_t)64 * (NT + 4) * 4);
@@ -164,7 +174,7 @@ inline CmConvGeo cm_conv_geometry(int mode, int phase, int H, int Wd, int HO, in
   const bool nine = a.ntaps == 9;
   MIGAN_CHECK(!nine || (ci / KC) % 2 == 0, MIGAN_EINVAL, "internal: the nine-tap kernel walks channel chunks in pairs");
   MIGAN_CHECK(nine || KC == 32, MIGAN_EINVAL, "internal: no generic-tap-list kernel with 16-channel chunks");
-  g.kernel = &cm_pick_conv(NT, KC, nine, MTI, mode == CM_CONV_UP4);
+  g.kernel = &cm_pick_conv(NT, KC, nine, MTI, mode == CM_CONV_UP4, f16);
   return g;
 }
 
@@ -176,6 +186,7 @@ struct CmConvL {                     // a 3x3 convolution
   int res = 0, ci = 0, co = 0;       // res: resolution of the block the layer belongs to
   int w = -1, b = -1;
   int noise_const = -1, noise_strength = -1, job = -1;   // modulated layers (synthesis): noise tensors and the index in CmNet::jobs
+  bool f16 = false;                  // the layer belongs to a half-precision block (comodgan_handle::mark_fp16): single-plane convolution
 };
 struct CmRgbL { std::string name; int c = 0, w = -1, b = -1, job = -1; };
 // A modulated layer: one job of the affine launch (styles = affine(cat([w, w0]))) and, under the same index, one job of the
@@ -205,8 +216,10 @@ struct CmPlanKey {
   bool debug = false;
   CmForced forced;
   int samples = 1;                   // completions per image (comodgan_forward_samples); batch counts images
+  int fp16_enc = -1, fp16_syn = -1;  // comodgan_set_fp16_blocks: which layers run the single-plane convolution
   bool operator==(const CmPlanKey& o) const {
-    return batch == o.batch && samples == o.samples && debug == o.debug && trunc_cutoff == o.trunc_cutoff && forced == o.forced;
+    return batch == o.batch && samples == o.samples && debug == o.debug && trunc_cutoff == o.trunc_cutoff && forced == o.forced &&
+           fp16_enc == o.fp16_enc && fp16_syn == o.fp16_syn;
   }
 };
 
@@ -225,6 +238,8 @@ struct comodgan_handle {
   size_t planned_need = 0;       // workspace bytes
   std::vector<rt::event_t> events;
   int trunc_cutoff = -1;       // comodgan_set_truncation_cutoff: -1 = None (every row of ws truncated), else rows [0, cutoff)
+  // comodgan_set_fp16_blocks: the reference's use_fp16_before_res / use_fp16_after_res, -1 = None (no half-precision block)
+  int fp16_enc = -1, fp16_syn = -1;
   // comodgan_assume_static_weights: skip the per-forward weight preparation while nothing it depends on has changed
   bool static_weights = false;
   const void* prepared_ws = nullptr;
@@ -237,6 +252,7 @@ struct comodgan_handle {
 
   int channels(int res) const { return std::min(cfg.ch_base / res, cfg.ch_max); }
   void build_schema();
+  void mark_fp16();
   size_t noise_floats() const {
     size_t n = 16;
     for (int res = 8; res <= cfg.resolution; res *= 2) n += 2 * (size_t)res * res;
@@ -316,6 +332,15 @@ inline void comodgan_handle::build_schema() {
   for (int k = 0; k < (int)net.convs.size(); ++k) net.prep.push_back((first_enc + k) % (int)net.convs.size());
   MIGAN_CHECK((int)net.jobs.size() <= kCmMaxAffine, MIGAN_EINVAL, "internal: too many affine layers");
   MIGAN_CHECK((int)net.jobs.size() <= kCmMaxStyle, MIGAN_EINVAL, "internal: too many modulated layers");
+  mark_fp16();
+}
+
+// Which blocks are half precision, as the reference marks them: encoder block b<res> where res > use_fp16_before_res
+// (comodgan.py:148), synthesis block b<res> where res > use_fp16_after_res (comodgan.py:384); the two b4 blocks never.
+inline void comodgan_handle::mark_fp16() {
+  for (auto& c : net.convs) c.f16 = false;
+  for (const auto& b : net.enc) net.convs[b.conv0].f16 = net.convs[b.conv1].f16 = fp16_enc >= 0 && b.res > fp16_enc;
+  for (const auto& b : net.syn) net.convs[b.conv0].f16 = net.convs[b.conv1].f16 = fp16_syn >= 0 && b.res > fp16_syn;
 }
 
 namespace migan {
@@ -448,7 +473,7 @@ struct CmWalk {
   void conv(int index, const char* suffix, int mode, int phase, const float* xin, float* out, int H, int Wd, int HO, int WO,
             const CmNoise& nz = CmNoise{}, bool raw = false) {
     const CmConvL& L = net.convs[index];
-    CmConvGeo g = cm_conv_geometry(mode, phase, H, Wd, HO, WO, L.ci, L.co, nb, forced);
+    CmConvGeo g = cm_conv_geometry(mode, phase, H, Wd, HO, WO, L.ci, L.co, nb, forced, L.f16);
     CmConvArgs& a = g.a;
     a.x = xin; a.y = out; a.wsplit = conv_ws[index].planes;
     if (L.job >= 0) { a.sa = job_ws[L.job].sa; a.coef = job_ws[L.job].coef; }
@@ -715,7 +740,7 @@ struct CmWalk {
 }  // namespace migan
 
 inline size_t comodgan_handle::ensure_planned(int batch, int samples) const {
-  const migan::CmPlanKey key{batch, trunc_cutoff, debug, migan::cm_read_forced(), samples};
+  const migan::CmPlanKey key{batch, trunc_cutoff, debug, migan::cm_read_forced(), samples, fp16_enc, fp16_syn};
   if (!(key == planned)) {
     comodgan_handle* m = const_cast<comodgan_handle*>(this);      // the queries of the C ABI take a const handle; the plan is a cache
     m->planned = migan::CmPlanKey{};                              // (nothing planned if the walk throws)
@@ -937,6 +962,25 @@ int comodgan_set_truncation_cutoff(comodgan_handle* h, int cutoff) {
   MIGAN_CHECK(h, MIGAN_EINVAL, "null handle");
   MIGAN_CHECK(cutoff >= -1, MIGAN_EINVAL, "truncation_cutoff must be >= 0, or -1 for None");
   h->trunc_cutoff = cutoff;                // (one more [batch][w_dim] buffer in the workspace: part of the plan's key)
+  MIGAN_API_END
+}
+
+int comodgan_set_fp16_blocks(comodgan_handle* h, int encoder_before_res, int synthesis_after_res) {
+  MIGAN_API_BEGIN
+  MIGAN_CHECK(h, MIGAN_EINVAL, "null handle");
+  MIGAN_CHECK(encoder_before_res >= -1, MIGAN_EINVAL, "encoder_before_res must be >= 0, or -1 for None");
+  MIGAN_CHECK(synthesis_after_res >= -1, MIGAN_EINVAL, "synthesis_after_res must be >= 0, or -1 for None");
+  h->fp16_enc = encoder_before_res;        // (part of the plan's key; the prepared weight planes serve both forms)
+  h->fp16_syn = synthesis_after_res;
+  h->mark_fp16();
+  MIGAN_API_END
+}
+
+int comodgan_get_fp16_blocks(const comodgan_handle* h, int* encoder_before_res, int* synthesis_after_res) {
+  MIGAN_API_BEGIN
+  MIGAN_CHECK(h && encoder_before_res && synthesis_after_res, MIGAN_EINVAL, "null argument");
+  *encoder_before_res = h->fp16_enc;
+  *synthesis_after_res = h->fp16_syn;
   MIGAN_API_END
 }
 

@@ -81,6 +81,8 @@ SAMPLES_EXPORTS = ("comodgan_workspace_bytes_samples", "comodgan_forward_samples
                    "comodgan_debug_tensor_samples")
 # include/migan_pipeline_samples_hip.h
 PIPELINE_SAMPLES_EXPORTS = ("migan_pipeline_batch_post_samples",)
+# include/comodgan_fp16_hip.h
+FP16_EXPORTS = ("comodgan_set_fp16_blocks", "comodgan_get_fp16_blocks")
 
 
 class PipelineItem(C.Structure):
@@ -142,7 +144,7 @@ class MiganLib:
         except OSError as e:  # pragma: no cover - depends on the machine
             raise MiganError(f"cannot load {self.path}: {e}") from e
         L = self.lib
-        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS:
+        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + FP16_EXPORTS:
             if not hasattr(L, name):
                 raise MiganError(f"{self.path} does not export {name}")
         vp, ci = C.c_void_p, C.c_int
@@ -206,6 +208,8 @@ class MiganLib:
         L.comodgan_forward_samples.argtypes = [vp, vp, vp, vp, ci, ci, C.c_float, ci, vp, vp, C.c_size_t, vp]
         L.comodgan_forward_samples_timed.argtypes = [vp, vp, vp, vp, ci, ci, C.c_float, ci, vp, vp, C.c_size_t, vp, fp, ci]
         L.comodgan_debug_tensor_samples.argtypes = [vp, ci, ci, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64), C.POINTER(ci)]
+        L.comodgan_set_fp16_blocks.argtypes = [vp, ci, ci]
+        L.comodgan_get_fp16_blocks.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
         L.migan_last_error.restype = C.c_char_p
         L.migan_last_kernel.restype = C.c_char_p
         L.migan_nan_policy.restype = C.c_char_p
@@ -216,7 +220,7 @@ class MiganLib:
         if not allow_test_backend and L.migan_backend().decode() != PRODUCT_BACKEND:
             raise MiganError(f"{self.path} reports backend {L.migan_backend().decode()!r}, not {PRODUCT_BACKEND!r}: only the gfx950 HIP "
                              f"library is a product backend (the CPU emulator build is test infrastructure)")
-        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS:
+        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + FP16_EXPORTS:
             if name not in ("migan_last_error", "migan_last_kernel", "migan_nan_policy", "migan_backend", "migan_gemm_variant", "migan_tuning_key"):
                 getattr(L, name).restype = ci
 
@@ -573,6 +577,16 @@ class CoModGANHandle:
     def set_truncation_cutoff(self, cutoff: Optional[int]) -> None:
         """None: truncation_psi applies to every row of ws; n: to rows [0, n) only (stylegan.py:432-437)"""
         self.lib.check(self.lib.lib.comodgan_set_truncation_cutoff(self._h, -1 if cutoff is None else int(cutoff)))
+
+    def set_fp16_blocks(self, encoder_before_res: Optional[int], synthesis_after_res: Optional[int]) -> None:
+        """the reference's use_fp16_before_res / use_fp16_after_res (comodgan.py:148,384); None marks no block.  Before sizing the workspace."""
+        self.lib.check(self.lib.lib.comodgan_set_fp16_blocks(self._h, -1 if encoder_before_res is None else int(encoder_before_res),
+                                                             -1 if synthesis_after_res is None else int(synthesis_after_res)))
+
+    def fp16_blocks(self) -> Tuple[Optional[int], Optional[int]]:
+        e, s = C.c_int(), C.c_int()
+        self.lib.check(self.lib.lib.comodgan_get_fp16_blocks(self._h, C.byref(e), C.byref(s)))
+        return (None if e.value < 0 else e.value, None if s.value < 0 else s.value)
 
     def set_debug(self, keep: bool) -> None:
         self.lib.check(self.lib.lib.comodgan_set_debug(self._h, 1 if keep else 0))
