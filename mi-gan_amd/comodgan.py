@@ -7,7 +7,8 @@ scripts/demo.py:95-106 assembles ``comodgan-256|512`` -- keeps the reference's c
 (include/comodgan_hip.h).  PyTorch is used for device memory, streams and drawing ``z`` / the per-pixel noise of
 ``noise_mode='random'`` only.  There is no CPU or pure-PyTorch path: a CPU tensor, a missing libmigan_hip.so or
 a missing GPU raises.  ``Encoder(use_fp16_before_res=)`` / ``Synthesis(use_fp16_after_res=)`` mark half-precision blocks as
-in the reference: their 3x3 convolutions take fp16 operands (fp32 accumulation and storage).  Not supported: autograd,
+in the reference: their 3x3 convolutions take fp16 operands (fp32 accumulation and storage; ``Generator.set_fp16_storage()``
+makes those blocks store their activations in fp16 as well, as the reference does).  Not supported: autograd,
 ``c`` (class conditioning: c_dim = 0 in every reference config), ``truncation_cutoff``, ``return_intermediate_outs``.
 """
 from __future__ import annotations
@@ -156,6 +157,8 @@ class Generator(nn.Module):
         self._refreeze = True        # the handle has not been told yet
         self._cutoff: Optional[int] = None   # truncation_cutoff the handle was last told
         self._fp16: Tuple[Optional[int], Optional[int]] = (None, None)   # half-precision blocks the handle was last told
+        self._fp16_storage = False       # set_fp16_storage(): the marked blocks keep their activations in fp16
+        self._fp16_storage_told = False  # what the handle was last told
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._invalidate())
 
     # ------------------------------------------------------------------ plumbing
@@ -166,6 +169,13 @@ class Generator(nn.Module):
         write) call ``freeze_weights()`` again, or ``freeze_weights(False)`` to go back to re-preparing every forward."""
         self._frozen = bool(frozen)
         self._refreeze = True
+        return self
+
+    def set_fp16_storage(self, on: bool = True) -> "Generator":
+        """Opt-in beside ``use_fp16_before_res`` / ``use_fp16_after_res``: the blocks they mark store their activations in fp16, as
+        the reference's half-precision path does (half the workspace and the activation traffic of those blocks; arithmetic stays
+        fp32 on converted values).  No effect while no block is marked.  Honoured by forward, forward_samples and forward_timed."""
+        self._fp16_storage = bool(on)
         return self
 
     def _invalidate(self) -> None:
@@ -201,6 +211,7 @@ class Generator(nn.Module):
             self._refreeze = True
             self._cutoff = None
             self._fp16 = (None, None)
+            self._fp16_storage_told = False
         # half-precision blocks (the reference's constructor arguments, kept as attributes of the two sub-modules): their 3x3
         # convolutions run with single fp16 operands.  Part of the plan, so the handle is told before the workspace is sized.
         fp16 = (_fp16_res("use_fp16_before_res", self.encoder.use_fp16_before_res),
@@ -208,6 +219,9 @@ class Generator(nn.Module):
         if fp16 != self._fp16:
             self._handle.set_fp16_blocks(*fp16)
             self._fp16 = fp16
+        if self._fp16_storage != self._fp16_storage_told:        # (part of the plan as well)
+            self._handle.set_fp16_storage(self._fp16_storage)
+            self._fp16_storage_told = self._fp16_storage
         tensors = self._tensors()
         ptrs = tuple(t.data_ptr() for t in tensors)
         if self._dirty or ptrs != self._bound:

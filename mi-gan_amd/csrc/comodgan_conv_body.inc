@@ -1,6 +1,7 @@
-// Body of cm_conv_kernel / cm_conv_f16_kernel (comodgan_kernels.hpp, where the template parameters are described): included
-// inside both kernel templates, which define F16 (false: error-compensated fp16 pairs, three MFMAs per product; true: the
-// single-plane form, one MFMA per product).  `p` is the kernel's CmConvArgs.
+// Body of cm_conv_kernel / cm_conv_f16_kernel / cm_conv_h_kernel (comodgan_kernels.hpp, where the template parameters are
+// described): included inside the three kernel templates, which define F16 (false: error-compensated fp16 pairs, three MFMAs per
+// product; true: the single-plane form, one MFMA per product) and the element types of the activation tensors, XH (p.x holds
+// _Float16) and YH (p.y and p.skip hold _Float16); both false in the first two kernels.  `p` is the kernel's CmConvArgs.
   MIGAN_DYN_SMEM(smem);
   constexpr int MT = 64 * MTI, GW = 16, GH = MT / GW, WROWS = 32 * MTI;
   constexpr int WCOLS = NT / 2, NTI = WCOLS / 32;
@@ -31,6 +32,8 @@
   constexpr int b_buf = NT * PB;
 
   const float* __restrict__ xb = p.x + (size_t)b * p.H * p.W * p.CI;
+  // fp16 storage: the same tensor, two bytes per element (the pointers of CmConvArgs are reinterpreted)
+  [[maybe_unused]] const unsigned short* __restrict__ xbh = reinterpret_cast<const unsigned short*>(p.x) + (size_t)b * p.H * p.W * p.CI;
   const float* __restrict__ sab = p.sa ? p.sa + (size_t)b * p.CI : nullptr;
   const unsigned w_plane_bytes = (unsigned)(9 * p.CI * p.CO) * 2u;     // bytes of one weight plane (< 2^23)
   [[maybe_unused]] const int total = nck * p.ntaps;            // generic tap list only
@@ -61,12 +64,19 @@
     const int iy = iy0 + py, ix = ix0 + px;
     goff[k] = (q < npix && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W) ? (iy * p.W + ix) * p.CI + c4 * 4 : -1;
   }
-  f4 areg[NIA];
+  // XH: an item is four halves, one 8-byte load; the prefetch registers keep the raw halves (half the registers) and store_a
+  // widens them, so the conversions sit in the staging step with the scaling, outside the tap loop
+  typename Io<XH ? 2 : 0>::raw4 areg[NIA];
   auto load_a = [&](int c) {
 #pragma unroll
     for (int k = 0; k < NIA; ++k) {
-      areg[k] = f4{0.f, 0.f, 0.f, 0.f};
-      if (goff[k] >= 0) areg[k] = ld4(xb + (size_t)(unsigned)goff[k] + c * KC);
+      if constexpr (XH) {
+        areg[k] = u2v{0u, 0u};
+        if (goff[k] >= 0) areg[k] = *reinterpret_cast<const u2v*>(xbh + (size_t)(unsigned)goff[k] + c * KC);
+      } else {
+        areg[k] = f4{0.f, 0.f, 0.f, 0.f};
+        if (goff[k] >= 0) areg[k] = ld4(xb + (size_t)(unsigned)goff[k] + c * KC);
+      }
     }
   };
   auto store_a = [&](int c) {
@@ -77,7 +87,7 @@
       const int q = (tid + k * 256) / QK;
       if (q < npix) {
         u2v h1, h2;
-        split2_f16(areg[k] * sc, h1, h2);
+        split2_f16(Io<XH ? 2 : 0>::cvt(areg[k]) * sc, h1, h2);
         char* dst = a_s + q * PB + c4 * 8;
         *reinterpret_cast<u2v*>(dst) = h1;
         if constexpr (!F16) *reinterpret_cast<u2v*>(dst + RB) = h2;
@@ -337,7 +347,11 @@
           sk[g] = f4{0.f, 0.f, 0.f, 0.f};
           if (!raw_out && ok[g]) {
             if (p.noise) nz[g] = p.noise[(size_t)b * p.noise_bstride + (size_t)oy * p.WO + ox];
-            if (p.skip) sk[g] = ld4once(p.skip + o[g]);
+            if constexpr (YH) {
+              if (p.skip) sk[g] = Io<2>::cvt(MIGAN_LOAD_NT(reinterpret_cast<const u2v*>(reinterpret_cast<const unsigned short*>(p.skip) + o[g])));
+            } else {
+              if (p.skip) sk[g] = ld4once(p.skip + o[g]);
+            }
           }
         }
 #pragma unroll
@@ -350,7 +364,9 @@
             v = act4(v + eq_bias);
             if (p.skip) v = v + sk[g];
           }
-          st4o(p.y + o[g], v);
+          // YH: four halves, rounded to nearest even, one 8-byte store
+          if constexpr (YH) MIGAN_STORE_NT(reinterpret_cast<u2v*>(reinterpret_cast<unsigned short*>(p.y) + o[g]), (u2v{MIGAN_PACK_F16(v.x, v.y), MIGAN_PACK_F16(v.z, v.w)}));
+          else st4o(p.y + o[g], v);
         }
       }
     }

@@ -8,6 +8,7 @@
 #include "../../include/comodgan_hip.h"
 #include "../../include/comodgan_samples_hip.h"
 #include "../../include/comodgan_fp16_hip.h"
+#include "../../include/comodgan_fp16_storage_hip.h"
 
 namespace migan {
 
@@ -25,12 +26,16 @@ struct CmDebugTensor {
   size_t offset = 0;
   int64_t shape[4] = {0, 0, 0, 0};
   int ndim = 0;
+  int dtype = COMODGAN_DTYPE_F32;    // element type in the workspace (comodgan_debug_tensor_dtype)
 };
 
 typedef void (*CmConvFn)(const CmConvArgs);
-struct CmConvEntry { int NT, KC, nine, MTI; CmConvFn fn; const char* name; int up4 = 0, f16 = 0; };
+// io: element types of the activation tensors (CM_IO_*); the fp16 forms exist for the single-plane kernel only
+enum : int { CM_IO_F32 = 0, CM_IO_HH = 1, CM_IO_HF = 2 };       // fp32 in and out / fp16 in and out / fp16 in, fp32 out
+struct CmConvEntry { int NT, KC, nine, MTI; CmConvFn fn; const char* name; int up4 = 0, f16 = 0, io = CM_IO_F32; };
 #define CM_CONV_ENTRY(NT, KC, NIA, NINE, MTI) {NT, KC, NINE, MTI, cm_conv_kernel<NT, KC, NIA, NINE, MTI>, "migan::cm_conv_kernel<" #NT ", " #KC ", " #NIA ", " #NINE ", " #MTI ", false>"}
 #define CM_CONV_F16_ENTRY(NT, KC, NIA, NINE, MTI, UP4) {NT, KC, NINE, MTI, cm_conv_f16_kernel<NT, KC, NIA, NINE, MTI, UP4>, "migan::cm_conv_f16_kernel<" #NT ", " #KC ", " #NIA ", " #NINE ", " #MTI ", " #UP4 ">", UP4, 1}
+#define CM_CONV_H_ENTRY(NT, KC, NIA, NINE, MTI, UP4, YH) {NT, KC, NINE, MTI, cm_conv_h_kernel<NT, KC, NIA, NINE, MTI, UP4, YH>, "migan::cm_conv_h_kernel<" #NT ", " #KC ", " #NIA ", " #NINE ", " #MTI ", " #UP4 ", " #YH ">", UP4, 1, YH ? CM_IO_HH : CM_IO_HF}
 inline const std::vector<CmConvEntry>& cm_conv_table() {
   static const std::vector<CmConvEntry> t = {
       // 8 x 16 pixel tiles (MTI 2), 64 / 128 output channels: nine-tap unrolled K loop (plain: 10x18-pixel tile, 6 items per thread;
@@ -49,12 +54,21 @@ inline const std::vector<CmConvEntry>& cm_conv_table() {
       CM_CONV_F16_ENTRY(64, 32, 6, false, 2, false), CM_CONV_F16_ENTRY(128, 32, 6, false, 2, false),
       CM_CONV_F16_ENTRY(256, 32, 11, true, 4, false), CM_CONV_F16_ENTRY(256, 16, 18, true, 4, false), CM_CONV_F16_ENTRY(256, 32, 11, false, 4, false),
       CM_CONV_F16_ENTRY(64, 32, 6, true, 2, true), CM_CONV_F16_ENTRY(128, 32, 6, true, 2, true),
+      // the single-plane form on fp16 activation storage, fp16 in and out: one row per row above (a later half-precision block
+      // reaches every tile form) ...
+      CM_CONV_H_ENTRY(64, 32, 6, true, 2, false, true), CM_CONV_H_ENTRY(128, 32, 6, true, 2, false, true),
+      CM_CONV_H_ENTRY(64, 16, 9, true, 2, false, true), CM_CONV_H_ENTRY(128, 16, 9, true, 2, false, true),
+      CM_CONV_H_ENTRY(64, 32, 6, false, 2, false, true), CM_CONV_H_ENTRY(128, 32, 6, false, 2, false, true),
+      CM_CONV_H_ENTRY(256, 32, 11, true, 4, false, true), CM_CONV_H_ENTRY(256, 16, 18, true, 4, false, true), CM_CONV_H_ENTRY(256, 32, 11, false, 4, false, true),
+      CM_CONV_H_ENTRY(64, 32, 6, true, 2, true, true), CM_CONV_H_ENTRY(128, 32, 6, true, 2, true, true),
+      // ... and fp16 in, fp32 out: only the strided conv1 of the last half-precision encoder block
+      CM_CONV_H_ENTRY(64, 16, 9, true, 2, false, false), CM_CONV_H_ENTRY(128, 16, 9, true, 2, false, false), CM_CONV_H_ENTRY(256, 16, 18, true, 4, false, false),
   };
   return t;
 }
-inline const CmConvEntry& cm_pick_conv(int NT, int KC, bool nine, int MTI, bool up4 = false, bool f16 = false) {
+inline const CmConvEntry& cm_pick_conv(int NT, int KC, bool nine, int MTI, bool up4 = false, bool f16 = false, int io = CM_IO_F32) {
   for (const auto& e : cm_conv_table())
-    if (e.NT == NT && e.KC == KC && (e.nine != 0) == nine && e.MTI == MTI && (e.up4 != 0) == up4 && (e.f16 != 0) == f16) return e;
+    if (e.NT == NT && e.KC == KC && (e.nine != 0) == nine && e.MTI == MTI && (e.up4 != 0) == up4 && (e.f16 != 0) == f16 && e.io == io) return e;
   throw Error(MIGAN_EINVAL, "internal: no cm_conv_kernel instantiation for this tile");
 }
 
@@ -100,8 +114,9 @@ struct CmConvGeo {
   double flops, bytes;
 };
 // f16: the single-plane form (a layer of a half-precision block): same tiles and tap lists on the narrower LDS rows.
+// io: the element types of its activation tensors (fp16 storage); they change the kernel symbol and the reported bytes only.
 inline CmConvGeo cm_conv_geometry(int mode, int phase, int H, int Wd, int HO, int WO, int ci, int co, int B, const CmForced& forced,
-                                  bool f16 = false) {
+                                  bool f16 = false, int io = CM_IO_F32) {
   CmConvGeo g = CmConvGeo();      // all zero, the padding of the argument struct included
   CmConvArgs& a = g.a;
   const int ey = phase >> 1, ex = phase & 1;
@@ -171,10 +186,15 @@ inline CmConvGeo cm_conv_geometry(int mode, int phase, int H, int Wd, int HO, in
                                 : 2.0 * ci * co * a.ntaps * (double)a.GHn * a.GWn;
   g.bytes = mode == CM_CONV_UP4 ? 4.0 * ((double)ci * H * Wd + (double)co * (2.0 * H + 1) * (2.0 * Wd + 1))
                                 : 4.0 * ((double)ci * H * Wd + (double)co * a.GHn * a.GWn);
+  if (io != CM_IO_F32) {
+    const double xe = 2.0, ye = io == CM_IO_HH ? 2.0 : 4.0;
+    g.bytes = mode == CM_CONV_UP4 ? xe * ci * H * Wd + ye * co * (2.0 * H + 1) * (2.0 * Wd + 1) : xe * ci * H * Wd + ye * co * a.GHn * a.GWn;
+  }
   const bool nine = a.ntaps == 9;
   MIGAN_CHECK(!nine || (ci / KC) % 2 == 0, MIGAN_EINVAL, "internal: the nine-tap kernel walks channel chunks in pairs");
   MIGAN_CHECK(nine || KC == 32, MIGAN_EINVAL, "internal: no generic-tap-list kernel with 16-channel chunks");
-  g.kernel = &cm_pick_conv(NT, KC, nine, MTI, mode == CM_CONV_UP4, f16);
+  MIGAN_CHECK(io == CM_IO_F32 || f16, MIGAN_EINVAL, "internal: fp16 storage outside a half-precision block");
+  g.kernel = &cm_pick_conv(NT, KC, nine, MTI, mode == CM_CONV_UP4, f16, io);
   return g;
 }
 
@@ -217,9 +237,10 @@ struct CmPlanKey {
   CmForced forced;
   int samples = 1;                   // completions per image (comodgan_forward_samples); batch counts images
   int fp16_enc = -1, fp16_syn = -1;  // comodgan_set_fp16_blocks: which layers run the single-plane convolution
+  bool fp16_storage = false;         // comodgan_set_fp16_storage: those blocks keep their activations in fp16
   bool operator==(const CmPlanKey& o) const {
     return batch == o.batch && samples == o.samples && debug == o.debug && trunc_cutoff == o.trunc_cutoff && forced == o.forced &&
-           fp16_enc == o.fp16_enc && fp16_syn == o.fp16_syn;
+           fp16_enc == o.fp16_enc && fp16_syn == o.fp16_syn && fp16_storage == o.fp16_storage;
   }
 };
 
@@ -240,6 +261,8 @@ struct comodgan_handle {
   int trunc_cutoff = -1;       // comodgan_set_truncation_cutoff: -1 = None (every row of ws truncated), else rows [0, cutoff)
   // comodgan_set_fp16_blocks: the reference's use_fp16_before_res / use_fp16_after_res, -1 = None (no half-precision block)
   int fp16_enc = -1, fp16_syn = -1;
+  // comodgan_set_fp16_storage: the marked blocks store their activations as _Float16 (no effect while no block is marked)
+  bool fp16_storage = false;
   // comodgan_assume_static_weights: skip the per-forward weight preparation while nothing it depends on has changed
   bool static_weights = false;
   const void* prepared_ws = nullptr;
@@ -390,9 +413,15 @@ struct CmWalk {
   }
   const float* weight(int slot) const { return sizing ? nullptr : h.slots[slot].ptr; }
   static unsigned grid1d(size_t items) { return (unsigned)std::min<size_t>((items + kThreads - 1) / kThreads, 1u << 20); }
-  void reg_debug(const char* name, const char* suffix, const float* p, std::initializer_list<int64_t> shp) {
+  // fp16 storage (comodgan_set_fp16_storage): the activation tensors of a half-precision block hold _Float16.  The pointers stay
+  // float* (the kernels reinterpret them); what is typed is passed along as a flag, `half`, next to the pointer.
+  bool enc_h(int res) const { return h.fp16_storage && res > 4 && h.fp16_enc >= 0 && res > h.fp16_enc; }    // encoder block b<res>
+  bool syn_h(int res) const { return h.fp16_storage && res > 4 && h.fp16_syn >= 0 && res > h.fp16_syn; }    // synthesis block b<res>
+  static size_t esz(bool half) { return half ? 2 : 4; }
+  void reg_debug(const char* name, const char* suffix, const float* p, std::initializer_list<int64_t> shp, bool half = false) {
     if (!sizing || !h.debug) return;
     CmDebugTensor t;
+    t.dtype = half ? COMODGAN_DTYPE_F16 : COMODGAN_DTYPE_F32;
     t.name = std::string(name) + suffix;
     t.offset = (size_t)(reinterpret_cast<const char*>(p) - base);
     t.ndim = (int)shp.size();
@@ -400,9 +429,9 @@ struct CmWalk {
     for (auto v : shp) t.shape[i++] = v;
     h.debug_tensors.push_back(t);
   }
-  float* act_out(const char* name, float* pingpong, int res, int c) {
-    float* p = h.debug ? alloc((size_t)res * res * c * nb * 4) : pingpong;
-    reg_debug(name, "", p, {nb, res, res, c});
+  float* act_out(const char* name, float* pingpong, int res, int c, bool half = false) {
+    float* p = h.debug ? alloc((size_t)res * res * c * nb * esz(half)) : pingpong;
+    reg_debug(name, "", p, {nb, res, res, c}, half);
     return p;
   }
   template <class Kernel, class Args>
@@ -471,9 +500,10 @@ struct CmWalk {
   // 3x3 convolution net.convs[index] from xin ([H][Wd]) to out ([HO][WO]).  raw: a transposed-convolution launch, cm_fir_kernel<1> finishes the layer
   // (bias, noise, activation).  A modulated layer takes its input scales and demodulation coefficients from its style job.
   void conv(int index, const char* suffix, int mode, int phase, const float* xin, float* out, int H, int Wd, int HO, int WO,
-            const CmNoise& nz = CmNoise{}, bool raw = false) {
+            const CmNoise& nz = CmNoise{}, bool raw = false, bool xh = false, bool yh = false) {
     const CmConvL& L = net.convs[index];
-    CmConvGeo g = cm_conv_geometry(mode, phase, H, Wd, HO, WO, L.ci, L.co, nb, forced, L.f16);
+    MIGAN_CHECK(xh || !yh, MIGAN_EINVAL, "internal: no convolution from fp32 to fp16 storage");
+    CmConvGeo g = cm_conv_geometry(mode, phase, H, Wd, HO, WO, L.ci, L.co, nb, forced, L.f16, xh ? (yh ? CM_IO_HH : CM_IO_HF) : CM_IO_F32);
     CmConvArgs& a = g.a;
     a.x = xin; a.y = out; a.wsplit = conv_ws[index].planes;
     if (L.job >= 0) { a.sa = job_ws[L.job].sa; a.coef = job_ws[L.job].coef; }
@@ -497,18 +527,25 @@ struct CmWalk {
   // ---------------------------------------------------------------- buffers
   void buffers() {
     const int R = h.cfg.resolution;
-    size_t max_act = 0, max_tmp = 0;
+    // the ping-pong buffers serve the encoder (batch N) and the synthesis network (batch B >= N): sized for the largest tenant in
+    // BYTES (with fp16 storage a tenant's element size follows its block: encoder() / synthesis()); the skip tensors feat[] are the
+    // encoder's, at batch N, each of its own type.  Without fp16 storage every term is the synthesis network's, at 4 bytes.
+    size_t max_a = 0, max_b = 0, max_tmp = 0;
     for (int res = 4; res <= R; res *= 2) {
-      max_act = std::max(max_act, (size_t)res * res * h.channels(res));
-      max_tmp = std::max(max_tmp, (size_t)(res + 1) * (res + 1) * h.channels(res));
+      const size_t act = (size_t)res * res * h.channels(res), raw = (size_t)(res + 1) * (res + 1) * h.channels(res);
+      // bufA: the input of encoder block b<res> and the x0 of synthesis block b<res> (res 4: x4); bufB: the synthesis network's
+      // alone, the x1 of block b<res> (res 4: the b4 convolution's output)
+      max_a = std::max(max_a, std::max(act * N * esz(enc_h(res)), act * B * esz(syn_h(res))));
+      max_b = std::max(max_b, act * B * esz(syn_h(res)));
+      // tmp: the FIR-down output of encoder block b<res>; the raw transposed convolution of synthesis block b<res> (fp32 in the
+      // first half-precision block, whose input is fp32)
+      max_tmp = std::max(max_tmp, std::max(raw * N * esz(enc_h(res)), raw * B * esz(syn_h(res) && syn_h(res / 2))));
     }
-    // the ping-pong buffers serve the encoder (batch N) and the synthesis network (batch B >= N): sized for the larger tenant;
-    // the skip tensors feat[] are the encoder's, at batch N
-    bufA = h.debug ? nullptr : alloc(max_act * B * 4);
-    bufB = h.debug ? nullptr : alloc(max_act * B * 4);
-    tmp = alloc(max_tmp * B * 4);
+    bufA = h.debug ? nullptr : alloc(max_a);
+    bufB = h.debug ? nullptr : alloc(max_b);
+    tmp = alloc(max_tmp);
     for (float*& im : img) im = h.debug ? nullptr : alloc((size_t)3 * R * R * B * 4);
-    for (int res = R; res >= 4; res /= 2) feat[ilog2(res)] = alloc((size_t)res * res * h.channels(res) * N * 4);
+    for (int res = R; res >= 4; res /= 2) feat[ilog2(res)] = alloc((size_t)res * res * h.channels(res) * N * esz(enc_h(res)));
   }
 
   // ---------------------------------------------------------------- mapping (stylegan.py:396-439)
@@ -557,26 +594,43 @@ struct CmWalk {
     const int R = h.cfg.resolution, c0 = h.channels(R), c4 = h.channels(4);
     nb = N;
     w0 = alloc((size_t)N * h.cfg.w0_dim * 4);
-    float* cur = h.debug ? alloc((size_t)R * R * c0 * N * 4) : bufA;
+    // fp16 storage: the input of a half-precision block is fp16 (the marking is monotone from the top), and so are its skip tensor
+    // and its FIR-down output; its conv1 writes what the next block reads
+    bool cur_h = enc_h(R);
+    float* cur = h.debug ? alloc((size_t)R * R * c0 * N * esz(cur_h)) : bufA;
+    reg_debug(net.fromrgb.name.c_str(), "", cur, {N, R, R, c0}, cur_h);
     CmFromRgbArgs a{};
     a.x = x; a.w = weight(net.fromrgb.w); a.b = weight(net.fromrgb.b); a.y = cur; a.wgain = 0.5f; a.B = N; a.R = R; a.C = c0;
+    if (cur_h)
+      emit(net.fromrgb.name.c_str(), "", "migan::cm_fromrgb_h_kernel", 2.0 * 4 * c0 * R * R, 0, (4.0 * 4 + 2.0 * c0) * R * R, cm_fromrgb_h_kernel, a,
+           grid1d((size_t)N * R * R * (c0 / 4) / 8), 0);
+    else
     emit(net.fromrgb.name.c_str(), "", "migan::cm_fromrgb_kernel", 2.0 * 4 * c0 * R * R, 0, 4.0 * (4 + c0) * R * R, cm_fromrgb_kernel, a,
          grid1d((size_t)N * R * R * (c0 / 4) / 8), 0);      // 8 pixels per thread: the weights are read once per thread
     for (const CmEncBlock& blk : net.enc) {
       const CmConvL& conv0 = net.convs[blk.conv0];
       const CmConvL& conv1 = net.convs[blk.conv1];
       const int res = blk.res, c = conv0.co;
+      const bool bh = enc_h(res), oh = enc_h(res / 2);
+      MIGAN_CHECK(cur_h == bh, MIGAN_EINVAL, "internal: encoder block input type");
       float* f = feat[ilog2(res)];
-      reg_debug(conv0.name.c_str(), "", f, {N, res, res, c});
-      conv(blk.conv0, "", CM_CONV_NORMAL, 0, cur, f, res, res, res, res);
+      reg_debug(conv0.name.c_str(), "", f, {N, res, res, c}, bh);
+      conv(blk.conv0, "", CM_CONV_NORMAL, 0, cur, f, res, res, res, res, CmNoise{}, false, bh, bh);
       CmFirArgs a{};
       a.x = f; a.y = tmp; a.B = N; a.H = res; a.W = res; a.C = c; a.HO = res + 1; a.WO = res + 1; a.pad = 2; a.fs = 0.125f;
+      if (bh)
+        emit(conv1.name.c_str(), ".fir", "migan::cm_fir_h_kernel<0, true, true, false>", 2.0 * 16 * c * (res + 1) * (res + 1), 0,
+             2.0 * c * (2.0 * res * res + 2 * res + 1), cm_fir_h_kernel<0, true, true, false>, a,
+             grid1d((size_t)N * cdiv(res + 1, 2) * cdiv(res + 1, 4) * (c / 4)), 0);
+      else
       emit(conv1.name.c_str(), ".fir", "migan::cm_fir_kernel<0>", 2.0 * 16 * c * (res + 1) * (res + 1), 0, 4.0 * c * (2.0 * res * res + 2 * res + 1),
            cm_fir_kernel<0>, a, grid1d((size_t)N * cdiv(res + 1, 2) * cdiv(res + 1, 4) * (c / 4)), 0);
-      float* out = act_out(conv1.name.c_str(), bufA, res / 2, conv1.co);
-      conv(blk.conv1, "", CM_CONV_DOWN, 0, tmp, out, res + 1, res + 1, res / 2, res / 2);
-      cur = out;
+      reg_debug(conv1.name.c_str(), ".fir", tmp, {N, res + 1, res + 1, c}, bh);       // (the shared tmp buffer: the last writer's data)
+      float* out = act_out(conv1.name.c_str(), bufA, res / 2, conv1.co, oh);
+      conv(blk.conv1, "", CM_CONV_DOWN, 0, tmp, out, res + 1, res + 1, res / 2, res / 2, CmNoise{}, false, bh, oh);
+      cur = out; cur_h = oh;
     }
+    MIGAN_CHECK(!cur_h, MIGAN_EINVAL, "internal: encoder.b4 reads fp32");
     const CmConvL& b4 = net.convs[net.enc_b4];
     reg_debug(b4.name.c_str(), "", feat[2], {N, 4, 4, c4});
     conv(net.enc_b4, "", CM_CONV_NORMAL, 0, cur, feat[2], 4, 4, 4, 4);
@@ -643,16 +697,42 @@ struct CmWalk {
   }
 
   // ---------------------------------------------------------------- synthesis (comodgan.py:395-420)
-  void torgb(const CmRgbL& L, const float* xin, int res, const float* prev, float* out) {
+  void torgb(const CmRgbL& L, const float* xin, int res, const float* prev, float* out, bool xh = false) {
     const int c = L.c;
     CmRgbArgs a{};
     a.x = xin; a.wm = job_ws[L.job].wm; a.bias = weight(L.b); a.img_prev = prev; a.img_out = out; a.B = B; a.H = res; a.W = res; a.C = c;
     const double fl = 2.0 * 3 * c * res * res, by = 4.0 * ((double)c * res * res + 3.75 * res * res);
     const auto grid_of = [&](int lpp) { return (unsigned)(((size_t)B * res * res * lpp + kThreads - 1) / kThreads); };
     const char* p = L.name.c_str();
+    if (xh) {        // the feature map is fp16; weights, running image and output are fp32
+      const double byh = 2.0 * c * res * res + 4.0 * 3.75 * res * res;
+      if (c <= 64) emit(p, "", "migan::cm_torgb_h_kernel<4>", fl, 0, byh, cm_torgb_h_kernel<4>, a, grid_of(4), 0);
+      else if (c <= 128) emit(p, "", "migan::cm_torgb_h_kernel<8>", fl, 0, byh, cm_torgb_h_kernel<8>, a, grid_of(8), 0);
+      else emit(p, "", "migan::cm_torgb_h_kernel<16>", fl, 0, byh, cm_torgb_h_kernel<16>, a, grid_of(16), 0);
+      return;
+    }
     if (c <= 64) emit(p, "", "migan::cm_torgb_kernel<4>", fl, 0, by, cm_torgb_kernel<4>, a, grid_of(4), 0);
     else if (c <= 128) emit(p, "", "migan::cm_torgb_kernel<8>", fl, 0, by, cm_torgb_kernel<8>, a, grid_of(8), 0);
     else emit(p, "", "migan::cm_torgb_kernel<16>", fl, 0, by, cm_torgb_kernel<16>, a, grid_of(16), 0);
+  }
+  // The FIR half of an up=2 layer on fp16 storage: xh / yh / sh = which of the raw tensor, the output and the encoder's skip tensor
+  // hold fp16 (not all false: that is cm_fir_kernel<1> / cm_fir_samples_kernel, launched by the caller as ever)
+  void fir_up_typed(const char* layer, const CmFirArgs& a, bool xh, bool yh, bool sh, double flops, double bytes, unsigned grid) {
+    CmFirSamplesArgs as{};
+    as.f = a; as.S = S;
+#define CM_FIR_UP_FORM(XH, YH, SH)                                                                                                  \
+  if (xh == XH && yh == YH && sh == SH) {                                                                                           \
+    if (S == 1) emit(layer, ".fir", "migan::cm_fir_h_kernel<1, " #XH ", " #YH ", " #SH ">", flops, 0, bytes, cm_fir_h_kernel<1, XH, YH, SH>, a, grid, 0); \
+    else emit(layer, ".fir", "migan::cm_fir_samples_h_kernel<" #XH ", " #YH ", " #SH ">", flops, 0, bytes, cm_fir_samples_h_kernel<XH, YH, SH>, as, grid, 0); \
+    return;                                                                                                                         \
+  }
+    CM_FIR_UP_FORM(false, false, true)       // an fp32 block above a half-precision encoder block
+    CM_FIR_UP_FORM(false, true, false)       // the first half-precision block: its raw tensor is fp32
+    CM_FIR_UP_FORM(false, true, true)
+    CM_FIR_UP_FORM(true, true, false)        // a later one
+    CM_FIR_UP_FORM(true, true, true)
+#undef CM_FIR_UP_FORM
+    throw Error(MIGAN_EINVAL, "internal: no FIR-up kernel reads an fp16 raw tensor into an fp32 block");
   }
   void synthesis() {
     static const char* const kPhase[4] = {".phase0", ".phase1", ".phase2", ".phase3"};
@@ -680,24 +760,33 @@ struct CmWalk {
     torgb(net.rgb_b4, xcur, 4, nullptr, (R == 4) ? y : im);
     const float* imprev = im;
     int flip = 1;
+    bool xcur_h = false;        // fp16 storage: the block input is fp16 from the second half-precision block on
     for (const CmSynBlock& blk : net.syn) {
       const CmConvL& conv0 = net.convs[blk.conv0];
       const CmConvL& conv1 = net.convs[blk.conv1];
       const int res = blk.res, co = conv0.co, hr = res / 2;
+      // fp16 storage: x0 and x1 of a half-precision block are fp16.  Its raw transposed convolution is, too, except in the first such
+      // block, whose input comes from an fp32 block: there the launches below are the operand-only mode's, fp32 in and out.
+      const bool bh = syn_h(res), sh = enc_h(res);
+      MIGAN_CHECK(!xcur_h || bh, MIGAN_EINVAL, "internal: synthesis block input type");
       // conv0: modulated transposed convolution (4 output phases) -> FIR + noise + bias + activation, + skip (comodgan.py:329-331)
       if (forced.up4)
-        conv(blk.conv0, ".phases", CM_CONV_UP4, 0, xcur, tmp, hr, hr, res + 1, res + 1, CmNoise{}, true);
+        conv(blk.conv0, ".phases", CM_CONV_UP4, 0, xcur, tmp, hr, hr, res + 1, res + 1, CmNoise{}, true, xcur_h, xcur_h);
       else
-        for (int ph = 0; ph < 4; ++ph) conv(blk.conv0, kPhase[ph], CM_CONV_UP, ph, xcur, tmp, hr, hr, res + 1, res + 1, CmNoise{}, true);
+        for (int ph = 0; ph < 4; ++ph) conv(blk.conv0, kPhase[ph], CM_CONV_UP, ph, xcur, tmp, hr, hr, res + 1, res + 1, CmNoise{}, true, xcur_h, xcur_h);
+      reg_debug(conv0.name.c_str(), ".raw", tmp, {B, res + 1, res + 1, co}, xcur_h);     // (the shared tmp buffer: the last writer's data)
       const CmNoise nz0 = noise_of(conv0);
-      float* x0 = act_out(conv0.name.c_str(), bufA, res, co);
+      float* x0 = act_out(conv0.name.c_str(), bufA, res, co, bh);
       CmFirArgs a{};
       a.x = tmp; a.y = x0; a.skip = feat[ilog2(res)]; a.bias = weight(conv0.b); a.noise = nz0.plane;
       a.noise_strength = weight(conv0.noise_strength); a.noise_bstride = nz0.bstride;
       a.B = B; a.H = res + 1; a.W = res + 1; a.C = co; a.HO = res; a.WO = res; a.pad = 1; a.fs = 0.25f;
       const double fir_fl = 2.0 * 16 * co * res * res;
       const unsigned fir_grid = grid1d((size_t)B * (res / 2) * cdiv(res, 4) * (co / 4));
-      if (S == 1) {
+      if (xcur_h || bh || sh) {
+        fir_up_typed(conv0.name.c_str(), a, xcur_h, bh, sh, fir_fl,
+                     co * ((double)esz(xcur_h) * (res + 1.0) * (res + 1.0) + ((double)esz(bh) + (double)esz(sh) / S) * res * res), fir_grid);
+      } else if (S == 1) {
         emit(conv0.name.c_str(), ".fir", "migan::cm_fir_kernel<1>", fir_fl, 0, 4.0 * co * ((res + 1.0) * (res + 1.0) + 2.0 * res * res),
              cm_fir_kernel<1>, a, fir_grid, 0);
       } else {
@@ -708,13 +797,13 @@ struct CmWalk {
              4.0 * co * ((res + 1.0) * (res + 1.0) + (1.0 + 1.0 / S) * res * res), cm_fir_samples_kernel, as, fir_grid, 0);
       }
       const CmNoise nz1 = noise_of(conv1);
-      float* x1 = act_out(conv1.name.c_str(), bufB, res, co);
-      conv(blk.conv1, "", CM_CONV_NORMAL, 0, x0, x1, res, res, res, res, nz1);
+      float* x1 = act_out(conv1.name.c_str(), bufB, res, co, bh);
+      conv(blk.conv1, "", CM_CONV_NORMAL, 0, x0, x1, res, res, res, res, nz1, false, bh, bh);
       // img = upsample2d(img) + torgb(x) (comodgan.py:334-343)
       float* imo = (res == R) ? y : (h.debug ? alloc((size_t)3 * res * res * B * 4) : img[flip]);
       if (res != R) reg_debug(blk.name.c_str(), ".img", imo, {B, 3, res, res});
-      torgb(blk.rgb, x1, res, imprev, imo);
-      imprev = imo; flip ^= 1; xcur = x1;
+      torgb(blk.rgb, x1, res, imprev, imo, bh);
+      imprev = imo; flip ^= 1; xcur = x1; xcur_h = bh;
     }
   }
 
@@ -740,7 +829,7 @@ struct CmWalk {
 }  // namespace migan
 
 inline size_t comodgan_handle::ensure_planned(int batch, int samples) const {
-  const migan::CmPlanKey key{batch, trunc_cutoff, debug, migan::cm_read_forced(), samples, fp16_enc, fp16_syn};
+  const migan::CmPlanKey key{batch, trunc_cutoff, debug, migan::cm_read_forced(), samples, fp16_enc, fp16_syn, fp16_storage};
   if (!(key == planned)) {
     comodgan_handle* m = const_cast<comodgan_handle*>(this);      // the queries of the C ABI take a const handle; the plan is a cache
     m->planned = migan::CmPlanKey{};                              // (nothing planned if the walk throws)
@@ -981,6 +1070,35 @@ int comodgan_get_fp16_blocks(const comodgan_handle* h, int* encoder_before_res, 
   MIGAN_CHECK(h && encoder_before_res && synthesis_after_res, MIGAN_EINVAL, "null argument");
   *encoder_before_res = h->fp16_enc;
   *synthesis_after_res = h->fp16_syn;
+  MIGAN_API_END
+}
+
+int comodgan_set_fp16_storage(comodgan_handle* h, int on) {
+  MIGAN_API_BEGIN
+  MIGAN_CHECK(h, MIGAN_EINVAL, "null handle");
+  h->fp16_storage = on != 0;               // (part of the plan's key; the prepared weight planes sit at the head of the workspace in both modes)
+  MIGAN_API_END
+}
+
+int comodgan_get_fp16_storage(const comodgan_handle* h, int* on) {
+  MIGAN_API_BEGIN
+  MIGAN_CHECK(h && on, MIGAN_EINVAL, "null argument");
+  *on = h->fp16_storage ? 1 : 0;
+  MIGAN_API_END
+}
+
+int comodgan_debug_tensor_dtype(const comodgan_handle* h, int batch, int samples, const char* layer, int* dtype) {
+  MIGAN_API_BEGIN
+  MIGAN_CHECK(h && layer && dtype && batch > 0, MIGAN_EINVAL, "null argument or empty batch");
+  MIGAN_CHECK(h->debug, MIGAN_ESTATE, "comodgan_set_debug(h, 1) first");
+  comodgan_check_samples(batch, samples);
+  h->ensure_planned(batch, samples);
+  for (const auto& t : h->debug_tensors) {
+    if (t.name != layer) continue;
+    *dtype = t.dtype;
+    return MIGAN_OK;
+  }
+  throw migan::Error(MIGAN_EINVAL, std::string("no such debug tensor: ") + layer);
   MIGAN_API_END
 }
 

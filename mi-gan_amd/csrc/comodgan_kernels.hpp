@@ -8,6 +8,8 @@
 // Everything that is a dense contraction (the 3x3 convolutions, 99 % of the 240 GFLOP per 512x512 image) runs
 // on the matrix cores as an implicit GEMM (cm_conv_kernel); the rest are streaming kernels:
 //
+//   cm_*_h_kernel       the typed twins of the conv / FIR / FromRGB / ToRGB kernels: _Float16 activation tensors in the blocks a
+//                       caller has declared half precision, with comodgan_set_fp16_storage on (fp32 arithmetic on converted values)
 //   cm_conv_kernel      3x3 convolution, NHWC, M = 8x16 output-grid pixels, N = 64/128 output channels, K = taps x Cin.
 //                       A operand: the input halo tile of a 32-channel chunk is staged ONCE in LDS (scaled by the
 //                       per-sample style = the "scale activations" form of weight modulation, stylegan.py:171-182,
@@ -112,13 +114,21 @@ MIGAN_DEVICE MIGAN_INLINE int cm_pixel_of_row(int r) {
 // The kernel's text is comodgan_conv_body.inc, compiled into two kernel templates: F16 is a constant of the enclosing kernel.
 template <int NT, int KC, int NIA, bool NINE, int MTI, bool UP4 = false>
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, ((MTI * NT * (UP4 ? 4 : 1) > 512) ? 1 : 2)) cm_conv_kernel(const CmConvArgs p) {
-  constexpr bool F16 = false;
+  constexpr bool F16 = false, XH = false, YH = false;
 #include "comodgan_conv_body.inc"
 }
 // The single-plane form: symbols of their own, so that the two-plane launches keep their names and their code.
 template <int NT, int KC, int NIA, bool NINE, int MTI, bool UP4 = false>
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, ((MTI * NT * (UP4 ? 4 : 1) > 512) ? 1 : 2)) cm_conv_f16_kernel(const CmConvArgs p) {
-  constexpr bool F16 = true;
+  constexpr bool F16 = true, XH = false, YH = false;
+#include "comodgan_conv_body.inc"
+}
+// The single-plane form on fp16 activation storage (comodgan_set_fp16_storage): p.x holds _Float16, and so do p.y and p.skip
+// when YH (the strided conv1 of the last half-precision encoder block hands fp32 to an fp32 block: YH = false).  Symbols of
+// their own again.  Why no stored value overflows: include/comodgan_fp16_storage_hip.h.
+template <int NT, int KC, int NIA, bool NINE, int MTI, bool UP4, bool YH>
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, ((MTI * NT * (UP4 ? 4 : 1) > 512) ? 1 : 2)) cm_conv_h_kernel(const CmConvArgs p) {
+  constexpr bool F16 = true, XH = true;
 #include "comodgan_conv_body.inc"
 }
 
@@ -502,6 +512,30 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_fromrgb_kernel(const CmFromRgbA
   }
 }
 
+// The same layer writing _Float16 (encoder block b<R> is half precision and fp16 storage is on): values are bounded by the
+// +-256 clamp, rounded to nearest even, 8 bytes per channel quad.  A symbol of its own; p.y is reinterpreted.
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_fromrgb_h_kernel(const CmFromRgbArgs p) {
+  const int qn = p.C >> 2;
+  const int c4 = (int)threadIdx.x % qn;
+  const int ppb = 256 / qn;
+  const size_t plane = (size_t)p.R * p.R;
+  const size_t npix = (size_t)p.B * plane;
+  f4 w[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) w[j] = ld4(p.w + (c4 * 4 + j) * 4) * p.wgain;
+  const f4 bias = ld4(p.b + c4 * 4);
+  unsigned short* yh = reinterpret_cast<unsigned short*>(p.y);
+  for (size_t pix = (size_t)blockIdx.x * ppb + threadIdx.x / qn; pix < npix; pix += (size_t)gridDim.x * ppb) {
+    const size_t bi = pix / plane, rem = pix % plane;
+    const float* xp = p.x + bi * 4 * plane + rem;
+    const float x0 = xp[0], x1 = xp[plane], x2 = xp[2 * plane], x3 = xp[3 * plane];
+    f4 v;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = (x0 * w[j].x + x1 * w[j].y + x2 * w[j].z + x3 * w[j].w) + bias[j];
+    Io<2>::st(reinterpret_cast<char*>(yh + pix * p.C + c4 * 4), 0u, act4(v));
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // upfirdn2d with the separable [1,3,3,1] filter (taps [1,3,3,1] * fs per axis), up = down = 1, zero padding `pad` on
 // every side, NHWC: out[y][x] = sum_{a,b} f[a] f[b] in[y + a - pad][x + b - pad].  Each thread produces a 2 x 4 block of
@@ -689,6 +723,111 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_fir_samples_kernel(const CmFirS
   }
 }
 
+// The typed twins of cm_fir_kernel<EPI> and cm_fir_samples_kernel (fp16 activation storage): XH / YH / SH say which of x, y and
+// the skip tensor hold _Float16 (the pointers of CmFirArgs are reinterpreted).  The skip tensor is the encoder's and typed by the
+// encoder block's marking, x (the raw transposed-convolution output) and y by the synthesis block's, so every combination but
+// fp16 x with fp32 y occurs.  One body for both: the same 2 x 4 block per thread from a 5 x 7 window, every window load 8 bytes
+// where x is fp16, the skip / noise / bias loads ahead of the window loads, no load behind a store; the skip block stays in its
+// stored form until it is added.  Arithmetic is fp32 on converted values (the FIR gain included), one rounding, to nearest even,
+// when y is written.
+template <int EPI, bool SAMP, bool XH, bool YH, bool SH>
+MIGAN_DEVICE MIGAN_INLINE void cm_fir_h_body(const CmFirArgs& p, int S) {
+  using XI = Io<XH ? 2 : 0>;
+  using YI = Io<YH ? 2 : 0>;
+  using SI = Io<SH ? 2 : 0>;
+  const int qn = p.C >> 2;
+  const int nbx = (p.WO + 3) >> 2, nby = (p.HO + 1) >> 1;
+  const size_t total = (size_t)p.B * nby * nbx * qn;
+  const float f0 = p.fs, f1 = 3.0f * p.fs;
+  const float ns = (EPI == 1 && p.noise) ? p.noise_strength[0] : 0.0f;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int c4 = (int)(i % qn);
+    size_t blk = i / qn;
+    int smp = 0;
+    if constexpr (SAMP) { smp = (int)(blk % S); blk /= S; }
+    const int bx = (int)(blk % nbx); blk /= nbx;
+    const int by = (int)(blk % nby);
+    const int bi = (int)(blk / nby);                             // batch index of the skip tensor (SAMP: the image)
+    const int b = SAMP ? bi * S + smp : bi;                      // batch index of x, y and the noise
+    const int x0 = bx * 4, y0 = by * 2;
+    const char* xb = reinterpret_cast<const char*>(p.x) + ((size_t)b * p.H * p.W * p.C + c4 * 4) * XI::ESZ;
+    typename SI::raw4 sk[2][4];
+    float nz[2][4];
+    f4 bias4 = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (EPI == 1) {
+      bias4 = ld4(p.bias + c4 * 4);
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int oy = y0 + r, ox = x0 + c;
+          const bool ok = oy < p.HO && ox < p.WO;
+          sk[r][c] = SI::zero();
+          nz[r][c] = 0.0f;
+          if (ok && p.skip) {
+            const char* sp = reinterpret_cast<const char*>(p.skip) + ((((size_t)bi * p.HO + oy) * p.WO + ox) * p.C + c4 * 4) * SI::ESZ;
+            sk[r][c] = SAMP ? SI::ld(sp, 0u) : SI::ld_once(sp, 0u);      // (S samples share an image's skip pixels: a plain load there)
+          }
+          if (ok && p.noise) nz[r][c] = p.noise[(size_t)b * p.noise_bstride + (size_t)oy * p.WO + ox];
+        }
+    }
+    f4 acc[2][4];
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc[r][c] = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < 5; ++r) {
+      const int iy = y0 - p.pad + r;
+      const bool yok = iy >= 0 && iy < p.H;
+      typename XI::raw4 raw[7];
+#pragma unroll
+      for (int c = 0; c < 7; ++c) {
+        const int ix = x0 - p.pad + c;
+        raw[c] = XI::zero();
+        if (yok && ix >= 0 && ix < p.W) raw[c] = XI::ld(xb + ((size_t)iy * p.W + ix) * p.C * XI::ESZ, 0u);
+      }
+      f4 v[7];
+#pragma unroll
+      for (int c = 0; c < 7; ++c) v[c] = XI::cvt(raw[c]);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const f4 h = (v[c] + v[c + 3]) * f0 + (v[c + 1] + v[c + 2]) * f1;
+        if (r < 4) acc[0][c] = acc[0][c] + h * ((r == 0 || r == 3) ? f0 : f1);
+        if (r > 0) acc[1][c] = acc[1][c] + h * ((r == 1 || r == 4) ? f0 : f1);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int oy = y0 + r;
+      if (oy >= p.HO) continue;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int ox = x0 + c;
+        if (ox >= p.WO) continue;
+        const size_t o = (((size_t)b * p.HO + oy) * p.WO + ox) * p.C + c4 * 4;
+        f4 v = acc[r][c];
+        if constexpr (EPI == 1) {
+          if (p.noise) v = v + MIGAN_FMUL_RN(nz[r][c], ns);
+          v = act4(v + bias4);
+          if (p.skip) v = v + SI::cvt(sk[r][c]);
+        }
+        YI::st(reinterpret_cast<char*>(p.y) + o * YI::ESZ, 0u, v);
+      }
+    }
+  }
+}
+template <int EPI, bool XH, bool YH, bool SH>
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_fir_h_kernel(const CmFirArgs p) {
+  static_assert(XH || YH || SH, "the all-fp32 form is cm_fir_kernel");
+  cm_fir_h_body<EPI, false, XH, YH, SH>(p, 1);
+}
+template <bool XH, bool YH, bool SH>
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_fir_samples_h_kernel(const CmFirSamplesArgs q) {
+  static_assert(XH || YH || SH, "the all-fp32 form is cm_fir_samples_kernel");
+  cm_fir_h_body<1, true, XH, YH, SH>(q.f, q.S);
+}
+
 // ------------------------------------------------------------------------------------------------
 // torgb_layer (stylegan.py:330-344) with per-sample modulated weights wm [B][3][C] (cm_style_multi_kernel) + bias +
 // upsample2d of the running image (comodgan.py:334-343).  16 lanes per pixel, wave-shuffle butterfly.
@@ -720,6 +859,47 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_torgb_kernel(const CmRgbArgs p)
       const f4 v = ld4(xp + q * 4);
       const f4 w0 = ld4(w + q * 4), w1 = ld4(w + p.C + q * 4), w2 = ld4(w + 2 * p.C + q * 4);
       // scalar FMA chains, not SLP-vectorised packed-fp32 dot products (profiles/r02_torgb_packed_f32_hazard.md)
+      float a0, a1, a2;
+      torgb_partial(v, w0, w1, w2, a0, a1, a2);
+      r0 += a0;
+      r1 += a1;
+      r2 += a2;
+    }
+  }
+#pragma unroll
+  for (int s = LPP / 2; s >= 1; s >>= 1) {
+    r0 += __shfl_xor(r0, s);
+    r1 += __shfl_xor(r1, s);
+    r2 += __shfl_xor(r2, s);
+  }
+  if (ok && sub < 3) {
+    const int rem = (int)(pixel % plane);
+    const int oy = rem / p.W, ox = rem % p.W;
+    const float sum = sub == 0 ? r0 : (sub == 1 ? r1 : r2);
+    float up = 0.0f;
+    if (p.img_prev) up = up_prev3(p.img_prev + ((size_t)b * 3 + sub) * (plane >> 2), p.H >> 1, p.W >> 1, oy, ox);
+    p.img_out[((size_t)b * 3 + sub) * plane + rem] = up + (sum + p.bias[sub]);
+  }
+}
+
+// The same layer reading an fp16 feature map (the ToRGB of a half-precision block with fp16 storage on): 8 bytes per lane and
+// step; the weights, the sums, the running image and the output stay fp32.  A symbol of its own; p.x is reinterpreted.
+template <int LPP>
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_torgb_h_kernel(const CmRgbArgs p) {
+  static_assert(LPP == 4 || LPP == 8 || LPP == 16, "lanes per pixel");
+  const int sub = threadIdx.x & (LPP - 1);
+  const size_t pixel = ((size_t)blockIdx.x * 256 + threadIdx.x) / LPP;
+  const size_t plane = (size_t)p.H * p.W;
+  const size_t npix = (size_t)p.B * plane;
+  const bool ok = pixel < npix;
+  float r0 = 0.f, r1 = 0.f, r2 = 0.f;
+  const int b = ok ? (int)(pixel / plane) : 0;
+  if (ok) {
+    const char* xp = reinterpret_cast<const char*>(reinterpret_cast<const unsigned short*>(p.x) + pixel * p.C);
+    const float* w = p.wm + (size_t)b * 3 * p.C;
+    for (int q = sub; q < (p.C >> 2); q += LPP) {
+      const f4 v = Io<2>::cvt(Io<2>::ld(xp, (unsigned)q * 8u));
+      const f4 w0 = ld4(w + q * 4), w1 = ld4(w + p.C + q * 4), w2 = ld4(w + 2 * p.C + q * 4);
       float a0, a1, a2;
       torgb_partial(v, w0, w1, w2, a0, a1, a2);
       r0 += a0;

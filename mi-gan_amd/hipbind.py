@@ -83,6 +83,9 @@ SAMPLES_EXPORTS = ("comodgan_workspace_bytes_samples", "comodgan_forward_samples
 PIPELINE_SAMPLES_EXPORTS = ("migan_pipeline_batch_post_samples",)
 # include/comodgan_fp16_hip.h
 FP16_EXPORTS = ("comodgan_set_fp16_blocks", "comodgan_get_fp16_blocks")
+# include/comodgan_fp16_storage_hip.h
+FP16_STORAGE_EXPORTS = ("comodgan_set_fp16_storage", "comodgan_get_fp16_storage", "comodgan_debug_tensor_dtype")
+COMODGAN_DTYPE_F32, COMODGAN_DTYPE_F16 = 0, 2
 
 
 class PipelineItem(C.Structure):
@@ -144,7 +147,7 @@ class MiganLib:
         except OSError as e:  # pragma: no cover - depends on the machine
             raise MiganError(f"cannot load {self.path}: {e}") from e
         L = self.lib
-        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + FP16_EXPORTS:
+        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS:
             if not hasattr(L, name):
                 raise MiganError(f"{self.path} does not export {name}")
         vp, ci = C.c_void_p, C.c_int
@@ -210,6 +213,9 @@ class MiganLib:
         L.comodgan_debug_tensor_samples.argtypes = [vp, ci, ci, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64), C.POINTER(ci)]
         L.comodgan_set_fp16_blocks.argtypes = [vp, ci, ci]
         L.comodgan_get_fp16_blocks.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
+        L.comodgan_set_fp16_storage.argtypes = [vp, ci]
+        L.comodgan_get_fp16_storage.argtypes = [vp, C.POINTER(ci)]
+        L.comodgan_debug_tensor_dtype.argtypes = [vp, ci, ci, C.c_char_p, C.POINTER(ci)]
         L.migan_last_error.restype = C.c_char_p
         L.migan_last_kernel.restype = C.c_char_p
         L.migan_nan_policy.restype = C.c_char_p
@@ -220,7 +226,7 @@ class MiganLib:
         if not allow_test_backend and L.migan_backend().decode() != PRODUCT_BACKEND:
             raise MiganError(f"{self.path} reports backend {L.migan_backend().decode()!r}, not {PRODUCT_BACKEND!r}: only the gfx950 HIP "
                              f"library is a product backend (the CPU emulator build is test infrastructure)")
-        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + FP16_EXPORTS:
+        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS:
             if name not in ("migan_last_error", "migan_last_kernel", "migan_nan_policy", "migan_backend", "migan_gemm_variant", "migan_tuning_key"):
                 getattr(L, name).restype = ci
 
@@ -588,6 +594,16 @@ class CoModGANHandle:
         self.lib.check(self.lib.lib.comodgan_get_fp16_blocks(self._h, C.byref(e), C.byref(s)))
         return (None if e.value < 0 else e.value, None if s.value < 0 else s.value)
 
+    def set_fp16_storage(self, on: bool = True) -> None:
+        """the blocks marked through set_fp16_blocks store their activations in fp16 (include/comodgan_fp16_storage_hip.h).  Before
+        sizing the workspace."""
+        self.lib.check(self.lib.lib.comodgan_set_fp16_storage(self._h, 1 if on else 0))
+
+    def get_fp16_storage(self) -> bool:
+        on = C.c_int()
+        self.lib.check(self.lib.lib.comodgan_get_fp16_storage(self._h, C.byref(on)))
+        return bool(on.value)
+
     def set_debug(self, keep: bool) -> None:
         self.lib.check(self.lib.lib.comodgan_set_debug(self._h, 1 if keep else 0))
 
@@ -605,6 +621,24 @@ class CoModGANHandle:
         self.lib.check(self.lib.lib.comodgan_debug_tensor_samples(self._h, int(batch), int(samples), layer.encode(), C.byref(off), shape,
                                                                   C.byref(nd)))
         return int(off.value), tuple(int(shape[k]) for k in range(nd.value))
+
+    def debug_tensor_dtype(self, batch: int, layer: str, samples: int = 1) -> int:
+        """COMODGAN_DTYPE_F32 or COMODGAN_DTYPE_F16: how the debug tensor is stored in the workspace"""
+        dt = C.c_int()
+        self.lib.check(self.lib.lib.comodgan_debug_tensor_dtype(self._h, int(batch), int(samples), layer.encode(), C.byref(dt)))
+        return int(dt.value)
+
+    def read_debug_tensor(self, ws_bytes, batch: int, layer: str, samples: int = 1):
+        """A debug tensor as a float32 numpy array, whatever its stored type.  ws_bytes: the workspace after a forward of this plan
+        as a flat uint8 numpy array in host memory (the caller copies it back from the device)."""
+        import numpy as np
+        off, shape = self.debug_tensor_samples(batch, samples, layer)
+        half = self.debug_tensor_dtype(batch, layer, samples) == COMODGAN_DTYPE_F16
+        n = 1
+        for d in shape:
+            n *= d
+        raw = np.ascontiguousarray(ws_bytes).view(np.uint8).reshape(-1)[off:off + n * (2 if half else 4)]
+        return raw.view(np.float16 if half else np.float32).reshape(shape).astype(np.float32)
 
 
 _LIB: Optional[MiganLib] = None
