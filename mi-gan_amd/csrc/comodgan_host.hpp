@@ -524,6 +524,71 @@ struct CmWalk {
     return nz;
   }
 
+  // The streaming layers.  `half` flags (fp16 storage) pick the typed twin of a kernel; the reported bytes follow from esz() of each
+  // tensor, so the fp32 figures are the esz == 4 case of one formula.
+  // FromRGB of the first encoder block: the network input (4 fp32 planes) -> out ([R][R][c0])
+  void fromrgb(float* out, bool yh) {
+    const int R = h.cfg.resolution, c0 = h.channels(R);
+    CmFromRgbArgs a{};
+    a.x = x; a.w = weight(net.fromrgb.w); a.b = weight(net.fromrgb.b); a.y = out; a.wgain = 0.5f; a.B = N; a.R = R; a.C = c0;
+    emit(net.fromrgb.name.c_str(), "", yh ? "migan::cm_fromrgb_h_kernel" : "migan::cm_fromrgb_kernel", 2.0 * 4 * c0 * R * R, 0,
+         (4.0 * 4 + (double)esz(yh) * c0) * R * R, yh ? cm_fromrgb_h_kernel : cm_fromrgb_kernel, a,
+         grid1d((size_t)N * R * R * (c0 / 4) / 8), 0);      // 8 pixels per thread: the weights are read once per thread
+  }
+  // The FIR in front of the strided convolution L: xin ([res][res]) -> tmp ([res + 1][res + 1]), both of the block's type
+  void fir_down(const CmConvL& L, const float* xin, int res, bool half) {
+    const int c = L.ci;
+    CmFirArgs a{};
+    a.x = xin; a.y = tmp; a.B = N; a.H = res; a.W = res; a.C = c; a.HO = res + 1; a.WO = res + 1; a.pad = 2; a.fs = 0.125f;
+    emit(L.name.c_str(), ".fir", half ? "migan::cm_fir_h_kernel<0, true, true, false>" : "migan::cm_fir_kernel<0>",
+         2.0 * 16 * c * (res + 1) * (res + 1), 0, (double)esz(half) * c * ((double)res * res + (res + 1.0) * (res + 1.0)),
+         half ? cm_fir_h_kernel<0, true, true, false> : cm_fir_kernel<0>, a,
+         grid1d((size_t)N * cdiv(res + 1, 2) * cdiv(res + 1, 4) * (c / 4)), 0);
+  }
+  // The FIR half of the up=2 layer L: tmp (the raw transposed convolution, [res + 1][res + 1]) -> out ([res][res]) with noise, bias,
+  // activation and the encoder's skip tensor.  xh / yh / sh: which of the raw tensor, the output and the skip tensor hold fp16.
+  // With S > 1 the skip tensor is per image, [N]: sample b reads image b / S (the S reads of a skip pixel counted once).
+  struct FirUpForm { bool xh, yh, sh; void (*one)(const CmFirArgs); const char* one_name; void (*samples)(const CmFirSamplesArgs); const char* samples_name; };
+  void fir_up(const CmConvL& L, float* out, const CmNoise& nz, int res, bool xh, bool yh, bool sh) {
+#define CM_FIR_UP_FORM(XH, YH, SH)                                                                                \
+  {XH, YH, SH, cm_fir_h_kernel<1, XH, YH, SH>, "migan::cm_fir_h_kernel<1, " #XH ", " #YH ", " #SH ">", \
+   cm_fir_samples_h_kernel<XH, YH, SH>, "migan::cm_fir_samples_h_kernel<" #XH ", " #YH ", " #SH ">"}
+    static const FirUpForm forms[] = {
+        {false, false, false, cm_fir_kernel<1>, "migan::cm_fir_kernel<1>", cm_fir_samples_kernel, "migan::cm_fir_samples_kernel"},
+        CM_FIR_UP_FORM(false, false, true),       // an fp32 block above a half-precision encoder block
+        CM_FIR_UP_FORM(false, true, false),       // the first half-precision block: its raw tensor is fp32
+        CM_FIR_UP_FORM(false, true, true),
+        CM_FIR_UP_FORM(true, true, false),        // a later one
+        CM_FIR_UP_FORM(true, true, true),
+    };
+#undef CM_FIR_UP_FORM
+    const FirUpForm* form = std::find_if(std::begin(forms), std::end(forms), [&](const FirUpForm& f) { return f.xh == xh && f.yh == yh && f.sh == sh; });
+    MIGAN_CHECK(form != std::end(forms), MIGAN_EINVAL, "internal: no FIR-up kernel reads an fp16 raw tensor into an fp32 block");
+    const int co = L.co;
+    CmFirSamplesArgs as{};
+    CmFirArgs& a = as.f;
+    a.x = tmp; a.y = out; a.skip = feat[ilog2(res)]; a.bias = weight(L.b); a.noise = nz.plane;
+    a.noise_strength = weight(L.noise_strength); a.noise_bstride = nz.bstride;
+    a.B = B; a.H = res + 1; a.W = res + 1; a.C = co; a.HO = res; a.WO = res; a.pad = 1; a.fs = 0.25f; as.S = S;
+    const double flops = 2.0 * 16 * co * res * res;
+    const double bytes = co * ((double)esz(xh) * (res + 1.0) * (res + 1.0) + ((double)esz(yh) + (double)esz(sh) / S) * res * res);
+    const unsigned grid = grid1d((size_t)B * (res / 2) * cdiv(res, 4) * (co / 4));
+    if (S == 1) emit(L.name.c_str(), ".fir", form->one_name, flops, 0, bytes, form->one, a, grid, 0);
+    else emit(L.name.c_str(), ".fir", form->samples_name, flops, 0, bytes, form->samples, as, grid, 0);
+  }
+  // ToRGB of a synthesis block: xin ([res][res][c], fp16 if xh) and the running image prev -> out; weights, images and output are fp32
+  void torgb(const CmRgbL& L, const float* xin, int res, const float* prev, float* out, bool xh = false) {
+    const int c = L.c, lpp = c <= 64 ? 4 : (c <= 128 ? 8 : 16);      // lanes per pixel
+    static const struct { void (*fn)(const CmRgbArgs); const char* name; } kernels[2][3] = {
+        {{cm_torgb_kernel<4>, "migan::cm_torgb_kernel<4>"}, {cm_torgb_kernel<8>, "migan::cm_torgb_kernel<8>"}, {cm_torgb_kernel<16>, "migan::cm_torgb_kernel<16>"}},
+        {{cm_torgb_h_kernel<4>, "migan::cm_torgb_h_kernel<4>"}, {cm_torgb_h_kernel<8>, "migan::cm_torgb_h_kernel<8>"}, {cm_torgb_h_kernel<16>, "migan::cm_torgb_h_kernel<16>"}}};
+    const auto& k = kernels[xh][lpp / 8];
+    CmRgbArgs a{};
+    a.x = xin; a.wm = job_ws[L.job].wm; a.bias = weight(L.b); a.img_prev = prev; a.img_out = out; a.B = B; a.H = res; a.W = res; a.C = c;
+    emit(L.name.c_str(), "", k.name, 2.0 * 3 * c * res * res, 0, (double)esz(xh) * c * res * res + 4.0 * 3.75 * res * res, k.fn, a,
+         (unsigned)(((size_t)B * res * res * lpp + kThreads - 1) / kThreads), 0);
+  }
+
   // ---------------------------------------------------------------- buffers
   void buffers() {
     const int R = h.cfg.resolution;
@@ -599,14 +664,7 @@ struct CmWalk {
     bool cur_h = enc_h(R);
     float* cur = h.debug ? alloc((size_t)R * R * c0 * N * esz(cur_h)) : bufA;
     reg_debug(net.fromrgb.name.c_str(), "", cur, {N, R, R, c0}, cur_h);
-    CmFromRgbArgs a{};
-    a.x = x; a.w = weight(net.fromrgb.w); a.b = weight(net.fromrgb.b); a.y = cur; a.wgain = 0.5f; a.B = N; a.R = R; a.C = c0;
-    if (cur_h)
-      emit(net.fromrgb.name.c_str(), "", "migan::cm_fromrgb_h_kernel", 2.0 * 4 * c0 * R * R, 0, (4.0 * 4 + 2.0 * c0) * R * R, cm_fromrgb_h_kernel, a,
-           grid1d((size_t)N * R * R * (c0 / 4) / 8), 0);
-    else
-    emit(net.fromrgb.name.c_str(), "", "migan::cm_fromrgb_kernel", 2.0 * 4 * c0 * R * R, 0, 4.0 * (4 + c0) * R * R, cm_fromrgb_kernel, a,
-         grid1d((size_t)N * R * R * (c0 / 4) / 8), 0);      // 8 pixels per thread: the weights are read once per thread
+    fromrgb(cur, cur_h);
     for (const CmEncBlock& blk : net.enc) {
       const CmConvL& conv0 = net.convs[blk.conv0];
       const CmConvL& conv1 = net.convs[blk.conv1];
@@ -616,15 +674,7 @@ struct CmWalk {
       float* f = feat[ilog2(res)];
       reg_debug(conv0.name.c_str(), "", f, {N, res, res, c}, bh);
       conv(blk.conv0, "", CM_CONV_NORMAL, 0, cur, f, res, res, res, res, CmNoise{}, false, bh, bh);
-      CmFirArgs a{};
-      a.x = f; a.y = tmp; a.B = N; a.H = res; a.W = res; a.C = c; a.HO = res + 1; a.WO = res + 1; a.pad = 2; a.fs = 0.125f;
-      if (bh)
-        emit(conv1.name.c_str(), ".fir", "migan::cm_fir_h_kernel<0, true, true, false>", 2.0 * 16 * c * (res + 1) * (res + 1), 0,
-             2.0 * c * (2.0 * res * res + 2 * res + 1), cm_fir_h_kernel<0, true, true, false>, a,
-             grid1d((size_t)N * cdiv(res + 1, 2) * cdiv(res + 1, 4) * (c / 4)), 0);
-      else
-      emit(conv1.name.c_str(), ".fir", "migan::cm_fir_kernel<0>", 2.0 * 16 * c * (res + 1) * (res + 1), 0, 4.0 * c * (2.0 * res * res + 2 * res + 1),
-           cm_fir_kernel<0>, a, grid1d((size_t)N * cdiv(res + 1, 2) * cdiv(res + 1, 4) * (c / 4)), 0);
+      fir_down(conv1, f, res, bh);
       reg_debug(conv1.name.c_str(), ".fir", tmp, {N, res + 1, res + 1, c}, bh);       // (the shared tmp buffer: the last writer's data)
       float* out = act_out(conv1.name.c_str(), bufA, res / 2, conv1.co, oh);
       conv(blk.conv1, "", CM_CONV_DOWN, 0, tmp, out, res + 1, res + 1, res / 2, res / 2, CmNoise{}, false, bh, oh);
@@ -697,43 +747,6 @@ struct CmWalk {
   }
 
   // ---------------------------------------------------------------- synthesis (comodgan.py:395-420)
-  void torgb(const CmRgbL& L, const float* xin, int res, const float* prev, float* out, bool xh = false) {
-    const int c = L.c;
-    CmRgbArgs a{};
-    a.x = xin; a.wm = job_ws[L.job].wm; a.bias = weight(L.b); a.img_prev = prev; a.img_out = out; a.B = B; a.H = res; a.W = res; a.C = c;
-    const double fl = 2.0 * 3 * c * res * res, by = 4.0 * ((double)c * res * res + 3.75 * res * res);
-    const auto grid_of = [&](int lpp) { return (unsigned)(((size_t)B * res * res * lpp + kThreads - 1) / kThreads); };
-    const char* p = L.name.c_str();
-    if (xh) {        // the feature map is fp16; weights, running image and output are fp32
-      const double byh = 2.0 * c * res * res + 4.0 * 3.75 * res * res;
-      if (c <= 64) emit(p, "", "migan::cm_torgb_h_kernel<4>", fl, 0, byh, cm_torgb_h_kernel<4>, a, grid_of(4), 0);
-      else if (c <= 128) emit(p, "", "migan::cm_torgb_h_kernel<8>", fl, 0, byh, cm_torgb_h_kernel<8>, a, grid_of(8), 0);
-      else emit(p, "", "migan::cm_torgb_h_kernel<16>", fl, 0, byh, cm_torgb_h_kernel<16>, a, grid_of(16), 0);
-      return;
-    }
-    if (c <= 64) emit(p, "", "migan::cm_torgb_kernel<4>", fl, 0, by, cm_torgb_kernel<4>, a, grid_of(4), 0);
-    else if (c <= 128) emit(p, "", "migan::cm_torgb_kernel<8>", fl, 0, by, cm_torgb_kernel<8>, a, grid_of(8), 0);
-    else emit(p, "", "migan::cm_torgb_kernel<16>", fl, 0, by, cm_torgb_kernel<16>, a, grid_of(16), 0);
-  }
-  // The FIR half of an up=2 layer on fp16 storage: xh / yh / sh = which of the raw tensor, the output and the encoder's skip tensor
-  // hold fp16 (not all false: that is cm_fir_kernel<1> / cm_fir_samples_kernel, launched by the caller as ever)
-  void fir_up_typed(const char* layer, const CmFirArgs& a, bool xh, bool yh, bool sh, double flops, double bytes, unsigned grid) {
-    CmFirSamplesArgs as{};
-    as.f = a; as.S = S;
-#define CM_FIR_UP_FORM(XH, YH, SH)                                                                                                  \
-  if (xh == XH && yh == YH && sh == SH) {                                                                                           \
-    if (S == 1) emit(layer, ".fir", "migan::cm_fir_h_kernel<1, " #XH ", " #YH ", " #SH ">", flops, 0, bytes, cm_fir_h_kernel<1, XH, YH, SH>, a, grid, 0); \
-    else emit(layer, ".fir", "migan::cm_fir_samples_h_kernel<" #XH ", " #YH ", " #SH ">", flops, 0, bytes, cm_fir_samples_h_kernel<XH, YH, SH>, as, grid, 0); \
-    return;                                                                                                                         \
-  }
-    CM_FIR_UP_FORM(false, false, true)       // an fp32 block above a half-precision encoder block
-    CM_FIR_UP_FORM(false, true, false)       // the first half-precision block: its raw tensor is fp32
-    CM_FIR_UP_FORM(false, true, true)
-    CM_FIR_UP_FORM(true, true, false)        // a later one
-    CM_FIR_UP_FORM(true, true, true)
-#undef CM_FIR_UP_FORM
-    throw Error(MIGAN_EINVAL, "internal: no FIR-up kernel reads an fp16 raw tensor into an fp32 block");
-  }
   void synthesis() {
     static const char* const kPhase[4] = {".phase0", ".phase1", ".phase2", ".phase3"};
     const int R = h.cfg.resolution, c4 = h.channels(4);
@@ -777,25 +790,7 @@ struct CmWalk {
       reg_debug(conv0.name.c_str(), ".raw", tmp, {B, res + 1, res + 1, co}, xcur_h);     // (the shared tmp buffer: the last writer's data)
       const CmNoise nz0 = noise_of(conv0);
       float* x0 = act_out(conv0.name.c_str(), bufA, res, co, bh);
-      CmFirArgs a{};
-      a.x = tmp; a.y = x0; a.skip = feat[ilog2(res)]; a.bias = weight(conv0.b); a.noise = nz0.plane;
-      a.noise_strength = weight(conv0.noise_strength); a.noise_bstride = nz0.bstride;
-      a.B = B; a.H = res + 1; a.W = res + 1; a.C = co; a.HO = res; a.WO = res; a.pad = 1; a.fs = 0.25f;
-      const double fir_fl = 2.0 * 16 * co * res * res;
-      const unsigned fir_grid = grid1d((size_t)B * (res / 2) * cdiv(res, 4) * (co / 4));
-      if (xcur_h || bh || sh) {
-        fir_up_typed(conv0.name.c_str(), a, xcur_h, bh, sh, fir_fl,
-                     co * ((double)esz(xcur_h) * (res + 1.0) * (res + 1.0) + ((double)esz(bh) + (double)esz(sh) / S) * res * res), fir_grid);
-      } else if (S == 1) {
-        emit(conv0.name.c_str(), ".fir", "migan::cm_fir_kernel<1>", fir_fl, 0, 4.0 * co * ((res + 1.0) * (res + 1.0) + 2.0 * res * res),
-             cm_fir_kernel<1>, a, fir_grid, 0);
-      } else {
-        // the skip tensor is the encoder's, [N]: sample b reads image b / S (the S reads of a skip pixel counted once)
-        CmFirSamplesArgs as{};
-        as.f = a; as.S = S;
-        emit(conv0.name.c_str(), ".fir", "migan::cm_fir_samples_kernel", fir_fl, 0,
-             4.0 * co * ((res + 1.0) * (res + 1.0) + (1.0 + 1.0 / S) * res * res), cm_fir_samples_kernel, as, fir_grid, 0);
-      }
+      fir_up(conv0, x0, nz0, res, xcur_h, bh, sh);
       const CmNoise nz1 = noise_of(conv1);
       float* x1 = act_out(conv1.name.c_str(), bufB, res, co, bh);
       conv(blk.conv1, "", CM_CONV_NORMAL, 0, x0, x1, res, res, res, res, nz1, false, bh, bh);

@@ -9,7 +9,9 @@
 // on the matrix cores as an implicit GEMM (cm_conv_kernel); the rest are streaming kernels:
 //
 //   cm_*_h_kernel       the typed twins of the conv / FIR / FromRGB / ToRGB kernels: _Float16 activation tensors in the blocks a
-//                       caller has declared half precision, with comodgan_set_fp16_storage on (fp32 arithmetic on converted values)
+//                       caller has declared half precision, with comodgan_set_fp16_storage on (fp32 arithmetic on converted values).
+//                       A twin is a symbol, not a text: each of these four layers has one body, comodgan_{conv,fir,fromrgb,torgb}_body.inc,
+//                       compiled into every symbol of its family with the element types as constants of the enclosing kernel
 //   cm_conv_kernel      3x3 convolution, NHWC, M = 8x16 output-grid pixels, N = 64/128 output channels, K = taps x Cin.
 //                       A operand: the input halo tile of a 32-channel chunk is staged ONCE in LDS (scaled by the
 //                       per-sample style = the "scale activations" form of weight modulation, stylegan.py:171-182,
@@ -27,7 +29,8 @@
 //   cm_fir_kernel<0>    upfirdn2d [1,3,3,1] FIR with pad 2 in front of the strided convolution (conv2d_resample down path)
 //   cm_fir_kernel<1>    upfirdn2d FIR (gain 4) behind the transposed convolution + noise/bias/activation/skip epilogue
 //   cm_fir_samples_kernel, cm_dense_multi_samples_kernel, cm_bcast_kernel   the three places of an S-samples forward
-//                       (comodgan_forward_samples) where a per-sample launch reads a per-image operand: sample b -> image b / S
+//                       (comodgan_forward_samples) where a per-sample launch reads a per-image operand: sample b -> image b / S.
+//                       The first is the FIR body with SAMP set, the second shares cm_affine_job with cm_dense_multi_kernel
 //   cm_fromrgb_kernel   1x1 conv 4 -> C with bias and activation, NCHW planes -> NHWC
 //   cm_torgb_kernel     modulated 1x1 conv C -> 3 (no demodulation) + bias + 2x FIR upsample of the running image
 //   cm_dense_kernel     fully connected layers (mapping, affine, encoder fc, synthesis fc): weight streaming, fp32 FMA
@@ -435,13 +438,21 @@ struct CmDenseMultiArgs {
   float wgain;
   int N, K, K1, njobs;
 };
-MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_dense_multi_kernel(const CmDenseMultiArgs p) {
+// The job of this workgroup as a dense layer `a`; returns the workgroup's index within the job.  P: const CmDenseMultiArgs or a
+// reference to one -- the table by value where it is the kernel's own argument, by reference where it is a member of it, which is
+// how each kernel read it before the two shared this function and keeps the code of both as it was.
+template <class P>
+MIGAN_DEVICE MIGAN_INLINE int cm_affine_job(P p, CmDenseArgs& a) {
   int j = 0;
   while (j + 1 < p.njobs && (int)blockIdx.x >= p.blk0[j + 1]) ++j;
-  CmDenseArgs a{};
   a.x = ((p.alt_mask >> j) & 1ull) ? p.x_alt : p.x; a.x2 = p.x2; a.w = p.w[j]; a.b = p.b[j]; a.y = p.y[j];
   a.wgain = p.wgain; a.bgain = 1.0f; a.psi = 1.0f; a.N = p.N; a.K = p.K; a.K1 = p.K1; a.O = p.O[j];
-  cm_dense_block(a, (int)blockIdx.x - p.blk0[j]);
+  return (int)blockIdx.x - p.blk0[j];
+}
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_dense_multi_kernel(const CmDenseMultiArgs p) {
+  CmDenseArgs a{};
+  const int block = cm_affine_job<const CmDenseMultiArgs>(p, a);
+  cm_dense_block(a, block);
 }
 // The same launch of an S-samples forward (comodgan_forward_samples): N = images x S rows of x / x_alt (the latents, one per
 // sample, image-major) against the global code x2 of N / S images.  A symbol of its own, so that the launch above keeps its
@@ -451,13 +462,9 @@ struct CmDenseMultiSamplesArgs {
   int S;
 };
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_dense_multi_samples_kernel(const CmDenseMultiSamplesArgs q) {
-  const CmDenseMultiArgs& p = q.m;
-  int j = 0;
-  while (j + 1 < p.njobs && (int)blockIdx.x >= p.blk0[j + 1]) ++j;
   CmDenseArgs a{};
-  a.x = ((p.alt_mask >> j) & 1ull) ? p.x_alt : p.x; a.x2 = p.x2; a.w = p.w[j]; a.b = p.b[j]; a.y = p.y[j];
-  a.wgain = p.wgain; a.bgain = 1.0f; a.psi = 1.0f; a.N = p.N; a.K = p.K; a.K1 = p.K1; a.O = p.O[j];
-  cm_dense_block<true>(a, (int)blockIdx.x - p.blk0[j], q.S);
+  const int block = cm_affine_job<const CmDenseMultiArgs&>(q.m, a);
+  cm_dense_block<true>(a, block, q.S);
 }
 
 // Head of synthesis.b4 of an S-samples forward: x4 = fc(w0) + feat[4] depends on the image only and is computed at batch N;
@@ -489,51 +496,16 @@ struct CmFromRgbArgs {
   float wgain;
   int B, R, C;
 };
+// cm_fromrgb_h_kernel writes _Float16 (encoder block b<R> is half precision and fp16 storage is on; p.y is reinterpreted): values
+// are bounded by the +-256 clamp, rounded to nearest even, 8 bytes per channel quad.  One text, comodgan_fromrgb_body.inc, and a
+// symbol per output type, so that the fp32 launch keeps its name.
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_fromrgb_kernel(const CmFromRgbArgs p) {
-  // a thread keeps one channel quad (its 4 x 4 weights and bias stay in registers) and walks pixels; 256 / (C/4) pixels per
-  // workgroup step, consecutive lanes = consecutive channel quads of a pixel (1 KiB contiguous store per wave)
-  const int qn = p.C >> 2;                      // 16 ... 256, divides 256
-  const int c4 = (int)threadIdx.x % qn;
-  const int ppb = 256 / qn;
-  const size_t plane = (size_t)p.R * p.R;
-  const size_t npix = (size_t)p.B * plane;
-  f4 w[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) w[j] = ld4(p.w + (c4 * 4 + j) * 4) * p.wgain;
-  const f4 bias = ld4(p.b + c4 * 4);
-  for (size_t pix = (size_t)blockIdx.x * ppb + threadIdx.x / qn; pix < npix; pix += (size_t)gridDim.x * ppb) {
-    const size_t bi = pix / plane, rem = pix % plane;
-    const float* xp = p.x + bi * 4 * plane + rem;
-    const float x0 = xp[0], x1 = xp[plane], x2 = xp[2 * plane], x3 = xp[3 * plane];
-    f4 v;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = (x0 * w[j].x + x1 * w[j].y + x2 * w[j].z + x3 * w[j].w) + bias[j];
-    st4(p.y + pix * p.C + c4 * 4, act4(v));
-  }
+  constexpr bool YH = false;
+#include "comodgan_fromrgb_body.inc"
 }
-
-// The same layer writing _Float16 (encoder block b<R> is half precision and fp16 storage is on): values are bounded by the
-// +-256 clamp, rounded to nearest even, 8 bytes per channel quad.  A symbol of its own; p.y is reinterpreted.
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_fromrgb_h_kernel(const CmFromRgbArgs p) {
-  const int qn = p.C >> 2;
-  const int c4 = (int)threadIdx.x % qn;
-  const int ppb = 256 / qn;
-  const size_t plane = (size_t)p.R * p.R;
-  const size_t npix = (size_t)p.B * plane;
-  f4 w[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) w[j] = ld4(p.w + (c4 * 4 + j) * 4) * p.wgain;
-  const f4 bias = ld4(p.b + c4 * 4);
-  unsigned short* yh = reinterpret_cast<unsigned short*>(p.y);
-  for (size_t pix = (size_t)blockIdx.x * ppb + threadIdx.x / qn; pix < npix; pix += (size_t)gridDim.x * ppb) {
-    const size_t bi = pix / plane, rem = pix % plane;
-    const float* xp = p.x + bi * 4 * plane + rem;
-    const float x0 = xp[0], x1 = xp[plane], x2 = xp[2 * plane], x3 = xp[3 * plane];
-    f4 v;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = (x0 * w[j].x + x1 * w[j].y + x2 * w[j].z + x3 * w[j].w) + bias[j];
-    Io<2>::st(reinterpret_cast<char*>(yh + pix * p.C + c4 * 4), 0u, act4(v));
-  }
+  constexpr bool YH = true;
+#include "comodgan_fromrgb_body.inc"
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -558,264 +530,64 @@ struct CmFirArgs {
   float fs;
   int B, H, W, C, HO, WO, pad;
 };
+// How the FIR body addresses one of its activation tensors behind the float* argument.  at(t, el, c4): channel quad c4 of the
+// pixel whose first element is el; at(a, el): el elements on; ld / ld_once (a tensor read exactly once) / st (streamed): four
+// consecutive channels, `raw4` what a thread keeps until cvt.  Two spellings of the same addresses, the ones the kernels had while
+// each had a text of its own: the all-fp32 kernels compute in float* with ld4 / ld4once / st4o; a typed kernel (TYPED: some tensor
+// holds _Float16) addresses every tensor in bytes through Io<2> or, for its fp32 tensors, Io<0>.  The compiler schedules the two
+// differently, and this is what keeps every symbol's code instruction for instruction (profiles/comodgan_stream_bodies.md).
+template <class IO> struct CmBytes {
+  typedef typename IO::raw4 raw4;
+  static MIGAN_DEVICE MIGAN_INLINE const char* at(const float* t, size_t el, int c4) { return reinterpret_cast<const char*>(t) + (el + c4 * 4) * IO::ESZ; }
+  static MIGAN_DEVICE MIGAN_INLINE const char* at(const char* a, size_t el) { return a + el * IO::ESZ; }
+  static MIGAN_DEVICE MIGAN_INLINE char* at(float* t, size_t el) { return reinterpret_cast<char*>(t) + el * IO::ESZ; }
+  static MIGAN_DEVICE MIGAN_INLINE raw4 ld(const char* a) { return IO::ld(a, 0u); }
+  static MIGAN_DEVICE MIGAN_INLINE raw4 ld_once(const char* a) { return IO::ld_once(a, 0u); }
+  static MIGAN_DEVICE MIGAN_INLINE f4 cvt(raw4 r) { return IO::cvt(r); }
+  static MIGAN_DEVICE MIGAN_INLINE raw4 zero() { return IO::zero(); }
+  static MIGAN_DEVICE MIGAN_INLINE void st(char* a, f4 v) { IO::st(a, 0u, v); }
+};
+template <bool TYPED, bool H> struct CmAct : CmBytes<Io<H ? 2 : 0>> {};
+template <> struct CmAct<false, false> {
+  typedef f4 raw4;
+  static MIGAN_DEVICE MIGAN_INLINE const float* at(const float* t, size_t el, int c4) { return t + el + c4 * 4; }
+  static MIGAN_DEVICE MIGAN_INLINE const float* at(const float* t, size_t el) { return t + el; }
+  static MIGAN_DEVICE MIGAN_INLINE float* at(float* t, size_t el) { return t + el; }
+  static MIGAN_DEVICE MIGAN_INLINE raw4 ld(const float* a) { return ld4(a); }
+  static MIGAN_DEVICE MIGAN_INLINE raw4 ld_once(const float* a) { return ld4once(a); }
+  static MIGAN_DEVICE MIGAN_INLINE f4 cvt(raw4 r) { return r; }
+  static MIGAN_DEVICE MIGAN_INLINE raw4 zero() { return f4{0.f, 0.f, 0.f, 0.f}; }
+  static MIGAN_DEVICE MIGAN_INLINE void st(float* a, f4 v) { st4o(a, v); }
+};
+
+// The kernels' text is comodgan_fir_body.inc; EPI, SAMP, S and the element types are constants of the enclosing kernel.
 template <int EPI>
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_fir_kernel(const CmFirArgs p) {
-  const int qn = p.C >> 2;
-  const int nbx = (p.WO + 3) >> 2, nby = (p.HO + 1) >> 1;
-  const size_t total = (size_t)p.B * nby * nbx * qn;
-  const float f0 = p.fs, f1 = 3.0f * p.fs;
-  const float ns = (EPI == 1 && p.noise) ? p.noise_strength[0] : 0.0f;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-    const int c4 = (int)(i % qn);
-    size_t blk = i / qn;
-    const int bx = (int)(blk % nbx); blk /= nbx;
-    const int by = (int)(blk % nby);
-    const int b = (int)(blk / nby);
-    const int x0 = bx * 4, y0 = by * 2;
-    const float* xb = p.x + (size_t)b * p.H * p.W * p.C + c4 * 4;
-    // EPI 1: the skip tensor and the noise plane of the 2 x 4 output block are requested first, so that they travel with
-    // the 35 window loads instead of after the arithmetic that needs them last
-    f4 sk[2][4];
-    float nz[2][4];
-    f4 bias4 = {0.f, 0.f, 0.f, 0.f};                             // (read here, not between the stores below: a load behind a store waits for that store)
-    if constexpr (EPI == 1) {
-      bias4 = ld4(p.bias + c4 * 4);
-#pragma unroll
-      for (int r = 0; r < 2; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const int oy = y0 + r, ox = x0 + c;
-          const bool ok = oy < p.HO && ox < p.WO;
-          sk[r][c] = f4{0.f, 0.f, 0.f, 0.f};
-          nz[r][c] = 0.0f;
-          if (ok && p.skip) sk[r][c] = ld4once(p.skip + (((size_t)b * p.HO + oy) * p.WO + ox) * p.C + c4 * 4);
-          if (ok && p.noise) nz[r][c] = p.noise[(size_t)b * p.noise_bstride + (size_t)oy * p.WO + ox];
-        }
-    }
-    f4 acc[2][4];
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) acc[r][c] = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int r = 0; r < 5; ++r) {
-      const int iy = y0 - p.pad + r;
-      const bool yok = iy >= 0 && iy < p.H;
-      f4 v[7];
-#pragma unroll
-      for (int c = 0; c < 7; ++c) {
-        const int ix = x0 - p.pad + c;
-        v[c] = f4{0.f, 0.f, 0.f, 0.f};
-        if (yok && ix >= 0 && ix < p.W) v[c] = ld4(xb + ((size_t)iy * p.W + ix) * p.C);
-      }
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const f4 h = (v[c] + v[c + 3]) * f0 + (v[c + 1] + v[c + 2]) * f1;
-        if (r < 4) acc[0][c] = acc[0][c] + h * ((r == 0 || r == 3) ? f0 : f1);
-        if (r > 0) acc[1][c] = acc[1][c] + h * ((r == 1 || r == 4) ? f0 : f1);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const int oy = y0 + r;
-      if (oy >= p.HO) continue;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const int ox = x0 + c;
-        if (ox >= p.WO) continue;
-        const size_t o = (((size_t)b * p.HO + oy) * p.WO + ox) * p.C + c4 * 4;
-        f4 v = acc[r][c];
-        if constexpr (EPI == 1) {
-          if (p.noise) v = v + MIGAN_FMUL_RN(nz[r][c], ns);
-          v = act4(v + bias4);
-          if (p.skip) v = v + sk[r][c];
-        }
-        st4o(p.y + o, v);
-      }
-    }
-  }
+  constexpr bool SAMP = false, XH = false, YH = false, SH = false;
+  constexpr int S = 1;
+#include "comodgan_fir_body.inc"
 }
-
-// cm_fir_kernel<1> of an S-samples forward (comodgan_forward_samples): x, y and the noise are per sample ([B = N * S], image-major),
-// the skip tensor is the encoder's, per image ([N][HO][WO][C]): sample b reads the skip pixels of image b / S.  A kernel of its own,
-// so that cm_fir_kernel<1> keeps its arguments and its code; the same 2 x 4 block per thread, the skip and noise loads ahead of the
-// window loads and no load behind a store.  The flat index carries the sample right above the channel quad -- (image, block row,
-// block column, sample, quad) -- so the S samples of an image that share a 2 x 4 block of skip pixels sit in adjacent lane groups of
-// one workgroup or of two consecutive ones: the first brings the pixels in, the others find them in the vector cache or in L2 (a
-// plain load, not the read-once form of the per-image kernel).  Every other access is that kernel's, at the sample's batch index.
+// cm_fir_kernel<1> of an S-samples forward (comodgan_forward_samples): B = N * S, skip: [N].  Symbols of their own (and so are
+// the typed twins below), so that cm_fir_kernel<1> keeps its arguments and its code.
 struct CmFirSamplesArgs {
   CmFirArgs f;                 // B = N * S; skip: [N]
   int S;
 };
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_fir_samples_kernel(const CmFirSamplesArgs q) {
+  constexpr int EPI = 1;
+  constexpr bool SAMP = true, XH = false, YH = false, SH = false;
   const CmFirArgs& p = q.f;
   const int S = q.S;
-  const int qn = p.C >> 2;
-  const int nbx = (p.WO + 3) >> 2, nby = (p.HO + 1) >> 1;
-  const size_t total = (size_t)p.B * nby * nbx * qn;
-  const float f0 = p.fs, f1 = 3.0f * p.fs;
-  const float ns = p.noise ? p.noise_strength[0] : 0.0f;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-    const int c4 = (int)(i % qn);
-    size_t blk = i / qn;
-    const int smp = (int)(blk % S); blk /= S;
-    const int bx = (int)(blk % nbx); blk /= nbx;
-    const int by = (int)(blk % nby);
-    const int bi = (int)(blk / nby);                             // image: batch index of the skip tensor
-    const int b = bi * S + smp;                                  // sample: batch index of x, y and the noise
-    const int x0 = bx * 4, y0 = by * 2;
-    const float* xb = p.x + (size_t)b * p.H * p.W * p.C + c4 * 4;
-    // the skip tensor and the noise plane of the 2 x 4 output block are requested first, so that they travel with
-    // the 35 window loads instead of after the arithmetic that needs them last
-    f4 sk[2][4];
-    float nz[2][4];
-    const f4 bias4 = ld4(p.bias + c4 * 4);                       // (read here, not between the stores below: a load behind a store waits for that store)
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const int oy = y0 + r, ox = x0 + c;
-        const bool ok = oy < p.HO && ox < p.WO;
-        sk[r][c] = f4{0.f, 0.f, 0.f, 0.f};
-        nz[r][c] = 0.0f;
-        if (ok && p.skip) sk[r][c] = ld4(p.skip + (((size_t)bi * p.HO + oy) * p.WO + ox) * p.C + c4 * 4);
-        if (ok && p.noise) nz[r][c] = p.noise[(size_t)b * p.noise_bstride + (size_t)oy * p.WO + ox];
-      }
-    f4 acc[2][4];
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) acc[r][c] = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int r = 0; r < 5; ++r) {
-      const int iy = y0 - p.pad + r;
-      const bool yok = iy >= 0 && iy < p.H;
-      f4 v[7];
-#pragma unroll
-      for (int c = 0; c < 7; ++c) {
-        const int ix = x0 - p.pad + c;
-        v[c] = f4{0.f, 0.f, 0.f, 0.f};
-        if (yok && ix >= 0 && ix < p.W) v[c] = ld4(xb + ((size_t)iy * p.W + ix) * p.C);
-      }
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const f4 h = (v[c] + v[c + 3]) * f0 + (v[c + 1] + v[c + 2]) * f1;
-        if (r < 4) acc[0][c] = acc[0][c] + h * ((r == 0 || r == 3) ? f0 : f1);
-        if (r > 0) acc[1][c] = acc[1][c] + h * ((r == 1 || r == 4) ? f0 : f1);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const int oy = y0 + r;
-      if (oy >= p.HO) continue;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const int ox = x0 + c;
-        if (ox >= p.WO) continue;
-        const size_t o = (((size_t)b * p.HO + oy) * p.WO + ox) * p.C + c4 * 4;
-        f4 v = acc[r][c];
-        if (p.noise) v = v + MIGAN_FMUL_RN(nz[r][c], ns);
-        v = act4(v + bias4);
-        if (p.skip) v = v + sk[r][c];
-        st4o(p.y + o, v);
-      }
-    }
-  }
+#include "comodgan_fir_body.inc"
 }
-
-// The typed twins of cm_fir_kernel<EPI> and cm_fir_samples_kernel (fp16 activation storage): XH / YH / SH say which of x, y and
-// the skip tensor hold _Float16 (the pointers of CmFirArgs are reinterpreted).  The skip tensor is the encoder's and typed by the
-// encoder block's marking, x (the raw transposed-convolution output) and y by the synthesis block's, so every combination but
-// fp16 x with fp32 y occurs.  One body for both: the same 2 x 4 block per thread from a 5 x 7 window, every window load 8 bytes
-// where x is fp16, the skip / noise / bias loads ahead of the window loads, no load behind a store; the skip block stays in its
-// stored form until it is added.  Arithmetic is fp32 on converted values (the FIR gain included), one rounding, to nearest even,
-// when y is written.
+// The typed twins (fp16 activation storage): XH / YH / SH say which of x, y and the skip tensor hold _Float16 (the pointers of
+// CmFirArgs are reinterpreted).  The skip tensor is the encoder's and typed by the encoder block's marking, x (the raw
+// transposed-convolution output) and y by the synthesis block's, so every combination but fp16 x with fp32 y occurs.  These reach
+// the text through a function taking the arguments by reference, as they always have: included straight into the kernel it
+// compiles to other (somewhat shorter, unmeasured) code, and the all-fp32 kernels through the function likewise.
 template <int EPI, bool SAMP, bool XH, bool YH, bool SH>
 MIGAN_DEVICE MIGAN_INLINE void cm_fir_h_body(const CmFirArgs& p, int S) {
-  using XI = Io<XH ? 2 : 0>;
-  using YI = Io<YH ? 2 : 0>;
-  using SI = Io<SH ? 2 : 0>;
-  const int qn = p.C >> 2;
-  const int nbx = (p.WO + 3) >> 2, nby = (p.HO + 1) >> 1;
-  const size_t total = (size_t)p.B * nby * nbx * qn;
-  const float f0 = p.fs, f1 = 3.0f * p.fs;
-  const float ns = (EPI == 1 && p.noise) ? p.noise_strength[0] : 0.0f;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-    const int c4 = (int)(i % qn);
-    size_t blk = i / qn;
-    int smp = 0;
-    if constexpr (SAMP) { smp = (int)(blk % S); blk /= S; }
-    const int bx = (int)(blk % nbx); blk /= nbx;
-    const int by = (int)(blk % nby);
-    const int bi = (int)(blk / nby);                             // batch index of the skip tensor (SAMP: the image)
-    const int b = SAMP ? bi * S + smp : bi;                      // batch index of x, y and the noise
-    const int x0 = bx * 4, y0 = by * 2;
-    const char* xb = reinterpret_cast<const char*>(p.x) + ((size_t)b * p.H * p.W * p.C + c4 * 4) * XI::ESZ;
-    typename SI::raw4 sk[2][4];
-    float nz[2][4];
-    f4 bias4 = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (EPI == 1) {
-      bias4 = ld4(p.bias + c4 * 4);
-#pragma unroll
-      for (int r = 0; r < 2; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const int oy = y0 + r, ox = x0 + c;
-          const bool ok = oy < p.HO && ox < p.WO;
-          sk[r][c] = SI::zero();
-          nz[r][c] = 0.0f;
-          if (ok && p.skip) {
-            const char* sp = reinterpret_cast<const char*>(p.skip) + ((((size_t)bi * p.HO + oy) * p.WO + ox) * p.C + c4 * 4) * SI::ESZ;
-            sk[r][c] = SAMP ? SI::ld(sp, 0u) : SI::ld_once(sp, 0u);      // (S samples share an image's skip pixels: a plain load there)
-          }
-          if (ok && p.noise) nz[r][c] = p.noise[(size_t)b * p.noise_bstride + (size_t)oy * p.WO + ox];
-        }
-    }
-    f4 acc[2][4];
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) acc[r][c] = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int r = 0; r < 5; ++r) {
-      const int iy = y0 - p.pad + r;
-      const bool yok = iy >= 0 && iy < p.H;
-      typename XI::raw4 raw[7];
-#pragma unroll
-      for (int c = 0; c < 7; ++c) {
-        const int ix = x0 - p.pad + c;
-        raw[c] = XI::zero();
-        if (yok && ix >= 0 && ix < p.W) raw[c] = XI::ld(xb + ((size_t)iy * p.W + ix) * p.C * XI::ESZ, 0u);
-      }
-      f4 v[7];
-#pragma unroll
-      for (int c = 0; c < 7; ++c) v[c] = XI::cvt(raw[c]);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const f4 h = (v[c] + v[c + 3]) * f0 + (v[c + 1] + v[c + 2]) * f1;
-        if (r < 4) acc[0][c] = acc[0][c] + h * ((r == 0 || r == 3) ? f0 : f1);
-        if (r > 0) acc[1][c] = acc[1][c] + h * ((r == 1 || r == 4) ? f0 : f1);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const int oy = y0 + r;
-      if (oy >= p.HO) continue;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const int ox = x0 + c;
-        if (ox >= p.WO) continue;
-        const size_t o = (((size_t)b * p.HO + oy) * p.WO + ox) * p.C + c4 * 4;
-        f4 v = acc[r][c];
-        if constexpr (EPI == 1) {
-          if (p.noise) v = v + MIGAN_FMUL_RN(nz[r][c], ns);
-          v = act4(v + bias4);
-          if (p.skip) v = v + SI::cvt(sk[r][c]);
-        }
-        YI::st(reinterpret_cast<char*>(p.y) + o * YI::ESZ, 0u, v);
-      }
-    }
-  }
+#include "comodgan_fir_body.inc"
 }
 template <int EPI, bool XH, bool YH, bool SH>
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_fir_h_kernel(const CmFirArgs p) {
@@ -842,85 +614,18 @@ struct CmRgbArgs {
 // LPP lanes per pixel (4 for 64 channels ... 16 for >= 256): each lane reads C / (4 LPP) float4 of the pixel, a butterfly over
 // the LPP lanes forms the three sums, lane ch of the group finishes channel ch (bias, upsampled previous image) -- a wave
 // writes 64 / LPP consecutive pixels of each plane.
+// cm_torgb_h_kernel reads an fp16 feature map (the ToRGB of a half-precision block with fp16 storage on; p.x is reinterpreted):
+// 8 bytes per lane and step; the weights, the sums, the running image and the output stay fp32.  One text,
+// comodgan_torgb_body.inc, and a symbol family per feature-map type, so that the fp32 launches keep their names.
 template <int LPP>
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_torgb_kernel(const CmRgbArgs p) {
-  static_assert(LPP == 4 || LPP == 8 || LPP == 16, "lanes per pixel");
-  const int sub = threadIdx.x & (LPP - 1);
-  const size_t pixel = ((size_t)blockIdx.x * 256 + threadIdx.x) / LPP;
-  const size_t plane = (size_t)p.H * p.W;
-  const size_t npix = (size_t)p.B * plane;
-  const bool ok = pixel < npix;
-  float r0 = 0.f, r1 = 0.f, r2 = 0.f;
-  const int b = ok ? (int)(pixel / plane) : 0;
-  if (ok) {
-    const float* xp = p.x + pixel * p.C;
-    const float* w = p.wm + (size_t)b * 3 * p.C;
-    for (int q = sub; q < (p.C >> 2); q += LPP) {
-      const f4 v = ld4(xp + q * 4);
-      const f4 w0 = ld4(w + q * 4), w1 = ld4(w + p.C + q * 4), w2 = ld4(w + 2 * p.C + q * 4);
-      // scalar FMA chains, not SLP-vectorised packed-fp32 dot products (profiles/r02_torgb_packed_f32_hazard.md)
-      float a0, a1, a2;
-      torgb_partial(v, w0, w1, w2, a0, a1, a2);
-      r0 += a0;
-      r1 += a1;
-      r2 += a2;
-    }
-  }
-#pragma unroll
-  for (int s = LPP / 2; s >= 1; s >>= 1) {
-    r0 += __shfl_xor(r0, s);
-    r1 += __shfl_xor(r1, s);
-    r2 += __shfl_xor(r2, s);
-  }
-  if (ok && sub < 3) {
-    const int rem = (int)(pixel % plane);
-    const int oy = rem / p.W, ox = rem % p.W;
-    const float sum = sub == 0 ? r0 : (sub == 1 ? r1 : r2);
-    float up = 0.0f;
-    if (p.img_prev) up = up_prev3(p.img_prev + ((size_t)b * 3 + sub) * (plane >> 2), p.H >> 1, p.W >> 1, oy, ox);
-    p.img_out[((size_t)b * 3 + sub) * plane + rem] = up + (sum + p.bias[sub]);
-  }
+  constexpr bool XH = false;
+#include "comodgan_torgb_body.inc"
 }
-
-// The same layer reading an fp16 feature map (the ToRGB of a half-precision block with fp16 storage on): 8 bytes per lane and
-// step; the weights, the sums, the running image and the output stay fp32.  A symbol of its own; p.x is reinterpreted.
 template <int LPP>
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_torgb_h_kernel(const CmRgbArgs p) {
-  static_assert(LPP == 4 || LPP == 8 || LPP == 16, "lanes per pixel");
-  const int sub = threadIdx.x & (LPP - 1);
-  const size_t pixel = ((size_t)blockIdx.x * 256 + threadIdx.x) / LPP;
-  const size_t plane = (size_t)p.H * p.W;
-  const size_t npix = (size_t)p.B * plane;
-  const bool ok = pixel < npix;
-  float r0 = 0.f, r1 = 0.f, r2 = 0.f;
-  const int b = ok ? (int)(pixel / plane) : 0;
-  if (ok) {
-    const char* xp = reinterpret_cast<const char*>(reinterpret_cast<const unsigned short*>(p.x) + pixel * p.C);
-    const float* w = p.wm + (size_t)b * 3 * p.C;
-    for (int q = sub; q < (p.C >> 2); q += LPP) {
-      const f4 v = Io<2>::cvt(Io<2>::ld(xp, (unsigned)q * 8u));
-      const f4 w0 = ld4(w + q * 4), w1 = ld4(w + p.C + q * 4), w2 = ld4(w + 2 * p.C + q * 4);
-      float a0, a1, a2;
-      torgb_partial(v, w0, w1, w2, a0, a1, a2);
-      r0 += a0;
-      r1 += a1;
-      r2 += a2;
-    }
-  }
-#pragma unroll
-  for (int s = LPP / 2; s >= 1; s >>= 1) {
-    r0 += __shfl_xor(r0, s);
-    r1 += __shfl_xor(r1, s);
-    r2 += __shfl_xor(r2, s);
-  }
-  if (ok && sub < 3) {
-    const int rem = (int)(pixel % plane);
-    const int oy = rem / p.W, ox = rem % p.W;
-    const float sum = sub == 0 ? r0 : (sub == 1 ? r1 : r2);
-    float up = 0.0f;
-    if (p.img_prev) up = up_prev3(p.img_prev + ((size_t)b * 3 + sub) * (plane >> 2), p.H >> 1, p.W >> 1, oy, ox);
-    p.img_out[((size_t)b * 3 + sub) * plane + rem] = up + (sum + p.bias[sub]);
-  }
+  constexpr bool XH = true;
+#include "comodgan_torgb_body.inc"
 }
 
 }  // namespace migan

@@ -1,0 +1,41 @@
+// Body of cm_torgb_kernel<LPP> and cm_torgb_h_kernel<LPP> (comodgan_kernels.hpp), included into each like comodgan_fir_body.inc.
+// The enclosing kernel supplies p (its CmRgbArgs), LPP and XH: the feature map p.x holds _Float16.
+  static_assert(LPP == 4 || LPP == 8 || LPP == 16, "lanes per pixel");
+  const int sub = threadIdx.x & (LPP - 1);
+  const size_t pixel = ((size_t)blockIdx.x * 256 + threadIdx.x) / LPP;
+  const size_t plane = (size_t)p.H * p.W;
+  const size_t npix = (size_t)p.B * plane;
+  const bool ok = pixel < npix;
+  float r0 = 0.f, r1 = 0.f, r2 = 0.f;
+  const int b = ok ? (int)(pixel / plane) : 0;
+  if (ok) {
+    // the pixel's channels, fp16 or fp32, each in the element arithmetic its symbol has always had: unified they are the same
+    // addresses and other code (profiles/comodgan_stream_bodies.md)
+    const char* xp = XH ? reinterpret_cast<const char*>(reinterpret_cast<const unsigned short*>(p.x) + pixel * p.C)
+                        : reinterpret_cast<const char*>(p.x + pixel * p.C);
+    const float* w = p.wm + (size_t)b * 3 * p.C;
+    for (int q = sub; q < (p.C >> 2); q += LPP) {
+      const f4 v = XH ? Io<2>::cvt(Io<2>::ld(xp, (unsigned)q * 8u)) : ld4(reinterpret_cast<const float*>(xp) + q * 4);
+      const f4 w0 = ld4(w + q * 4), w1 = ld4(w + p.C + q * 4), w2 = ld4(w + 2 * p.C + q * 4);
+      // scalar FMA chains, not SLP-vectorised packed-fp32 dot products (profiles/r02_torgb_packed_f32_hazard.md)
+      float a0, a1, a2;
+      torgb_partial(v, w0, w1, w2, a0, a1, a2);
+      r0 += a0;
+      r1 += a1;
+      r2 += a2;
+    }
+  }
+#pragma unroll
+  for (int s = LPP / 2; s >= 1; s >>= 1) {
+    r0 += __shfl_xor(r0, s);
+    r1 += __shfl_xor(r1, s);
+    r2 += __shfl_xor(r2, s);
+  }
+  if (ok && sub < 3) {
+    const int rem = (int)(pixel % plane);
+    const int oy = rem / p.W, ox = rem % p.W;
+    const float sum = sub == 0 ? r0 : (sub == 1 ? r1 : r2);
+    float up = 0.0f;
+    if (p.img_prev) up = up_prev3(p.img_prev + ((size_t)b * 3 + sub) * (plane >> 2), p.H >> 1, p.W >> 1, oy, ox);
+    p.img_out[((size_t)b * 3 + sub) * plane + rem] = up + (sum + p.bias[sub]);
+  }

@@ -22,6 +22,10 @@ SOURCES = [
     os.path.join(ROOT, "mi-gan_amd", "csrc", "migan_k_slice.inc"),
     os.path.join(ROOT, "include", "migan_hip.h"),
     os.path.join(ROOT, "mi-gan_amd", "csrc", "comodgan_kernels.hpp"),
+    os.path.join(ROOT, "mi-gan_amd", "csrc", "comodgan_conv_body.inc"),
+    os.path.join(ROOT, "mi-gan_amd", "csrc", "comodgan_fir_body.inc"),
+    os.path.join(ROOT, "mi-gan_amd", "csrc", "comodgan_fromrgb_body.inc"),
+    os.path.join(ROOT, "mi-gan_amd", "csrc", "comodgan_torgb_body.inc"),
     os.path.join(ROOT, "mi-gan_amd", "csrc", "comodgan_host.hpp"),
     os.path.join(ROOT, "include", "comodgan_hip.h"),
 ]
