@@ -4,17 +4,21 @@
 scripts/demo.py:95-106 assembles ``comodgan-256|512`` -- keeps the reference's constructors, sub-module tree /
 ``state_dict`` schema (``load_state_dict(torch.load(path))``, demo.py:110) and ``forward`` contract
 (comodgan.py:435-455), but ``Generator.forward`` is one call into the MI355X HIP library through the C ABI
-(include/comodgan_hip.h).  PyTorch is used for device memory, streams and drawing ``z`` / the per-pixel noise of
+(include/comodgan_hip.h).  The three sub-modules of a ``Generator`` are callable with the reference's signatures as well
+(include/comodgan_stages_hip.h): ``G.mapping(z)`` -> ws, ``G.encoder(img)`` -> (x, feats), ``G.synthesis(x, feats, ws)`` -> img, with the
+stage tensors in torch memory -- encode once and complete later, edit ws, read the per-resolution ToRGB outputs
+(``return_intermediate_outs=True``).  PyTorch is used for device memory, streams and drawing ``z`` / the per-pixel noise of
 ``noise_mode='random'`` only.  There is no CPU or pure-PyTorch path: a CPU tensor, a missing libmigan_hip.so or
 a missing GPU raises.  ``Encoder(use_fp16_before_res=)`` / ``Synthesis(use_fp16_after_res=)`` mark half-precision blocks as
 in the reference: their 3x3 convolutions take fp16 operands (fp32 accumulation and storage; ``Generator.set_fp16_storage()``
 makes those blocks store their activations in fp16 as well, as the reference does).  Not supported: autograd,
-``c`` (class conditioning: c_dim = 0 in every reference config), ``truncation_cutoff``, ``return_intermediate_outs``.
+``c`` (class conditioning: c_dim = 0 in every reference config), ``return_intermediate_outs`` on ``Generator.forward`` (the fused call
+keeps no per-resolution image; ``G.synthesis(..., return_intermediate_outs=True)`` is where the reference defines them).
 """
 from __future__ import annotations
 
 import operator
-from typing import List, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -36,8 +40,17 @@ class _Node(nn.Module):
         return self._kind
 
     def forward(self, *args, **kwargs):
-        raise NotImplementedError(f"{self._kind}: only comodgan.Generator.forward is implemented on the MI355X HIP path; "
-                                  "sub-modules hold the reference-named parameters")
+        raise NotImplementedError(f"{self._kind}: on the MI355X HIP path only comodgan.Generator and the Mapping / Encoder / Synthesis of a "
+                                  "Generator compute; other sub-modules hold the reference-named parameters")
+
+    def _generator(self) -> "Generator":
+        """The Generator this stage belongs to: it owns the handle, the workspace and the weight binding.  Kept in a tuple in the instance
+        dict, so that it is no registered sub-module (no cycle in modules() / state_dict()) and copies follow it."""
+        owner = self.__dict__.get("_owner")
+        if owner is None:
+            raise NotImplementedError(f"{self._kind}: a stage computes as part of a comodgan.Generator (which owns the HIP handle and the "
+                                      "weight binding); stand-alone it holds the reference-named parameters")
+        return owner[0]
 
 
 def _init_tensor(e: cs.Entry) -> torch.Tensor:
@@ -90,7 +103,7 @@ def _fp16_res(name: str, value) -> Optional[int]:
 
 
 class Mapping(_Node):
-    """stylegan.py:356-439 (c_dim = 0).  Parameter container; evaluated inside Generator.forward."""
+    """stylegan.py:356-439 (c_dim = 0).  Callable as the ``mapping`` of a Generator."""
 
     def __init__(self, z_dim: int = 512, c_dim: int = 0, w_dim: int = 512, num_ws: int = 14, num_layers: int = 8, **unused):
         super().__init__("Mapping")
@@ -98,6 +111,10 @@ class Mapping(_Node):
             raise NotImplementedError("class-conditional mapping (c_dim > 0) is not part of the inference path")
         self.z_dim, self.c_dim, self.w_dim, self.num_ws, self.num_layers = z_dim, c_dim, w_dim, num_ws, num_layers
         _populate(self, "mapping", cs.Config(resolution=8, z_dim=z_dim, w_dim=w_dim, map_layers=num_layers, num_ws=num_ws))
+
+    def forward(self, z, c=None, truncation_psi=1, truncation_cutoff=None, skip_w_avg_update=False):
+        """z [N, z_dim] -> ws [N, num_ws, w_dim] (stylegan.py:402-439): rows below the cutoff truncated, the others raw."""
+        return self._generator()._stage_mapping(z, c, truncation_psi, truncation_cutoff)
 
 
 class Encoder(_Node):
@@ -113,6 +130,11 @@ class Encoder(_Node):
         cs.check_config(cfg)                                     # ValueError like comodgan.py:134-135
         self.resolution, self.ic_n, self.oc_n, self.ch_base, self.ch_max = resolution, ic_n, oc_n, ch_base, ch_max
         _populate(self, "encoder", cfg)
+
+    def forward(self, img, c=None):
+        """img [N, 4, R, R] -> (x [N, oc_n], feats {res: [N, C_res, res, res]}) (comodgan.py:190-204).  The feature tensors are
+        channels_last (the kernels' NHWC layout under an NCHW shape); float16 for the blocks that store fp16 (set_fp16_storage)."""
+        return self._generator()._stage_encoder(img, c)
 
 
 class Synthesis(_Node):
@@ -130,6 +152,11 @@ class Synthesis(_Node):
         self.num_ws = cs.default_num_ws(resolution)              # comodgan.py:367-370 (14 at 256, 16 at 512)
         _populate(self, "synthesis", cfg)
 
+    def forward(self, x, feats, ws, noise_mode="random", return_intermediate_outs=False):
+        """comodgan.py:395-421: img [B, 3, R, R], or (img, {"res_to_rgb": {res: ...}, "res_img": {res: ...}}).  Beyond the reference:
+        ws may hold B = N * S rows for N encoded images, image-major as in forward_samples -- row i * S + s is completed from image i."""
+        return self._generator()._stage_synthesis(x, feats, ws, noise_mode, return_intermediate_outs)
+
 
 class Generator(nn.Module):
     """Co-Mod-GAN generator (reference comodgan.py:423-455) on MI355X."""
@@ -142,6 +169,8 @@ class Generator(nn.Module):
                 synthesis.resolution, synthesis.ch_base, synthesis.ch_max, synthesis.w0_dim) or mapping.w_dim != synthesis.w_dim:
             raise ValueError("encoder and synthesis geometries differ")
         self.mapping, self.synthesis, self.encoder = mapping, synthesis, encoder
+        for stage in (mapping, encoder, synthesis):
+            stage.__dict__["_owner"] = (self,)                   # (_Node._generator)
         self.num_ws, self.z_dim, self.c_dim, self.w_dim = mapping.num_ws, mapping.z_dim, mapping.c_dim, mapping.w_dim
         self.img_resolution, self.img_channels, self.ic_n = synthesis.resolution, synthesis.rgb_n, encoder.ic_n
         self._cfg = cs.Config(resolution=synthesis.resolution, ch_base=synthesis.ch_base, ch_max=synthesis.ch_max, z_dim=mapping.z_dim,
@@ -159,6 +188,7 @@ class Generator(nn.Module):
         self._fp16: Tuple[Optional[int], Optional[int]] = (None, None)   # half-precision blocks the handle was last told
         self._fp16_storage = False       # set_fp16_storage(): the marked blocks keep their activations in fp16
         self._fp16_storage_told = False  # what the handle was last told
+        self._stage_need: Dict[tuple, int] = {}   # workspace bytes of the stage calls, per (handle, batch, samples, plan settings)
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._invalidate())
 
     # ------------------------------------------------------------------ plumbing
@@ -250,8 +280,9 @@ class Generator(nn.Module):
         """Args: x: 4 channel rgb+mask [N,4,R,R] (comodgan.py:437-441); z: [N,z_dim] (drawn with torch.randn when None, :438-439)."""
         assert noise_mode in ["random", "const", "none"]         # stylegan.py:280
         if c is not None or return_intermediate_outs:
-            raise NotImplementedError("c (class conditioning: c_dim = 0 in every published config) and return_intermediate_outs (a training-"
-                                      "loss hook) are not part of the MI355X inference path")
+            raise NotImplementedError("c (class conditioning: c_dim = 0 in every published config) is not part of the MI355X inference path, and "
+                                      "the fused Generator.forward keeps no per-resolution image: for return_intermediate_outs call the stages, "
+                                      "G.synthesis(*G.encoder(x), G.mapping(z), return_intermediate_outs=True)")
         if truncation_cutoff is not None and (int(truncation_cutoff) != truncation_cutoff or truncation_cutoff < 0):
             raise ValueError(f"truncation_cutoff must be a non-negative integer or None, got {truncation_cutoff!r}")
         r = self.img_resolution
@@ -336,6 +367,116 @@ class Generator(nn.Module):
         ms = h.forward_samples(x.data_ptr(), z.data_ptr(), y.data_ptr(), n, s, ws.data_ptr(), ws.numel(), float(truncation_psi), noise_mode,
                                None if noise is None else noise.data_ptr(), self._stream(x), timed=_timed)
         return (y, ms) if _timed else y
+
+    # ------------------------------------------------------------------ the stages (include/comodgan_stages_hip.h)
+    def _stage_workspace(self, h: CoModGANHandle, batch: int, samples: int, device: torch.device) -> torch.Tensor:
+        """One workspace for the stage calls and the fused forward: the prepared weight planes at its head serve all of them."""
+        key = (id(h), batch, samples, self._fp16, self._fp16_storage_told, self._cutoff)
+        need = self._stage_need.get(key)
+        if need is None:
+            if len(self._stage_need) > 64:
+                self._stage_need.clear()
+            need = self._stage_need[key] = h.stages_workspace_bytes(batch, samples)
+        if self._ws is None or self._ws.device != device or self._ws.numel() < need:
+            self._ws = None
+            self._refreeze = True
+            self._ws = torch.empty(need, dtype=torch.uint8, device=device)
+        if self._refreeze:
+            h.assume_static_weights(self._frozen)
+            self._refreeze = False
+        return self._ws
+
+    def _feat_dtype(self, res: int) -> torch.dtype:
+        before = self._fp16[0]
+        return torch.float16 if (self._fp16_storage_told and res > 4 and before is not None and res > before) else torch.float32
+
+    def _resolutions(self) -> List[int]:
+        return [1 << k for k in range(2, self.img_resolution.bit_length())]          # 4 ... R
+
+    def _stage_mapping(self, z: torch.Tensor, c, truncation_psi, truncation_cutoff) -> torch.Tensor:
+        if c is not None:
+            raise NotImplementedError("c (class conditioning: c_dim = 0 in every published config) is not part of the MI355X inference path")
+        if truncation_cutoff is not None and (int(truncation_cutoff) != truncation_cutoff or truncation_cutoff < 0):
+            raise ValueError(f"truncation_cutoff must be a non-negative integer or None, got {truncation_cutoff!r}")
+        if z.dim() != 2 or z.shape[1] != self.z_dim or z.shape[0] == 0:
+            raise RuntimeError(f"expected z of shape [N, {self.z_dim}], got {list(z.shape)}")
+        h = self._engine(z)
+        z = z.to(torch.float32).contiguous()
+        n = z.shape[0]
+        wsp = self._stage_workspace(h, n, 1, z.device)
+        ws = torch.empty((n, self.num_ws, self.w_dim), dtype=torch.float32, device=z.device)
+        h.mapping(z.data_ptr(), ws.data_ptr(), n, wsp.data_ptr(), wsp.numel(), float(truncation_psi),
+                  None if truncation_cutoff is None else int(truncation_cutoff), self._stream(z))
+        return ws
+
+    def _stage_encoder(self, img: torch.Tensor, c=None):
+        if c is not None:
+            raise NotImplementedError("c (class conditioning: c_dim = 0 in every published config) is not part of the MI355X inference path")
+        r = self.img_resolution
+        if img.dim() != 4 or img.shape[1] != 4 or img.shape[2] != r or img.shape[3] != r or img.shape[0] == 0:
+            raise RuntimeError(f"expected input of shape [N, 4, {r}, {r}] (mask-0.5, img*mask), got {list(img.shape)}")
+        if img.dtype != torch.float32:
+            raise RuntimeError(f"Input type ({img.dtype}) and weight type (torch.float32) should be the same")
+        h = self._engine(img)
+        img = img.contiguous()
+        n = img.shape[0]
+        wsp = self._stage_workspace(h, n, 1, img.device)
+        x = torch.empty((n, self._cfg.w0_dim), dtype=torch.float32, device=img.device)
+        # NHWC memory under the reference's NCHW shape: the encoder kernels write the tensors the caller gets
+        feats = {res: torch.empty((n, min(self._cfg.ch_base // res, self._cfg.ch_max), res, res), dtype=self._feat_dtype(res), device=img.device,
+                                  memory_format=torch.channels_last) for res in reversed(self._resolutions())}
+        h.encode(img.data_ptr(), x.data_ptr(), [feats[res].data_ptr() for res in self._resolutions()], n, wsp.data_ptr(), wsp.numel(),
+                 self._stream(img))
+        return x, feats
+
+    def _stage_synthesis(self, x: torch.Tensor, feats, ws: torch.Tensor, noise_mode: str = "random", return_intermediate_outs: bool = False):
+        assert noise_mode in ["random", "const", "none"]         # stylegan.py:280
+        r, c = self.img_resolution, self._cfg
+        if x.dim() != 2 or x.shape[1] != c.w0_dim or x.shape[0] == 0:
+            raise RuntimeError(f"expected x (the encoder's global code) of shape [N, {c.w0_dim}], got {list(x.shape)}")
+        n = x.shape[0]
+        if ws.dim() != 3 or ws.shape[1] != self.num_ws or ws.shape[2] != self.w_dim or ws.shape[0] == 0:
+            raise RuntimeError(f"expected ws of shape [N * S, {self.num_ws}, {self.w_dim}], got {list(ws.shape)}")
+        b = ws.shape[0]
+        if b % n:
+            raise ValueError(f"ws has {b} rows for {n} encoded images (x: {list(x.shape)}): the rows must be a multiple of the images, "
+                             f"row i * S + s completing image i")
+        s = b // n
+        h = self._engine(x)
+        x = x.to(torch.float32).contiguous()
+        ws = ws.to(device=x.device, dtype=torch.float32).contiguous()           # comodgan.py:397
+        ptrs = []
+        keep = []
+        for res in self._resolutions():
+            if res not in feats:
+                raise ValueError(f"feats has no entry for resolution {res}: expected the keys {self._resolutions()}, got {sorted(feats)}")
+            f = feats[res]
+            want = (n, min(c.ch_base // res, c.ch_max), res, res)
+            if tuple(f.shape) != want:
+                raise RuntimeError(f"feats[{res}]: expected shape {list(want)}, got {list(f.shape)}")
+            dt = self._feat_dtype(res)
+            if f.dtype != dt or f.device != x.device or not f.is_contiguous(memory_format=torch.channels_last):
+                f = f.to(device=x.device, dtype=dt).contiguous(memory_format=torch.channels_last)      # plumbing, off the hot path
+            keep.append(f)
+            ptrs.append(f.data_ptr())
+        noise = None
+        if noise_mode == "random":
+            noise = torch.randn(b * h.noise_floats(), dtype=torch.float32, device=x.device)
+        wsp = self._stage_workspace(h, n, s, x.device)
+        y = torch.empty((b, 3, r, r), dtype=torch.float32, device=x.device)
+        to_rgb = res_img = None
+        outs = None
+        if return_intermediate_outs:
+            lower = [res for res in self._resolutions() if res < r]
+            imgs = {res: torch.empty((b, 3, res, res), dtype=torch.float32, device=x.device) for res in lower}
+            rgbs = {res: torch.empty((b, 3, res, res), dtype=torch.float32, device=x.device) for res in self._resolutions() if res > 4}
+            res_img = [imgs[res].data_ptr() if res < r else 0 for res in self._resolutions()]
+            to_rgb = [rgbs[res].data_ptr() if res > 4 else 0 for res in self._resolutions()]
+            imgs[r] = y
+            outs = {"res_to_rgb": {4: imgs[4], **rgbs}, "res_img": imgs}      # comodgan.py:410: one tensor under both keys at res 4
+        h.synthesize(x.data_ptr(), ptrs, ws.data_ptr(), y.data_ptr(), n, s, wsp.data_ptr(), wsp.numel(), noise_mode,
+                     None if noise is None else noise.data_ptr(), to_rgb, res_img, self._stream(x))
+        return (y, outs) if return_intermediate_outs else y
 
     def forward_timed(self, x: torch.Tensor, z: torch.Tensor, noise_mode: str = "const"):
         """forward() with a hipEvent pair around every kernel launch: (y, [ms per launch])."""

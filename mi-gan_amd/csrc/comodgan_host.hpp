@@ -9,6 +9,7 @@
 #include "../../include/comodgan_samples_hip.h"
 #include "../../include/comodgan_fp16_hip.h"
 #include "../../include/comodgan_fp16_storage_hip.h"
+#include "../../include/comodgan_stages_hip.h"
 
 namespace migan {
 
@@ -238,11 +239,15 @@ struct CmPlanKey {
   int samples = 1;                   // completions per image (comodgan_forward_samples); batch counts images
   int fp16_enc = -1, fp16_syn = -1;  // comodgan_set_fp16_blocks: which layers run the single-plane convolution
   bool fp16_storage = false;         // comodgan_set_fp16_storage: those blocks keep their activations in fp16
+  int stage = 0;                     // CM_STAGE_*: the fused forward, or one stage of include/comodgan_stages_hip.h
+  unsigned parts = 0;                // comodgan_synthesize: bit log2(res) set = the ToRGB of block b<res> also stores its un-added output
   bool operator==(const CmPlanKey& o) const {
     return batch == o.batch && samples == o.samples && debug == o.debug && trunc_cutoff == o.trunc_cutoff && forced == o.forced &&
-           fp16_enc == o.fp16_enc && fp16_syn == o.fp16_syn && fp16_storage == o.fp16_storage;
+           fp16_enc == o.fp16_enc && fp16_syn == o.fp16_syn && fp16_storage == o.fp16_storage && stage == o.stage && parts == o.parts;
   }
 };
+// What a walk runs: everything (comodgan_forward / comodgan_forward_samples), or one stage with its stage tensors in caller memory
+enum : int { CM_STAGE_FUSED = 0, CM_STAGE_MAPPING = 1, CM_STAGE_ENCODE = 2, CM_STAGE_SYNTH = 3 };
 
 }  // namespace migan
 
@@ -268,6 +273,7 @@ struct comodgan_handle {
   const void* prepared_ws = nullptr;
   rt::stream_t prepared_stream{};   // the planes are only valid for work ordered after their preparation: same stream
   unsigned long long weights_epoch = 1, prepared_epoch = 0;
+  unsigned long long preparations = 0;   // weight preparations launched so far (comodgan_weight_preparations)
   // the mapping network (8 small dense layers on z only) runs on a library-owned stream beside the encoder
   rt::stream_t map_stream{};
   rt::event_t ev_fork{}, ev_map{};
@@ -284,7 +290,7 @@ struct comodgan_handle {
   // Workspace bytes of a forward at this batch (images) and sample count.  Sizes the network again unless the cached plan was made
   // for the same batch, samples, debug flag, truncation cutoff and forced kernel forms: infos / debug_tensors / events can never
   // belong to another launch sequence.
-  size_t ensure_planned(int batch, int samples = 1) const;
+  size_t ensure_planned(int batch, int samples = 1, int stage = 0, unsigned parts = 0) const;
 };
 
 // Mirror of mi-gan_amd/comodgan_schema.py::entries (the state_dict's registration order) and, from the same loops, the network as
@@ -402,6 +408,16 @@ struct CmWalk {
   std::vector<JobWs> job_ws;     // per net.jobs
   float *bufA = nullptr, *bufB = nullptr, *tmp = nullptr, *img[2] = {}, *feat[16] = {};
   float *wlat = nullptr, *wraw = nullptr, *w0 = nullptr;
+  // A staged walk (include/comodgan_stages_hip.h) runs one section of the network; what crosses a section boundary is the caller's:
+  // ws (written by the mapping stage, read by styles()), w0 and feat[] (written by encoder(), read by synthesis()), and the optional
+  // per-resolution outputs of synthesis(), indexed like feat[].  A sizing walk sees none of them.
+  int stage = CM_STAGE_FUSED;
+  unsigned parts = 0;            // CmPlanKey::parts
+  int map_cutoff = -1;           // the mapping stage's truncation_cutoff (an argument there, not the handle's setting)
+  float* ws_out = nullptr;
+  const float* ws_rows = nullptr;
+  float *w0_ext = nullptr, *feat_ext[16] = {}, *rgb_ext[16] = {}, *img_ext[16] = {};
+  bool staged() const { return stage != CM_STAGE_FUSED; }
 
   CmWalk(comodgan_handle& handle, int batch, int samples, const CmForced& f, bool size_only)
       : h(handle), net(handle.net), N(batch), S(samples), B(batch * samples), nb(batch), forced(f), sizing(size_only) {}
@@ -455,19 +471,30 @@ struct CmWalk {
   }
 
   // ---------------------------------------------------------------- weight preparation (every forward: weights are read in place)
+  // the prepared tensors of one convolution: the head of the workspace is these, in the order of net.prep, in every walk
+  ConvWs conv_ws_alloc(const CmConvL& c) {
+    const bool mod = c.job >= 0;
+    ConvWs p;
+    const size_t plane_bytes = (size_t)2 * 9 * c.ci * c.co * sizeof(unsigned short);
+    p.planes = reinterpret_cast<unsigned short*>(alloc(16 + plane_bytes)) + kSplitHeader;
+    p.amax = alloc((size_t)c.co * 4);
+    p.wsq = mod ? alloc((size_t)c.co * c.ci * 4) : nullptr;
+    p.wn2 = mod ? alloc((size_t)c.co * 4) : nullptr;
+    return p;
+  }
+  // the mapping stage reads no 3x3 weight: it steps over the head, so that planes prepared there stay valid
+  void reserve_weights() {
+    for (const int i : net.prep) conv_ws_alloc(net.convs[i]);
+  }
   void prepare_weights(const void* ws) {
     skip_launch = !sizing && h.static_weights && h.prepared_ws == ws && h.prepared_epoch == h.weights_epoch && h.prepared_stream == stream;
-    if (!sizing && !skip_launch) h.prepared_ws = nullptr;      // marked prepared again only after every preparation launch succeeded
+    if (!sizing && !skip_launch) { h.prepared_ws = nullptr; ++h.preparations; }      // marked prepared again only after every preparation launch succeeded
     conv_ws.resize(net.convs.size());
     for (const int i : net.prep) {
       const CmConvL& c = net.convs[i];
       const bool mod = c.job >= 0;
       ConvWs& p = conv_ws[i];
-      const size_t plane_bytes = (size_t)2 * 9 * c.ci * c.co * sizeof(unsigned short);
-      p.planes = reinterpret_cast<unsigned short*>(alloc(16 + plane_bytes)) + kSplitHeader;
-      p.amax = alloc((size_t)c.co * 4);
-      p.wsq = mod ? alloc((size_t)c.co * c.ci * 4) : nullptr;
-      p.wn2 = mod ? alloc((size_t)c.co * 4) : nullptr;
+      p = conv_ws_alloc(c);
       CmWprepArgs q{};
       q.w = weight(c.w); q.amax = p.amax; q.wsq = p.wsq; q.wn2 = p.wn2; q.CO = c.co; q.CI = c.ci;
       emit(c.name.c_str(), ".wprep", "migan::cm_wprep_kernel", 0, 0, 4.0 * c.co * c.ci * (mod ? 10 : 9) / nb, cm_wprep_kernel, q, (unsigned)c.co,
@@ -577,7 +604,9 @@ struct CmWalk {
     else emit(L.name.c_str(), ".fir", form->samples_name, flops, 0, bytes, form->samples, as, grid, 0);
   }
   // ToRGB of a synthesis block: xin ([res][res][c], fp16 if xh) and the running image prev -> out; weights, images and output are fp32
-  void torgb(const CmRgbL& L, const float* xin, int res, const float* prev, float* out, bool xh = false) {
+  // parts (staged walk): the un-added ToRGB output goes there as well, from the same launch
+  void torgb(const CmRgbL& L, const float* xin, int res, const float* prev, float* out, bool xh = false, float* parts_out = nullptr,
+             bool with_parts = false) {
     const int c = L.c, lpp = c <= 64 ? 4 : (c <= 128 ? 8 : 16);      // lanes per pixel
     static const struct { void (*fn)(const CmRgbArgs); const char* name; } kernels[2][3] = {
         {{cm_torgb_kernel<4>, "migan::cm_torgb_kernel<4>"}, {cm_torgb_kernel<8>, "migan::cm_torgb_kernel<8>"}, {cm_torgb_kernel<16>, "migan::cm_torgb_kernel<16>"}},
@@ -585,8 +614,20 @@ struct CmWalk {
     const auto& k = kernels[xh][lpp / 8];
     CmRgbArgs a{};
     a.x = xin; a.wm = job_ws[L.job].wm; a.bias = weight(L.b); a.img_prev = prev; a.img_out = out; a.B = B; a.H = res; a.W = res; a.C = c;
-    emit(L.name.c_str(), "", k.name, 2.0 * 3 * c * res * res, 0, (double)esz(xh) * c * res * res + 4.0 * 3.75 * res * res, k.fn, a,
-         (unsigned)(((size_t)B * res * res * lpp + kThreads - 1) / kThreads), 0);
+    const unsigned grid = (unsigned)(((size_t)B * res * res * lpp + kThreads - 1) / kThreads);
+    if (with_parts) {
+      static const struct { void (*fn)(const CmRgbPartsArgs); const char* name; } parts_kernels[2][3] = {
+          {{cm_torgb_parts_kernel<4>, "migan::cm_torgb_parts_kernel<4>"}, {cm_torgb_parts_kernel<8>, "migan::cm_torgb_parts_kernel<8>"},
+           {cm_torgb_parts_kernel<16>, "migan::cm_torgb_parts_kernel<16>"}},
+          {{cm_torgb_parts_h_kernel<4>, "migan::cm_torgb_parts_h_kernel<4>"}, {cm_torgb_parts_h_kernel<8>, "migan::cm_torgb_parts_h_kernel<8>"},
+           {cm_torgb_parts_h_kernel<16>, "migan::cm_torgb_parts_h_kernel<16>"}}};
+      const auto& kp = parts_kernels[xh][lpp / 8];
+      CmRgbPartsArgs ap{};
+      ap.r = a; ap.rgb_out = parts_out;
+      emit(L.name.c_str(), "", kp.name, 2.0 * 3 * c * res * res, 0, (double)esz(xh) * c * res * res + 4.0 * 6.75 * res * res, kp.fn, ap, grid, 0);
+      return;
+    }
+    emit(L.name.c_str(), "", k.name, 2.0 * 3 * c * res * res, 0, (double)esz(xh) * c * res * res + 4.0 * 3.75 * res * res, k.fn, a, grid, 0);
   }
 
   // ---------------------------------------------------------------- buffers
@@ -612,6 +653,32 @@ struct CmWalk {
     for (float*& im : img) im = h.debug ? nullptr : alloc((size_t)3 * R * R * B * 4);
     for (int res = R; res >= 4; res /= 2) feat[ilog2(res)] = alloc((size_t)res * res * h.channels(res) * N * esz(enc_h(res)));
   }
+  // The same for one stage of a staged walk: the tenants of that stage only (see buffers()), the encoder's at batch N, the synthesis
+  // network's at batch B; feat[] and w0 are the caller's tensors.
+  void stage_buffers() {
+    const int R = h.cfg.resolution;
+    const bool enc = stage == CM_STAGE_ENCODE, syn = stage == CM_STAGE_SYNTH;
+    size_t max_a = 0, max_b = 0, max_tmp = 0;
+    for (int res = 4; res <= R; res *= 2) {
+      const size_t act = (size_t)res * res * h.channels(res), raw = (size_t)(res + 1) * (res + 1) * h.channels(res);
+      if (enc) {
+        max_a = std::max(max_a, act * N * esz(enc_h(res)));
+        max_tmp = std::max(max_tmp, raw * N * esz(enc_h(res)));
+      }
+      if (syn) {
+        max_a = std::max(max_a, act * B * esz(syn_h(res)));
+        max_b = std::max(max_b, act * B * esz(syn_h(res)));
+        max_tmp = std::max(max_tmp, raw * B * esz(syn_h(res) && syn_h(res / 2)));
+      }
+    }
+    bufA = h.debug ? nullptr : alloc(max_a);
+    bufB = (h.debug || !syn) ? nullptr : alloc(max_b);
+    tmp = alloc(max_tmp);
+    // the ping-pong images serve the resolutions below R whose running image the caller did not ask for
+    if (syn) for (float*& im : img) im = h.debug ? nullptr : alloc((size_t)3 * (R / 2) * (R / 2) * B * 4);
+    for (int res = R; res >= 4; res /= 2) feat[ilog2(res)] = feat_ext[ilog2(res)];
+    w0 = w0_ext;
+  }
 
   // ---------------------------------------------------------------- mapping (stylegan.py:396-439)
   void mapping() {
@@ -622,12 +689,15 @@ struct CmWalk {
     wlat = alloc((size_t)B * cfg.w_dim * 4);
     // truncation_cutoff (stylegan.py:436-437): only ws[:, :cutoff] are pulled towards w_avg; the layers reading later rows get the raw w
     // (the buffer is part of the workspace whenever a cutoff is set, whatever psi a forward passes: the planned size must not depend on it)
-    wraw = h.trunc_cutoff >= 0 ? alloc((size_t)B * cfg.w_dim * 4) : nullptr;
-    const bool cut = psi != 1.0f && h.trunc_cutoff >= 0;
+    // (the mapping stage takes the cutoff as an argument: there the buffer always exists)
+    wraw = (staged() || h.trunc_cutoff >= 0) ? alloc((size_t)B * cfg.w_dim * 4) : nullptr;
+    const int cutoff = staged() ? map_cutoff : h.trunc_cutoff;
+    const bool cut = psi != 1.0f && cutoff >= 0;
     // The mapping network depends on z only and its eight launches are latency-bound (27 us each, 64 workgroups): they run on the
     // handle's own stream while the caller's stream goes on with the encoder; the affine layers (first reader of w) wait for it.
     // Ordering is by events only.  Timed / debug walks keep everything on the caller's stream.
-    side = !sizing && !timed && !h.debug;
+    // The mapping stage has nothing to run beside: it stays on the caller's stream.
+    side = !staged() && !sizing && !timed && !h.debug;
     if (side) {
       if (!h.side_ready) {
         rt_check(rt::stream_create(&h.map_stream), "hipStreamCreate");
@@ -648,6 +718,14 @@ struct CmWalk {
       cur = out;
     }
     reg_debug("mapping", "", wlat, {B, cfg.w_dim});
+    if (staged()) {
+      // ws = w.unsqueeze(1).repeat([1, num_ws, 1]) (stylegan.py:429-430) with the truncation of stylegan.py:432-437 already in the rows
+      CmWsRowsArgs r{};
+      r.w = wlat; r.w_raw = cut ? wraw : wlat; r.ws = ws_out; r.B = B; r.num_ws = cfg.num_ws; r.D = cfg.w_dim;
+      r.cutoff = cut ? std::min(cutoff, cfg.num_ws) : cfg.num_ws;
+      emit("mapping.ws", "", "migan::cm_ws_rows_kernel", 0, 0, 4.0 * cfg.w_dim * (cfg.num_ws + 1.0), cm_ws_rows_kernel, r,
+           grid1d((size_t)B * cfg.num_ws * (cfg.w_dim / 4)), 0);
+    }
     if (side) {
       rt_check(rt::event_record(h.ev_map, h.map_stream), "hipEventRecord");
       cur_stream = stream;
@@ -658,7 +736,7 @@ struct CmWalk {
   void encoder() {
     const int R = h.cfg.resolution, c0 = h.channels(R), c4 = h.channels(4);
     nb = N;
-    w0 = alloc((size_t)N * h.cfg.w0_dim * 4);
+    if (!staged()) w0 = alloc((size_t)N * h.cfg.w0_dim * 4);      // (staged: the caller's, like feat[])
     // fp16 storage: the input of a half-precision block is fp16 (the marking is monotone from the top), and so are its skip tensor
     // and its FIR-down output; its conv1 writes what the next block reads
     bool cur_h = enc_h(R);
@@ -692,9 +770,10 @@ struct CmWalk {
   // ---------------------------------------------------------------- affine + style jobs, ahead of the synthesis blocks
   void styles() {
     const int wl = h.cfg.w_dim + h.cfg.w0_dim;
-    const bool cut = psi != 1.0f && h.trunc_cutoff >= 0;
+    const bool cut = !staged() && psi != 1.0f && h.trunc_cutoff >= 0;
     nb = B;
     job_ws.assign(net.jobs.size(), JobWs{});
+    CmDenseMultiRowsArgs ar{};      // staged walk: the latents are rows of the caller's ws
     // every affine layer (styles = affine(cat([w, w0])), stylegan.py:282,337) in one launch
     CmDenseMultiArgs a{};
     double afl = 0;        // flops and workgroups so far
@@ -704,13 +783,19 @@ struct CmWalk {
       a.w[a.njobs] = weight(j.aff_w); a.b[a.njobs] = weight(j.aff_b); a.y[a.njobs] = job_ws[a.njobs].styles;
       a.O[a.njobs] = j.c; a.blk0[a.njobs] = ablk;
       if (cut && j.widx >= h.trunc_cutoff) a.alt_mask |= 1ull << a.njobs;
+      ar.widx[a.njobs] = j.widx;
       ablk += cdiv(j.c, 8); afl += 2.0 * wl * j.c; ++a.njobs;
     }
     a.blk0[a.njobs] = ablk;
     a.x = wlat; a.x_alt = wraw; a.x2 = w0; a.wgain = 1.0f / std::sqrt((float)wl); a.N = B; a.K = wl; a.K1 = h.cfg.w_dim;
     if (side) rt_check(rt::stream_wait_event(stream, h.ev_map), "hipStreamWaitEvent");     // w from the mapping stream
     // x / x_alt (the latents) are per sample, x2 = w0 per image: with S > 1 the launch that maps row b to image b / S
-    if (S == 1) {
+    if (staged()) {
+      MIGAN_CHECK(a.njobs == 0 || net.jobs[a.njobs - 1].widx < h.cfg.num_ws, MIGAN_EINVAL, "num_ws is smaller than the rows the synthesis layers read");
+      a.x = ws_rows; a.x_alt = nullptr;
+      ar.m = a; ar.S = S; ar.num_ws = h.cfg.num_ws;
+      emit("synthesis.affine", "", "migan::cm_dense_multi_rows_kernel", afl, 0, 2.0 * afl / B, cm_dense_multi_rows_kernel, ar, (unsigned)ablk, 0);
+    } else if (S == 1) {
       emit("synthesis.affine", "", "migan::cm_dense_multi_kernel", afl, 0, 2.0 * afl / B, cm_dense_multi_kernel, a, (unsigned)ablk, 0);
     } else {
       CmDenseMultiSamplesArgs as{};
@@ -768,7 +853,8 @@ struct CmWalk {
     const CmNoise nz4 = noise_of(b4);
     float* xcur = act_out(b4.name.c_str(), bufB, 4, c4);
     conv(net.syn_b4, "", CM_CONV_NORMAL, 0, x4, xcur, 4, 4, 4, 4, nz4);
-    float* im = h.debug ? alloc((size_t)3 * 16 * B * 4) : img[0];
+    // staged walk: a running image the caller asked for is written to the caller's tensor instead of a ping-pong image
+    float* im = h.debug ? alloc((size_t)3 * 16 * B * 4) : (img_ext[2] ? img_ext[2] : img[0]);
     reg_debug("synthesis.b4", ".img", im, {B, 3, 4, 4});
     torgb(net.rgb_b4, xcur, 4, nullptr, (R == 4) ? y : im);
     const float* imprev = im;
@@ -795,9 +881,10 @@ struct CmWalk {
       float* x1 = act_out(conv1.name.c_str(), bufB, res, co, bh);
       conv(blk.conv1, "", CM_CONV_NORMAL, 0, x0, x1, res, res, res, res, nz1, false, bh, bh);
       // img = upsample2d(img) + torgb(x) (comodgan.py:334-343)
-      float* imo = (res == R) ? y : (h.debug ? alloc((size_t)3 * res * res * B * 4) : img[flip]);
+      const int lv = ilog2(res);
+      float* imo = (res == R) ? y : (h.debug ? alloc((size_t)3 * res * res * B * 4) : (img_ext[lv] ? img_ext[lv] : img[flip]));
       if (res != R) reg_debug(blk.name.c_str(), ".img", imo, {B, 3, res, res});
-      torgb(blk.rgb, x1, res, imprev, imo, bh);
+      torgb(blk.rgb, x1, res, imprev, imo, bh, rgb_ext[lv], (parts >> lv) & 1u);
       imprev = imo; flip ^= 1; xcur = x1; xcur_h = bh;
     }
   }
@@ -807,12 +894,26 @@ struct CmWalk {
     cur_stream = stream;
     timed = ms != nullptr;
     if (sizing) { h.infos.clear(); h.debug_tensors.clear(); }
-    prepare_weights(ws);
-    buffers();
-    mapping();
-    encoder();
-    styles();
-    synthesis();
+    if (stage == CM_STAGE_FUSED) {
+      prepare_weights(ws);
+      buffers();
+      mapping();
+      encoder();
+      styles();
+      synthesis();
+    } else if (stage == CM_STAGE_MAPPING) {
+      reserve_weights();
+      mapping();
+    } else {
+      prepare_weights(ws);
+      stage_buffers();
+      if (stage == CM_STAGE_ENCODE) {
+        encoder();
+      } else {
+        styles();
+        synthesis();
+      }
+    }
     if (timed) {
       rt_check(rt::stream_sync(stream), "hipStreamSynchronize");
       for (int i = 0; i < nlaunch; ++i) rt_check(rt::event_elapsed(&ms[i], h.events[2 * i], h.events[2 * i + 1]), "hipEventElapsedTime");
@@ -823,12 +924,14 @@ struct CmWalk {
 
 }  // namespace migan
 
-inline size_t comodgan_handle::ensure_planned(int batch, int samples) const {
-  const migan::CmPlanKey key{batch, trunc_cutoff, debug, migan::cm_read_forced(), samples, fp16_enc, fp16_syn, fp16_storage};
+inline size_t comodgan_handle::ensure_planned(int batch, int samples, int stage, unsigned parts) const {
+  const migan::CmPlanKey key{batch, trunc_cutoff, debug, migan::cm_read_forced(), samples, fp16_enc, fp16_syn, fp16_storage, stage, parts};
   if (!(key == planned)) {
     comodgan_handle* m = const_cast<comodgan_handle*>(this);      // the queries of the C ABI take a const handle; the plan is a cache
     m->planned = migan::CmPlanKey{};                              // (nothing planned if the walk throws)
-    m->planned_need = migan::CmWalk(*m, batch, samples, key.forced, true).run(nullptr, nullptr);
+    migan::CmWalk walk(*m, batch, samples, key.forced, true);
+    walk.stage = stage; walk.parts = parts;
+    m->planned_need = walk.run(nullptr, nullptr);
     m->planned = key;
   }
   return planned_need;
@@ -1021,7 +1124,7 @@ int comodgan_forward_timed(comodgan_handle* h, const void* x, const void* z, voi
 int comodgan_num_launches(const comodgan_handle* h, int* n) {
   MIGAN_API_BEGIN
   MIGAN_CHECK(h && n, MIGAN_EINVAL, "null argument");
-  h->ensure_planned(std::max(h->planned.batch, 1), h->planned.samples);      // the launches of the plan made last, in the forms forced now
+  h->ensure_planned(std::max(h->planned.batch, 1), h->planned.samples, h->planned.stage, h->planned.parts);      // the launches of the plan made last, in the forms forced now
   *n = (int)h->infos.size();
   MIGAN_API_END
 }
@@ -1030,7 +1133,7 @@ int comodgan_launch_info(const comodgan_handle* h, int index, const char** layer
                          double* bytes) {
   MIGAN_API_BEGIN
   MIGAN_CHECK(h, MIGAN_EINVAL, "null handle");
-  h->ensure_planned(std::max(h->planned.batch, 1), h->planned.samples);
+  h->ensure_planned(std::max(h->planned.batch, 1), h->planned.samples, h->planned.stage, h->planned.parts);
   MIGAN_CHECK(index >= 0 && index < (int)h->infos.size(), MIGAN_EINVAL, "launch index out of range");
   const migan::CmInfo& L = h->infos[index];
   if (layer) *layer = L.layer.c_str();
@@ -1123,6 +1226,104 @@ int comodgan_debug_tensor_samples(const comodgan_handle* h, int batch, int sampl
     return MIGAN_OK;
   }
   throw migan::Error(MIGAN_EINVAL, std::string("no such debug tensor: ") + layer);
+  MIGAN_API_END
+}
+
+// ---------------------------------------------------------------- include/comodgan_stages_hip.h
+static void comodgan_check_stage_call(const comodgan_handle* h, const void* ws) {
+  MIGAN_CHECK(h, MIGAN_EINVAL, "null handle");
+  MIGAN_CHECK(h->committed, MIGAN_ESTATE, "stage call before comodgan_commit");
+  MIGAN_CHECK(ws != nullptr && ((uintptr_t)ws % 256) == 0, MIGAN_EINVAL, "null or misaligned workspace (256 bytes)");
+}
+
+int comodgan_stages_workspace_bytes(const comodgan_handle* h, int batch, int samples, size_t* bytes) {
+  MIGAN_API_BEGIN
+  using namespace migan;
+  MIGAN_CHECK(h && bytes && batch > 0, MIGAN_EINVAL, "bad argument");
+  comodgan_check_samples(batch, samples);
+  size_t need = h->ensure_planned(batch, samples);
+  need = std::max(need, h->ensure_planned(batch * samples, 1, CM_STAGE_MAPPING));
+  need = std::max(need, h->ensure_planned(batch, 1, CM_STAGE_ENCODE));
+  need = std::max(need, h->ensure_planned(batch, samples, CM_STAGE_SYNTH));      // (the optional outputs take no workspace)
+  *bytes = need;
+  MIGAN_API_END
+}
+
+int comodgan_mapping(comodgan_handle* h, const void* z, void* ws_rows, int rows, float psi, int cutoff, void* ws, size_t ws_bytes, void* stream) {
+  MIGAN_API_BEGIN
+  using namespace migan;
+  comodgan_check_stage_call(h, ws);
+  MIGAN_CHECK(z && ws_rows && rows > 0, MIGAN_EINVAL, "null tensor or empty batch");
+  MIGAN_CHECK(cutoff >= -1, MIGAN_EINVAL, "truncation_cutoff must be >= 0, or -1 for None");
+  MIGAN_CHECK(((uintptr_t)z % 4) == 0 && ((uintptr_t)ws_rows % 16) == 0 && h->cfg.w_dim % 4 == 0, MIGAN_EINVAL, "misaligned tensor");
+  MIGAN_CHECK(ws_bytes >= h->ensure_planned(rows, 1, CM_STAGE_MAPPING), MIGAN_EINVAL, "workspace too small for this batch");
+  DeviceGuard guard(h->device);
+  CmWalk walk(*h, rows, 1, h->planned.forced, false);
+  walk.stage = CM_STAGE_MAPPING;
+  walk.z = (const float*)z; walk.ws_out = (float*)ws_rows; walk.psi = psi; walk.map_cutoff = cutoff; walk.stream = (rt::stream_t)stream;
+  walk.run(ws, nullptr);
+  MIGAN_API_END
+}
+
+int comodgan_encode(comodgan_handle* h, const void* x, void* w0, void* const* feats, int batch, void* ws, size_t ws_bytes, void* stream) {
+  MIGAN_API_BEGIN
+  using namespace migan;
+  comodgan_check_stage_call(h, ws);
+  MIGAN_CHECK(x && w0 && feats && batch > 0, MIGAN_EINVAL, "null tensor or empty batch");
+  MIGAN_CHECK(((uintptr_t)x % 16) == 0 && ((uintptr_t)w0 % 4) == 0, MIGAN_EINVAL, "misaligned tensor");
+  MIGAN_CHECK(ws_bytes >= h->ensure_planned(batch, 1, CM_STAGE_ENCODE), MIGAN_EINVAL, "workspace too small for this batch");
+  DeviceGuard guard(h->device);
+  CmWalk walk(*h, batch, 1, h->planned.forced, false);
+  walk.stage = CM_STAGE_ENCODE;
+  for (int res = 4; res <= h->cfg.resolution; res *= 2) {
+    void* f = feats[ilog2(res) - 2];
+    MIGAN_CHECK(f != nullptr && ((uintptr_t)f % 16) == 0, MIGAN_EINVAL, "null or misaligned feature tensor");
+    walk.feat_ext[ilog2(res)] = (float*)f;
+  }
+  walk.x = (const float*)x; walk.w0_ext = (float*)w0; walk.stream = (rt::stream_t)stream;
+  walk.run(ws, nullptr);
+  MIGAN_API_END
+}
+
+int comodgan_synthesize(comodgan_handle* h, const void* w0, const void* const* feats, const void* ws_rows, void* y, int batch, int samples,
+                        int noise_mode, const void* noise, void* const* to_rgb, void* const* res_img, void* ws, size_t ws_bytes, void* stream) {
+  MIGAN_API_BEGIN
+  using namespace migan;
+  comodgan_check_stage_call(h, ws);
+  MIGAN_CHECK(w0 && feats && ws_rows && y && batch > 0, MIGAN_EINVAL, "null tensor or empty batch");
+  comodgan_check_samples(batch, samples);
+  MIGAN_CHECK(noise_mode == COMODGAN_NOISE_NONE || noise_mode == COMODGAN_NOISE_CONST || noise_mode == COMODGAN_NOISE_RANDOM, MIGAN_EINVAL,
+              "noise_mode must be none, const or random");
+  MIGAN_CHECK(noise_mode != COMODGAN_NOISE_RANDOM || noise != nullptr, MIGAN_EINVAL, "noise_mode random needs the noise tensor");
+  MIGAN_CHECK(((uintptr_t)y % 16) == 0 && ((uintptr_t)w0 % 4) == 0 && ((uintptr_t)ws_rows % 4) == 0, MIGAN_EINVAL, "misaligned tensor");
+  const int R = h->cfg.resolution;
+  unsigned parts = 0;
+  for (int res = 8; res <= R && to_rgb; res *= 2)
+    if (to_rgb[ilog2(res) - 2]) parts |= 1u << ilog2(res);
+  MIGAN_CHECK(ws_bytes >= h->ensure_planned(batch, samples, CM_STAGE_SYNTH, parts), MIGAN_EINVAL, "workspace too small for this batch");
+  DeviceGuard guard(h->device);
+  CmWalk walk(*h, batch, samples, h->planned.forced, false);
+  walk.stage = CM_STAGE_SYNTH; walk.parts = parts;
+  for (int res = 4; res <= R; res *= 2) {
+    const int lv = ilog2(res);
+    const void* f = feats[lv - 2];
+    MIGAN_CHECK(f != nullptr && ((uintptr_t)f % 16) == 0, MIGAN_EINVAL, "null or misaligned feature tensor");
+    walk.feat_ext[lv] = const_cast<float*>((const float*)f);      // (read only by this stage)
+    if (res >= 8 && to_rgb) walk.rgb_ext[lv] = (float*)to_rgb[lv - 2];
+    if (res < R && res_img) walk.img_ext[lv] = (float*)res_img[lv - 2];
+    MIGAN_CHECK(((uintptr_t)walk.rgb_ext[lv] % 4) == 0 && ((uintptr_t)walk.img_ext[lv] % 4) == 0, MIGAN_EINVAL, "misaligned tensor");
+  }
+  walk.w0_ext = const_cast<float*>((const float*)w0);
+  walk.ws_rows = (const float*)ws_rows; walk.y = (float*)y; walk.noise = (const float*)noise; walk.noise_mode = noise_mode;
+  walk.stream = (rt::stream_t)stream;
+  walk.run(ws, nullptr);
+  MIGAN_API_END
+}
+
+int comodgan_weight_preparations(const comodgan_handle* h, unsigned long long* n) {
+  MIGAN_API_BEGIN
+  MIGAN_CHECK(h && n, MIGAN_EINVAL, "null argument");
+  *n = h->preparations;
   MIGAN_API_END
 }
 

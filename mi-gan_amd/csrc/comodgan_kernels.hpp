@@ -334,8 +334,9 @@ struct CmDenseArgs {
   int act, norm, in_c, out_c;
 };
 // SAMP (the affine launch of an S-samples forward): x is per sample, x2 per image -- row n of x2 is n / S.
-template <bool SAMP = false>
-MIGAN_DEVICE MIGAN_INLINE void cm_dense_block(const CmDenseArgs& p, int block, int S = 1) {
+// ROWS (the affine launch of the staged walk): x is one row of a caller's ws [N][num_ws][w_dim] per batch row, xs floats apart.
+template <bool SAMP = false, bool ROWS = false>
+MIGAN_DEVICE MIGAN_INLINE void cm_dense_block(const CmDenseArgs& p, int block, int S = 1, int xs = 0) {
   constexpr int RP = 8;                      // batch rows per pass over the weights (16 spills)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int o0 = (block * 4 + wave) * 2;
@@ -379,7 +380,7 @@ MIGAN_DEVICE MIGAN_INLINE void cm_dense_block(const CmDenseArgs& p, int block, i
         for (int r = 0; r < RP; ++r) {
           const int n = n0 + r;
           float xv = 0.0f;
-          if (n < p.N) xv = (k < p.K1) ? p.x[(size_t)n * p.K1 + k] : p.x2[(size_t)(SAMP ? n / S : n) * K2 + (k - p.K1)];
+          if (n < p.N) xv = (k < p.K1) ? p.x[(size_t)n * (ROWS ? xs : p.K1) + k] : p.x2[(size_t)(SAMP ? n / S : n) * K2 + (k - p.K1)];
           acc[0][r] += xv * w0;
           acc[1][r] += xv * w1;
           nrm[r] += xv * xv;
@@ -442,9 +443,10 @@ struct CmDenseMultiArgs {
 // reference to one -- the table by value where it is the kernel's own argument, by reference where it is a member of it, which is
 // how each kernel read it before the two shared this function and keeps the code of both as it was.
 template <class P>
-MIGAN_DEVICE MIGAN_INLINE int cm_affine_job(P p, CmDenseArgs& a) {
+MIGAN_DEVICE MIGAN_INLINE int cm_affine_job(P p, CmDenseArgs& a, int* job = nullptr) {
   int j = 0;
   while (j + 1 < p.njobs && (int)blockIdx.x >= p.blk0[j + 1]) ++j;
+  if (job) *job = j;
   a.x = ((p.alt_mask >> j) & 1ull) ? p.x_alt : p.x; a.x2 = p.x2; a.w = p.w[j]; a.b = p.b[j]; a.y = p.y[j];
   a.wgain = p.wgain; a.bgain = 1.0f; a.psi = 1.0f; a.N = p.N; a.K = p.K; a.K1 = p.K1; a.O = p.O[j];
   return (int)blockIdx.x - p.blk0[j];
@@ -465,6 +467,42 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_dense_multi_samples_kernel(cons
   CmDenseArgs a{};
   const int block = cm_affine_job<const CmDenseMultiArgs&>(q.m, a);
   cm_dense_block<true>(a, block, q.S);
+}
+// The same launch of the staged walk (comodgan_synthesize, include/comodgan_stages_hip.h): the latents are the caller's
+// ws [N][num_ws][w_dim], N = images x S rows; job j reads row widx[j] of each (comodgan.py:399-405), so the row stride of x is
+// num_ws * w_dim and whatever truncation the caller wants is already in the rows: no x_alt, alt_mask = 0.  x2 = w0 of N / S images.
+struct CmDenseMultiRowsArgs {
+  CmDenseMultiArgs m;              // x: ws
+  int widx[kCmMaxAffine];
+  int S, num_ws;
+};
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_dense_multi_rows_kernel(const CmDenseMultiRowsArgs q) {
+  CmDenseArgs a{};
+  int j = 0;
+  const int block = cm_affine_job<const CmDenseMultiArgs&>(q.m, a, &j);
+  a.x += (size_t)q.widx[j] * q.m.K1;
+  cm_dense_block<true, true>(a, block, q.S, q.num_ws * q.m.K1);
+}
+
+// ws of the mapping stage (comodgan_mapping; stylegan.py:429-437): the mapping output w [B][D] repeated to [B][num_ws][D], rows
+// below `cutoff` from w (truncated towards w_avg by the last dense launch), the others from w_raw (the value before the lerp).
+struct CmWsRowsArgs {
+  const float* w;      // [B][D]
+  const float* w_raw;  // [B][D]; read only where cutoff < num_ws
+  float* ws;           // [B][num_ws][D]
+  int B, num_ws, D, cutoff;      // D a multiple of 4
+};
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_ws_rows_kernel(const CmWsRowsArgs p) {
+  const int dq = p.D >> 2;
+  const size_t total = (size_t)p.B * p.num_ws * dq;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int q = (int)(i % dq);
+    const size_t br = i / dq;
+    const int r = (int)(br % p.num_ws);
+    const size_t b = br / p.num_ws;
+    const float* src = r < p.cutoff ? p.w : p.w_raw;
+    st4(p.ws + br * p.D + q * 4, ld4(src + b * p.D + q * 4));
+  }
 }
 
 // Head of synthesis.b4 of an S-samples forward: x4 = fc(w0) + feat[4] depends on the image only and is computed at batch N;
@@ -619,12 +657,35 @@ struct CmRgbArgs {
 // comodgan_torgb_body.inc, and a symbol family per feature-map type, so that the fp32 launches keep their names.
 template <int LPP>
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_torgb_kernel(const CmRgbArgs p) {
-  constexpr bool XH = false;
+  constexpr bool XH = false, PARTS = false;
+  float* const rgb_out = nullptr;
 #include "comodgan_torgb_body.inc"
 }
 template <int LPP>
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_torgb_h_kernel(const CmRgbArgs p) {
-  constexpr bool XH = true;
+  constexpr bool XH = true, PARTS = false;
+  float* const rgb_out = nullptr;
+#include "comodgan_torgb_body.inc"
+}
+// The ToRGB of the staged walk with return_intermediate_outs (comodgan.py:334-343 returns to_rgb_out beside img): the same pass
+// also stores the un-added torgb(x) to rgb_out, planar like img_out.  Symbols of their own, so that the launches above keep their
+// arguments and their code.
+struct CmRgbPartsArgs {
+  CmRgbArgs r;
+  float* rgb_out;        // planar [B][3][H][W]
+};
+template <int LPP>
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_torgb_parts_kernel(const CmRgbPartsArgs q) {
+  constexpr bool XH = false, PARTS = true;
+  const CmRgbArgs& p = q.r;
+  float* const rgb_out = q.rgb_out;
+#include "comodgan_torgb_body.inc"
+}
+template <int LPP>
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_torgb_parts_h_kernel(const CmRgbPartsArgs q) {
+  constexpr bool XH = true, PARTS = true;
+  const CmRgbArgs& p = q.r;
+  float* const rgb_out = q.rgb_out;
 #include "comodgan_torgb_body.inc"
 }
 

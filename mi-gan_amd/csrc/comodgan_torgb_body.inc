@@ -1,5 +1,6 @@
-// Body of cm_torgb_kernel<LPP> and cm_torgb_h_kernel<LPP> (comodgan_kernels.hpp), included into each like comodgan_fir_body.inc.
-// The enclosing kernel supplies p (its CmRgbArgs), LPP and XH: the feature map p.x holds _Float16.
+// Body of cm_torgb_kernel<LPP>, cm_torgb_h_kernel<LPP> and their _parts twins (comodgan_kernels.hpp), included into each like
+// comodgan_fir_body.inc.  The enclosing kernel supplies p (its CmRgbArgs), LPP, XH: the feature map p.x holds _Float16, and
+// PARTS: torgb(x) before the running image is added goes to rgb_out as well.
   static_assert(LPP == 4 || LPP == 8 || LPP == 16, "lanes per pixel");
   const int sub = threadIdx.x & (LPP - 1);
   const size_t pixel = ((size_t)blockIdx.x * 256 + threadIdx.x) / LPP;
@@ -37,5 +38,12 @@
     const float sum = sub == 0 ? r0 : (sub == 1 ? r1 : r2);
     float up = 0.0f;
     if (p.img_prev) up = up_prev3(p.img_prev + ((size_t)b * 3 + sub) * (plane >> 2), p.H >> 1, p.W >> 1, oy, ox);
-    p.img_out[((size_t)b * 3 + sub) * plane + rem] = up + (sum + p.bias[sub]);
+    if (PARTS) {
+      // both stores behind every load: a load issued after a store waits for it (vmcnt retires in order)
+      const float rgb = sum + p.bias[sub];
+      rgb_out[((size_t)b * 3 + sub) * plane + rem] = rgb;
+      p.img_out[((size_t)b * 3 + sub) * plane + rem] = up + rgb;
+    } else {
+      p.img_out[((size_t)b * 3 + sub) * plane + rem] = up + (sum + p.bias[sub]);
+    }
   }

@@ -85,6 +85,9 @@ PIPELINE_SAMPLES_EXPORTS = ("migan_pipeline_batch_post_samples",)
 FP16_EXPORTS = ("comodgan_set_fp16_blocks", "comodgan_get_fp16_blocks")
 # include/comodgan_fp16_storage_hip.h
 FP16_STORAGE_EXPORTS = ("comodgan_set_fp16_storage", "comodgan_get_fp16_storage", "comodgan_debug_tensor_dtype")
+# include/comodgan_stages_hip.h
+STAGES_EXPORTS = ("comodgan_stages_workspace_bytes", "comodgan_mapping", "comodgan_encode", "comodgan_synthesize",
+                  "comodgan_weight_preparations")
 COMODGAN_DTYPE_F32, COMODGAN_DTYPE_F16 = 0, 2
 
 
@@ -147,7 +150,7 @@ class MiganLib:
         except OSError as e:  # pragma: no cover - depends on the machine
             raise MiganError(f"cannot load {self.path}: {e}") from e
         L = self.lib
-        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS:
+        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS:
             if not hasattr(L, name):
                 raise MiganError(f"{self.path} does not export {name}")
         vp, ci = C.c_void_p, C.c_int
@@ -216,6 +219,11 @@ class MiganLib:
         L.comodgan_set_fp16_storage.argtypes = [vp, ci]
         L.comodgan_get_fp16_storage.argtypes = [vp, C.POINTER(ci)]
         L.comodgan_debug_tensor_dtype.argtypes = [vp, ci, ci, C.c_char_p, C.POINTER(ci)]
+        L.comodgan_stages_workspace_bytes.argtypes = [vp, ci, ci, C.POINTER(C.c_size_t)]
+        L.comodgan_mapping.argtypes = [vp, vp, vp, ci, C.c_float, ci, vp, C.c_size_t, vp]
+        L.comodgan_encode.argtypes = [vp, vp, vp, C.POINTER(vp), ci, vp, C.c_size_t, vp]
+        L.comodgan_synthesize.argtypes = [vp, vp, C.POINTER(vp), vp, vp, ci, ci, ci, vp, C.POINTER(vp), C.POINTER(vp), vp, C.c_size_t, vp]
+        L.comodgan_weight_preparations.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.migan_last_error.restype = C.c_char_p
         L.migan_last_kernel.restype = C.c_char_p
         L.migan_nan_policy.restype = C.c_char_p
@@ -226,7 +234,7 @@ class MiganLib:
         if not allow_test_backend and L.migan_backend().decode() != PRODUCT_BACKEND:
             raise MiganError(f"{self.path} reports backend {L.migan_backend().decode()!r}, not {PRODUCT_BACKEND!r}: only the gfx950 HIP "
                              f"library is a product backend (the CPU emulator build is test infrastructure)")
-        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS:
+        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS:
             if name not in ("migan_last_error", "migan_last_kernel", "migan_nan_policy", "migan_backend", "migan_gemm_variant", "migan_tuning_key"):
                 getattr(L, name).restype = ci
 
@@ -566,6 +574,48 @@ class CoModGANHandle:
         ms = (C.c_float * n)()
         self.lib.check(self.lib.lib.comodgan_forward_samples_timed(*args, ms, n))
         return [float(v) for v in ms]
+
+    # -- include/comodgan_stages_hip.h: the three stages as calls of their own, stage tensors in caller memory
+    def levels(self) -> int:
+        """feature resolutions 4 ... R"""
+        return int(self.cfg.resolution).bit_length() - 2
+
+    def _level_ptrs(self, ptrs, what: str):
+        if ptrs is None:
+            return None
+        if len(ptrs) != self.levels():
+            raise ValueError(f"{what}: expected {self.levels()} pointers (res 4 ... {self.cfg.resolution}), got {len(ptrs)}")
+        return (C.c_void_p * len(ptrs))(*[C.c_void_p(p) if p else None for p in ptrs])
+
+    def stages_workspace_bytes(self, batch: int, samples: int = 1) -> int:
+        n = C.c_size_t()
+        self.lib.check(self.lib.lib.comodgan_stages_workspace_bytes(self._h, int(batch), int(samples), C.byref(n)))
+        return n.value
+
+    def mapping(self, z_ptr: int, ws_rows_ptr: int, rows: int, ws_ptr: int, ws_bytes: int, truncation_psi: float = 1.0,
+                truncation_cutoff: Optional[int] = None, stream: int = 0) -> None:
+        self.lib.check(self.lib.lib.comodgan_mapping(self._h, C.c_void_p(z_ptr), C.c_void_p(ws_rows_ptr), int(rows), float(truncation_psi),
+                                                     -1 if truncation_cutoff is None else int(truncation_cutoff), C.c_void_p(ws_ptr), ws_bytes,
+                                                     C.c_void_p(stream)))
+
+    def encode(self, x_ptr: int, w0_ptr: int, feat_ptrs: Sequence[int], batch: int, ws_ptr: int, ws_bytes: int, stream: int = 0) -> None:
+        """feat_ptrs: NHWC tensors for res 4, 8, ..., R"""
+        self.lib.check(self.lib.lib.comodgan_encode(self._h, C.c_void_p(x_ptr), C.c_void_p(w0_ptr), self._level_ptrs(feat_ptrs, "feats"), int(batch),
+                                                    C.c_void_p(ws_ptr), ws_bytes, C.c_void_p(stream)))
+
+    def synthesize(self, w0_ptr: int, feat_ptrs: Sequence[int], ws_rows_ptr: int, y_ptr: int, batch: int, samples: int, ws_ptr: int, ws_bytes: int,
+                   noise_mode: str = "const", noise_ptr: Optional[int] = None, to_rgb_ptrs: Optional[Sequence[int]] = None,
+                   res_img_ptrs: Optional[Sequence[int]] = None, stream: int = 0) -> None:
+        """to_rgb_ptrs / res_img_ptrs: None, or one pointer (or 0) per res 4, 8, ..., R"""
+        self.lib.check(self.lib.lib.comodgan_synthesize(
+            self._h, C.c_void_p(w0_ptr), self._level_ptrs(feat_ptrs, "feats"), C.c_void_p(ws_rows_ptr), C.c_void_p(y_ptr), int(batch), int(samples),
+            NOISE_MODES[noise_mode], C.c_void_p(noise_ptr) if noise_ptr else None, self._level_ptrs(to_rgb_ptrs, "to_rgb"),
+            self._level_ptrs(res_img_ptrs, "res_img"), C.c_void_p(ws_ptr), ws_bytes, C.c_void_p(stream)))
+
+    def weight_preparations(self) -> int:
+        n = C.c_ulonglong()
+        self.lib.check(self.lib.lib.comodgan_weight_preparations(self._h, C.byref(n)))
+        return n.value
 
     def launches(self) -> List[Dict]:
         n = C.c_int()
