@@ -189,7 +189,12 @@ int migan_pipeline_batch_post(const migan_pipeline_item* items, int n, int resol
 int migan_num_launches(const migan_handle* h, int* n);
 /* layer: reference module path ("encoder.b512.conv1", "synthesis.b8.torgb", ...);
  * kernel: kernel symbol as rocprofv3 prints it; flops / bytes: algorithmic work PER IMAGE
- * (2*MAC of every fused stage; one read of each input, one write of each output). */
+ * (2*MAC of every fused stage; one read of each input, one write of each output).
+ * Which kernel an entry names: before any forward on the handle (and again after migan_set_gemm / migan_set_debug, which re-plan), the
+ * table kernel of the plan's own tile geometry.  After a forward at the handle's own size, what that forward launched for the entry: the
+ * forms of the LAST sub-batch it launched (sub-batches of unequal size may take different forms); for migan_forward_timed, the forms of
+ * the production sub-batch, which is what it times.  The first of the two entries of a down=2 layer that ran as one fused kernel
+ * launches nothing and names that kernel.  migan_forward_hw at another size does not change what is reported. */
 int migan_launch_info(const migan_handle* h, int index, const char** layer, const char** kernel,
                       double* flops_per_image, double* mfma_flops_per_image,
                       double* bytes_per_image, int* workgroups_batch1);

@@ -441,10 +441,11 @@ inline const std::vector<Wide2Entry>& wide2_table() {
 #undef MIGAN_W2
 // the row a launch of `batch` images takes, or nullptr.  tuning().w2: 0 off | 1 weight planes DMA'd as 16-channel halves (four 16 KB slots, variant 0) |
 // 2 (default) as whole 32-channel chunks (two 32 KB slots, variant 1)
-inline const Wide2Entry* pick_wide2(const Geo& g, const SepArgs& a, int batch) {
-  if (!tuning().w2 || g.stv != 0 || g.gemmv != 2 || a.skip != nullptr) return nullptr;
+// (a: shape of the launch.  No uint8 form: only FromRGB and fused-ToRGB launches carry uint8 pointers, and neither takes this kernel)
+inline const Wide2Entry* pick_wide2(const Geo& g, const SepArgs& a, int batch, bool fused_rgb, bool has_skip) {
+  if (!tuning().w2 || g.stv != 0 || g.gemmv != 2 || has_skip) return nullptr;
   int variant;
-  if (g.mode == MODE_NORMAL && g.wide && !g.fromrgb && a.trgb_w == nullptr && a.u8_img == nullptr) variant = tuning().w2 == 1 ? 0 : 1;
+  if (g.mode == MODE_NORMAL && g.wide && !g.fromrgb && !fused_rgb) variant = tuning().w2 == 1 ? 0 : 1;
   else if (g.mode == MODE_PW && g.maing && tuning().w2_pw) variant = 3;
   else return nullptr;
   if (a.H % 16 != 0 || a.W % 16 != 0 || a.CI % 64 != 0 || a.CO % 256 != 0) return nullptr;      // whole 16 x 16 tiles
@@ -459,13 +460,6 @@ inline const KernelEntry& pick_kernel(const Geo& g) {
         e.MINW == g.MINW && e.maing == g.maing && e.persist == g.persist && e.gemmv == g.gemmv && e.torgb == g.torgb && e.stv == g.stv)
       return e;
   throw Error(MIGAN_EINVAL, "internal: no kernel instantiation for this geometry");
-}
-
-inline const char* kernel_name(const Geo& g) { return g.wide ? wide_entry(g).name : pick_kernel(g).name; }
-
-// persistent variants exist where they fit the register budget without spilling
-inline bool has_persistent_variant(const Geo& g) {
-  return g.maing && ((g.NT == 64 && g.mode != MODE_PW && (g.KC == 16 || g.MINW == 2)) || (g.mode == MODE_PW && g.NT == 128 && g.MINW == 2));
 }
 
 // ---- depthwise + FIR-down kernel (first half of down=2 layers) ----
@@ -533,7 +527,7 @@ inline const RgbEntry& torgb_entry(int stv) {
 // layers with fewer than 64 channels (resolutions above 512): one plain kernel per (down / up, fromrgb)
 // (the tiled kernels take Cin % 32 == 0 and Cout % 64 == 0: choose_geo)
 inline bool is_narrow(int cin, int cout) { return cin % 32 != 0 || cout % 64 != 0; }
-// (dynamic LDS: the 18 x 18 x Cout fp32 tile of the FIR-up form, 81 KiB at Cout = 64: launch_narrow; the other forms take none)
+// (dynamic LDS: the 18 x 18 x Cout fp32 tile of the FIR-up form, 81 KiB at Cout = 64: resolve_layer; the other forms take none)
 struct NarrowEntry { int mode; bool fromrgb; SepKernelFn fn; const char* name; size_t max_lds; };
 #define MIGAN_N(MODE, RGB) {MODE, RGB, narrow_sepconv_kernel<MODE, RGB>, "migan::narrow_sepconv_kernel<" #MODE ", " #RGB ">", kLds96}
 inline const std::vector<NarrowEntry>& narrow_table() {
@@ -546,22 +540,6 @@ inline const NarrowEntry& narrow_entry(int mode, bool fromrgb) {
   for (const NarrowEntry& e : narrow_table())
     if (e.fromrgb == fromrgb && (fromrgb || e.mode == mode)) return e;      // (FromRGB: the plain form, whatever the mode)
   throw Error(MIGAN_EINVAL, "internal: no narrow kernel for this mode");
-}
-
-// (a.B / H / W / HO / WO / CI / CO set by the caller)
-inline const char* launch_narrow(int mode, bool fromrgb, SepArgs a, rt::stream_t stream) {
-  unsigned grid;
-  size_t lds = 0;
-  if (mode == MODE_UP) {           // one workgroup per 16 x 16 low-resolution pixels, their 18 x 18 1x1 outputs in LDS
-    a.tiles_x = cdiv(a.W, kNarrowUpTile); a.tiles_y = cdiv(a.H, kNarrowUpTile);
-    grid = (unsigned)(a.tiles_x * a.tiles_y * a.B);
-    lds = (size_t)(kNarrowUpTile + 2) * (kNarrowUpTile + 2) * a.CO * sizeof(float);
-  } else {                         // one thread per output pixel
-    grid = (unsigned)(((size_t)a.B * a.HO * a.WO + kThreads - 1) / kThreads);
-  }
-  const NarrowEntry& e = narrow_entry(mode, fromrgb);
-  rt_check(rt::launch(e.fn, a, grid, kThreads, lds, stream), e.name);
-  return last_kernel_ref() = e.name;
 }
 
 // Raise the dynamic-LDS limit of every instantiation (tiles use up to 145 KiB).  The attribute is per device, so
@@ -627,35 +605,16 @@ inline std::vector<ProfRow>& prof_layers() {
 }
 #endif
 
-// Parameters of one SeparableConv2d and of the FromRGB / ToRGB fused around it (null: absent), wherever they live: plan slots or a migan_sepconv_desc
-struct SepParams {
-  const float *wdw = nullptr, *bdw = nullptr, *wpw = nullptr;
+// Every pointer the launches of one SeparableConv2d take (null: absent), wherever it lives: plan slots and workspace buffers, or a migan_sepconv_desc
+struct LayerPtrs {
+  const void *x = nullptr, *skip = nullptr;
+  void* y = nullptr;
+  const float *wdw = nullptr, *bdw = nullptr, *wpw = nullptr, *noise = nullptr, *noise_strength = nullptr;
   const unsigned short* wsplit = nullptr;      // null: the exact-fp32 GEMM
-  const float *noise = nullptr, *noise_strength = nullptr, *frgb_w = nullptr, *frgb_b = nullptr, *trgb_w = nullptr, *trgb_b = nullptr, *img_prev = nullptr;
+  const float *frgb_w = nullptr, *frgb_b = nullptr, *trgb_w = nullptr, *trgb_b = nullptr, *img_prev = nullptr;
   float* img_out = nullptr;
+  const migan_io_u8 *u8_in = nullptr, *u8_out = nullptr;      // migan_forward_u8, where x is the network's input / img_out its output
 };
-// tensor and shape part of a launch's SepArgs (tile geometry: fill_geo or the launcher; uint8 I/O pointers: the caller)
-inline SepArgs sep_args(const SepParams& p, const void* x, void* y, const void* skip, int B, int H, int W, int CI, int CO, int HO, int WO) {
-  SepArgs a{};
-  a.x = x; a.y = y; a.skip = skip;
-  a.wdw = p.wdw; a.bdw = p.bdw; a.wpw = p.wpw; a.wsplit = p.wsplit;
-  a.noise = p.noise; a.noise_strength = p.noise_strength;
-  a.frgb_w = p.frgb_w; a.frgb_b = p.frgb_b;
-  a.trgb_w = p.trgb_w; a.trgb_b = p.trgb_b;
-  a.img_prev = p.img_prev; a.img_out = p.img_out;
-  a.B = B; a.H = H; a.W = W; a.CI = CI; a.CO = CO; a.HO = HO; a.WO = WO;
-  return a;
-}
-
-inline void fill_geo(SepArgs& a, const Geo& g) {
-  a.lgGH = g.lgGH; a.lgGW = g.lgGW; a.lgIMGS = g.lgIMGS;
-  a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y; a.nchunks = g.nchunks;
-  a.sy = g.sy; a.sx = g.sx; a.off = g.off; a.lgRS = g.lgRS;
-  a.off_a = g.off_a; a.off_b = g.off_b; a.off_v = g.off_v; a.off_rgb = g.off_rgb; a.off_w = g.off_w;
-  a.b_stride = g.b_stride;
-  a.a_stride = g.a_stride;
-  a.prof = prof_buffer();
-}
 
 inline unsigned tiles_of(const Geo& g, int batch) {
   return (unsigned)(g.tiles_x * g.tiles_y * cdiv(batch, 1 << g.lgIMGS) * g.nchunks);
@@ -668,41 +627,64 @@ inline bool use_persistent(const Geo& g, int batch, bool fused_rgb) {
   // 16-bit storage: the one-tile FIR-up kernel needs 164 VGPRs / 41 KB of LDS, i.e. three workgroups per CU, and beats its
   // persistent form (226 VGPRs, two per CU): synthesis.b512.conv1 0.81 -> 0.64 ms (profiles/r02_w3_and_persistence_sweep.txt)
   if (g.stv != 0 && g.mode == MODE_UP) return false;
-  return has_persistent_variant(g) && !fused_rgb && total >= tuning().persist_min && total > tuning().persist_grid;
+  // persistent variants exist where they fit the register budget without spilling
+  const bool exists = g.maing && ((g.NT == 64 && g.mode != MODE_PW && (g.KC == 16 || g.MINW == 2)) || (g.mode == MODE_PW && g.NT == 128 && g.MINW == 2));
+  return exists && !fused_rgb && total >= tuning().persist_min && total > tuning().persist_grid;
 }
 inline unsigned grid_of(const Geo& g, int batch, bool fused_rgb = false) {
   return use_persistent(g, batch, fused_rgb) ? (unsigned)tuning().persist_grid : tiles_of(g, batch);
 }
 
-// One fused-SeparableConv2d launch, decided: what rt::launch gets, and the symbol that migan_last_kernel / migan_launch_info report.
-struct SepLaunch {
-  SepKernelFn fn;
-  const char* name;
-  unsigned grid, threads;
-  size_t lds_bytes;
-  SepArgs args;                    // the caller's, with what the chosen family lays out itself overridden
+// ------------------------------------------------------------------------------------------------
+// What one SeparableConv2d becomes on the device: a pure host decision (no device pointer, no device, no side effect), taken in resolve_layer
+// alone.  The generator plan (Plan::resolve, per sub-batch) and migan_sepconv_forward launch, and report, what it returns.
+
+// One SeparableConv2d as its caller wants it, with the tile geometry chosen for it (build_plan: at plan time; migan_sepconv_forward: per call)
+struct LayerDesc {
+  int mode = MODE_NORMAL;              // the layer's own: MODE_NORMAL, MODE_DOWN (down=2) or MODE_UP
+  int cin = 0, cout = 0, hin = 0, win = 0, hout = 0, wout = 0;
+  bool fromrgb = false, torgb = false; // FromRGB fused in front; ToRGB wanted behind (fused where one workgroup owns all of Cout, else torgb_kernel)
+  bool skip = false, noise = false, out_dead = false;      // out_dead: no later launch reads the feature map (Launch::out_dead)
+  const Geo* g = nullptr;              // tile of a NORMAL / UP layer or of the pointwise half of a down=2 layer, with the layer's stv and gemmv (!= 0: the
+                                       // 16-bit weight planes exist); null: a narrow layer (is_narrow; fp32 storage, conv2.weight read in fp32)
+  const Geo* small = nullptr; int n_small = 0;      // small-tile variants that may replace g, smallest tile first (none: small tiles not allowed)
+  const DwGeo* dg = nullptr;           // down=2: tile of dwfir_kernel
 };
-// The kernel family of a launch, first match: pipelined persistent form, 256 x 256 tile, 128 x 256 wide tile, sepconv_kernel table.
-// n_decide: the batch the kernel FORM is chosen for (0 = a.B); grids are sized for a.B, the batch actually launched.  The per-launch timing run
-// launches the whole batch at once but must time the forms the production forward -- sub-batches on staggered streams -- launches.
-// out_dead: no later launch reads a.y (Launch::out_dead); a form whose fused ToRGB tail can run without writing the feature map gets y = nullptr and
-// skips that store, every other form keeps the pointer and stores.  The network output is the same bits either way.
-inline SepLaunch resolve_sepconv(Geo g, const SepArgs& a, int n_decide = 0, bool out_dead = false) {
-  const bool fused_rgb = a.trgb_w != nullptr;
-  const int nd = n_decide > 0 ? n_decide : a.B;
+// One launch, decided: what rt::launch gets but the pointers, and the symbol migan_last_kernel / migan_launch_info report.
+enum LaunchKind : int { K_NONE, K_SEP, K_DWFIR, K_RGB };      // the argument struct it takes; K_NONE: nothing to launch
+struct Resolved {
+  LaunchKind kind = K_NONE;
+  union { SepKernelFn sep; DwFirKernelFn dw; RgbKernelFn rgb; } fn{};
+  const char* name = "";
+  unsigned grid = 0, threads = 0; size_t lds_bytes = 0;
+  bool whole_down = false;           // sepconv_pipedown_kernel: the whole down=2 layer, reading the LAYER's input (no dwfir scratch)
+  bool drop_y = false;               // the fused ToRGB tail runs without writing the feature map: y = nullptr
+  union { SepArgs sep; DwFirArgs dw; RgbArgs rgb; } args{};      // shape and geometry; every pointer null
+};
+inline Resolved sep_launch(SepKernelFn fn, const char* name, unsigned grid, unsigned threads, size_t lds_bytes, const SepArgs& a) {
+  Resolved r;
+  r.kind = K_SEP; r.fn.sep = fn; r.name = name; r.grid = grid; r.threads = threads; r.lds_bytes = lds_bytes; r.args.sep = a;
+  return r;
+}
+
+// The kernel family of a tiled launch, first match: pipelined persistent form, 256 x 256 tile, 128 x 256 wide tile (fp16 GEMM variants only, whose
+// weight planes exist), sepconv_kernel table.
+// a: shape and geometry of g.  nd: the batch the kernel FORM is chosen for; grids are sized for a.B, the batch actually launched.  The per-launch
+// timing run launches the whole batch at once but must time the forms the production forward -- sub-batches on staggered streams -- launches
+// (ADVICE round 4).  d.out_dead: a form whose fused ToRGB tail can run without writing the feature map skips that store (drop_y), every other
+// form stores.  The network output is the same bits either way.
+inline Resolved resolve_sepconv(Geo g, const SepArgs& a, const LayerDesc& d, bool fused_rgb, int nd) {
   const unsigned pipe_grid = (unsigned)tuning().pipe_grid;
-  if (const PipeEntry* pe = pick_pipe(g, a.CI, a.CO, nd, fused_rgb, a.skip != nullptr)) {
-    MIGAN_CHECK(a.wsplit != nullptr, MIGAN_EINVAL, "internal: the pipelined kernel needs the fp16 weight planes");
-    SepLaunch l{pe->fn, pe->name, 0, (unsigned)pipe_threads(pe->na), pe->lds_bytes, a};
-    l.args.nchunks = a.CO / pe->NT;                      // (FIR-up: 64-column chunks, see pick_pipe)
-    if (out_dead && pe->torgb) l.args.y = nullptr;       // sepconv_pipe_kernel<MODE_NORMAL, ..., TORGB = true, ...>: finish_block tests p.y
-    l.grid = std::min((unsigned)(g.tiles_x * g.tiles_y * l.args.nchunks * a.B), pipe_grid);
+  if (const PipeEntry* pe = pick_pipe(g, a.CI, a.CO, nd, fused_rgb, d.skip)) {
+    Resolved l = sep_launch(pe->fn, pe->name, 0, (unsigned)pipe_threads(pe->na), pe->lds_bytes, a);
+    l.args.sep.nchunks = a.CO / pe->NT;                  // (FIR-up: 64-column chunks, see pick_pipe)
+    l.drop_y = d.out_dead && pe->torgb;                  // sepconv_pipe_kernel<MODE_NORMAL, ..., TORGB = true, ...>: finish_block tests p.y
+    l.grid = std::min((unsigned)(g.tiles_x * g.tiles_y * l.args.sep.nchunks * a.B), pipe_grid);
     return l;
   }
-  if (const Wide2Entry* we = pick_wide2(g, a, nd)) {
-    MIGAN_CHECK(a.wsplit != nullptr, MIGAN_EINVAL, "internal: the 256 x 256 tile kernel needs the fp16 weight planes");
-    SepLaunch l{we->fn, we->name, 0, (unsigned)kW2Threads, (size_t)W2Lds::TOTAL, a};
-    SepArgs& aw = l.args;
+  if (const Wide2Entry* we = pick_wide2(g, a, nd, fused_rgb, d.skip)) {
+    Resolved l = sep_launch(we->fn, we->name, 0, (unsigned)kW2Threads, (size_t)W2Lds::TOTAL, a);
+    SepArgs& aw = l.args.sep;
     aw.tiles_x = a.W / 16; aw.tiles_y = a.H / 16; aw.nchunks = a.CO / 256;
     aw.sy = 16; aw.sx = 16; aw.off = 0;
     l.grid = std::min((unsigned)(aw.tiles_x * aw.tiles_y * aw.nchunks * a.B), pipe_grid);
@@ -713,64 +695,130 @@ inline SepLaunch resolve_sepconv(Geo g, const SepArgs& a, int n_decide = 0, bool
   MIGAN_CHECK(!fused_rgb || (g.mode == MODE_NORMAL && !g.fromrgb && g.nchunks == 1), MIGAN_EINVAL,
               "ToRGB can only be fused into a plain layer whose output channels fit one column tile");
   if (g.wide) {
-    MIGAN_CHECK(a.wsplit != nullptr, MIGAN_EINVAL, "internal: the wide kernel needs the fp16 weight planes");
     const WideEntry& e = wide_entry(g);
-    return SepLaunch{e.fn, e.name, tiles_of(g, a.B), (unsigned)kWideThreads, g.lds_bytes, a};
+    return sep_launch(e.fn, e.name, tiles_of(g, a.B), (unsigned)kWideThreads, g.lds_bytes, a);
   }
   const KernelEntry& k = pick_kernel(g);
-  return SepLaunch{k.fn, k.name, grid_of(g, a.B, fused_rgb), (unsigned)kThreads, g.lds_bytes, a};
-}
-// returns the symbol it launched
-inline const char* launch_sepconv(const Geo& g, const SepArgs& a, rt::stream_t stream, int n_decide = 0, bool out_dead = false) {
-  prepare_kernels();
-  const SepLaunch l = resolve_sepconv(g, a, n_decide, out_dead);
-  rt_check(rt::launch(l.fn, l.args, l.grid, l.threads, l.lds_bytes, stream), l.name);
-  return last_kernel_ref() = l.name;
+  return sep_launch(k.fn, k.name, grid_of(g, a.B, fused_rgb), (unsigned)kThreads, g.lds_bytes, a);
 }
 
-// The fused form of the down=2 layer `a` describes (x, H, W: the layer's own input), or nullptr: dwfir_kernel + pointwise GEMM.
-// sepconv_pipedown_kernel has no FromRGB / ToRGB / noise / skip and needs the fp16 weight planes.
-inline const DownEntry* pick_fused_down(const SepArgs& a, int n_decide, int stv, int gemmv) {
-  if (a.frgb_w || a.trgb_w || a.noise || a.skip || a.wsplit == nullptr) return nullptr;
-  return pick_pipedown(a.CI, a.CO, a.H, a.W, n_decide, stv, gemmv);
+// The launches layer d becomes for n images (kernel forms chosen for nd: resolve_sepconv), in order, into out[]; returns how many.  A tiled
+// down=2 layer is two (dwfir_kernel + pointwise GEMM; or nothing, named after the fused kernel, + that kernel), a ToRGB that does not fuse one more.
+constexpr int kMaxLayerLaunches = 3;
+inline int resolve_layer(const LayerDesc& d, int n, int nd, Resolved out[kMaxLayerLaunches]) {
+  SepArgs a{};
+  a.B = n; a.H = d.hin; a.W = d.win; a.CI = d.cin; a.CO = d.cout; a.HO = d.hout; a.WO = d.wout;
+  if (d.g == nullptr) {              // fewer than 64 channels: the plain kernel, the whole layer (its ToRGB included) in one launch
+    unsigned grid = (unsigned)(((size_t)a.B * a.HO * a.WO + kThreads - 1) / kThreads);      // one thread per output pixel
+    size_t lds = 0;
+    if (d.mode == MODE_UP) {         // one workgroup per 16 x 16 low-resolution pixels, their 18 x 18 1x1 outputs in LDS
+      a.tiles_x = cdiv(a.W, kNarrowUpTile); a.tiles_y = cdiv(a.H, kNarrowUpTile);
+      grid = (unsigned)(a.tiles_x * a.tiles_y * a.B);
+      lds = (size_t)(kNarrowUpTile + 2) * (kNarrowUpTile + 2) * a.CO * sizeof(float);
+    }
+    const NarrowEntry& e = narrow_entry(d.mode, d.fromrgb);
+    out[0] = sep_launch(e.fn, e.name, grid, kThreads, lds, a);
+    return 1;
+  }
+  int k = 0;
+  if (d.mode == MODE_DOWN) {
+    // sepconv_pipedown_kernel (depthwise + FIR-down feed the 1x1 through LDS) has no FromRGB / ToRGB / noise / skip and needs the fp16 planes
+    const bool plain = !d.fromrgb && !d.torgb && !d.noise && !d.skip;
+    if (const DownEntry* e = plain ? pick_pipedown(d.cin, d.cout, d.hin, d.win, nd, d.g->stv, d.g->gemmv) : nullptr) {
+      (out[0] = Resolved()).name = e->name;      // (the bytes of this plan entry belong to that launch)
+      a.tiles_x = a.W / 32; a.tiles_y = a.H / 8; a.nchunks = 1;
+      const unsigned grid = std::min((unsigned)(a.tiles_x * a.tiles_y * a.B), (unsigned)tuning().pipe_grid);
+      out[1] = sep_launch(e->fn, e->name, grid, (unsigned)((e->na + e->nb) * 64), e->lds_bytes, a);
+      out[1].whole_down = true;
+      return 2;
+    }
+    // reference :155-161: depthwise + act + FIR at the input size (dwfir_kernel), then the 1x1 at half of it
+    const DwGeo& g = *d.dg;
+    Resolved& r = out[k++] = Resolved();
+    DwFirArgs& f = r.args.dw;
+    f.B = n; f.H = d.hin; f.W = d.win; f.C = d.cin; f.lgGH = g.lgGH; f.lgGW = g.lgGW; f.lgIMGS = g.lgIMGS;
+    f.tiles_x = g.tiles_x; f.tiles_y = g.tiles_y; f.nkg = g.nkg; f.kpw = g.kpw; f.off_d = g.off_d; f.off_w = g.off_w;
+    // small launches (single-image latency, the <= 16x16 layers): fewer 16-channel chunks per workgroup, more workgroups, as long as
+    // the launch stays within the small-launch threshold (same reasoning as MIGAN_GEOMETRIES_SMALL)
+    r.grid = dwfir_grid(g, n);
+    if (tuning().small && tuning().small_dwfir)
+      while (f.kpw > 1 && r.grid * 2 <= (unsigned)tuning().small_max_wgs) { f.kpw /= 2; f.nkg *= 2; r.grid *= 2; }
+    const DwFirEntry& e = dwfir_entry(g, dwfir_variant(d.g->stv, d.g->gemmv));
+    r.kind = K_DWFIR; r.fn.dw = e.fn; r.name = e.name; r.threads = kThreads; r.lds_bytes = g.lds_bytes;
+  }
+  // one workgroup owns all output channels of its pixels (cout <= 128, or 256 on whole 8x16 tiles): ToRGB fuses into the epilogue
+  const bool fused_rgb = d.torgb && d.g->nchunks == 1;
+  // launches that would leave most CUs idle run the 32-row tiles: a quarter of the work per workgroup, four times the workgroups
+  const Geo* g = d.g;
+  for (int i = 0; !fused_rgb && i < d.n_small; ++i) {
+    const Geo& gs = d.small[i];
+    // K-split tiles sum K in another order than every other tile (four partial sums): single-image forwards only, so that an
+    // image of a batch of two or more is bit-identical whatever the batch size and the sub-batch grouping
+    if (gs.NT == 32 && nd != 1) continue;
+    if ((int)tiles_of(gs, nd) <= tuning().small_max_wgs) { g = &gs; break; }
+  }
+  if (d.mode == MODE_DOWN) { a.H = d.hout; a.W = d.wout; }      // the pointwise GEMM runs at the output size, on dwfir_kernel's output
+  a.lgGH = g->lgGH; a.lgGW = g->lgGW; a.lgIMGS = g->lgIMGS; a.lgRS = g->lgRS;
+  a.tiles_x = g->tiles_x; a.tiles_y = g->tiles_y; a.nchunks = g->nchunks; a.sy = g->sy; a.sx = g->sx; a.off = g->off;
+  a.off_a = g->off_a; a.off_b = g->off_b; a.off_v = g->off_v; a.off_rgb = g->off_rgb; a.off_w = g->off_w;
+  a.b_stride = g->b_stride; a.a_stride = g->a_stride;
+  out[k++] = resolve_sepconv(*g, a, d, fused_rgb, nd);
+  if (d.torgb && !fused_rgb) {                   // torgb_kernel on y afterwards
+    Resolved& r = out[k++] = Resolved();
+    r.args.rgb.B = n; r.args.rgb.H = d.hout; r.args.rgb.W = d.wout; r.args.rgb.C = d.cout;
+    const RgbEntry& e = torgb_entry(d.g->stv);
+    r.kind = K_RGB; r.fn.rgb = e.fn; r.name = e.name; r.threads = kThreads;
+    r.grid = (unsigned)(((size_t)n * d.hout * d.wout * 16 + kThreads - 1) / kThreads);
+  }
+  return k;
 }
-inline const char* launch_pipedown(const DownEntry& e, SepArgs a, rt::stream_t stream) {
-  prepare_kernels();
-  MIGAN_CHECK(a.wsplit != nullptr, MIGAN_EINVAL, "internal: the fused down=2 kernel needs the fp16 weight planes");
-  a.tiles_x = a.W / 32; a.tiles_y = a.H / 8; a.nchunks = 1;
-  a.prof = prof_buffer();
-  const unsigned tiles = (unsigned)(a.tiles_x * a.tiles_y * a.B);
-  rt_check(rt::launch(e.fn, a, std::min(tiles, (unsigned)tuning().pipe_grid), (unsigned)((e.na + e.nb) * 64), e.lds_bytes, stream), e.name);
-  return last_kernel_ref() = e.name;
+// launches what resolve_layer decided: the pointers go in here
+template <class Args>
+inline void set_u8(Args& a, const migan_io_u8& u8, bool output) {
+  a.u8_img = (const unsigned char*)u8.img; a.u8_mask = (const unsigned char*)u8.mask;
+  if (output) a.u8_out = (unsigned char*)u8.out;
 }
-inline void launch_dwfir(const DwGeo& g, DwFirArgs a, rt::stream_t stream, int stv = 0) {
-  prepare_kernels();
-  a.lgGH = g.lgGH; a.lgGW = g.lgGW; a.lgIMGS = g.lgIMGS;
-  a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y; a.nkg = g.nkg; a.kpw = g.kpw;
-  a.off_d = g.off_d; a.off_w = g.off_w;
-  // small launches (single-image latency, the <= 16x16 layers): fewer 16-channel chunks per workgroup, more workgroups, as long as
-  // the launch stays within the small-launch threshold (same reasoning as MIGAN_GEOMETRIES_SMALL)
-  unsigned grid = dwfir_grid(g, a.B);
-  if (tuning().small && tuning().small_dwfir)
-    while (a.kpw > 1 && grid * 2 <= (unsigned)tuning().small_max_wgs) { a.kpw /= 2; a.nkg *= 2; grid *= 2; }
-  const DwFirEntry& e = dwfir_entry(g, stv);
-  rt_check(rt::launch(e.fn, a, grid, kThreads, g.lds_bytes, stream), e.name);
+inline void launch(const Resolved& r, const LayerPtrs& q, rt::stream_t stream) {
+  if (r.kind == K_SEP) {
+    SepArgs a = r.args.sep;
+    a.x = q.x; a.y = r.drop_y ? nullptr : q.y; a.skip = q.skip;
+    a.wdw = q.wdw; a.bdw = q.bdw; a.wpw = q.wpw; a.wsplit = q.wsplit; a.noise = q.noise; a.noise_strength = q.noise_strength;
+    a.frgb_w = q.frgb_w; a.frgb_b = q.frgb_b; a.trgb_w = q.trgb_w; a.trgb_b = q.trgb_b; a.img_prev = q.img_prev; a.img_out = q.img_out;
+    a.prof = prof_buffer();
+    if (q.u8_in) set_u8(a, *q.u8_in, false);                     // the FromRGB head builds x from the uint8 image and mask
+    if (q.u8_out && a.trgb_w) set_u8(a, *q.u8_out, true);         // the fused ToRGB tail composes and writes uint8
+    rt_check(rt::launch(r.fn.sep, a, r.grid, r.threads, r.lds_bytes, stream), r.name);
+    last_kernel_ref() = r.name;
+  } else if (r.kind == K_DWFIR) {
+    DwFirArgs a = r.args.dw;
+    a.x = q.x; a.y = (float*)q.y; a.wdw = q.wdw; a.bdw = q.bdw;
+    rt_check(rt::launch(r.fn.dw, a, r.grid, r.threads, r.lds_bytes, stream), r.name);
+  } else if (r.kind == K_RGB) {
+    RgbArgs a = r.args.rgb;
+    a.x = q.x; a.w = q.trgb_w; a.b = q.trgb_b; a.img_prev = q.img_prev; a.img_out = q.img_out;
+    if (q.u8_out) set_u8(a, *q.u8_out, true);
+    rt_check(rt::launch(r.fn.rgb, a, r.grid, r.threads, r.lds_bytes, stream), r.name);
+  }
 }
 
 // 16-bit elements one tensor occupies in a weight-split buffer: header + planes, rounded to 16 bytes
 inline size_t wsplit_elems_of(int cin, int cout) {
   return (size_t)kSplitHeader + (((size_t)3 * cin * cout + 7) & ~(size_t)7);
 }
+// conv2.weight tensors -> 16-bit operand planes of GEMM variant gemmv (!= 0), one launch for all of them
+inline SplitArgs split_args(unsigned short* dst, int gemmv) {
+  SplitArgs sa{};
+  sa.dst = dst; sa.f16 = gemmv == 3 ? 2 : (gemmv == 2 ? 1 : 0);
+  return sa;
+}
+inline void add_split(SplitArgs& sa, const float* src, size_t dst_off, int cin, int cout) {
+  MIGAN_CHECK(sa.n < 40, MIGAN_EINVAL, "internal: too many layers for the weight-split table");
+  sa.src[sa.n] = src; sa.dst_off[sa.n] = dst_off; sa.count[sa.n] = (unsigned)(cin * cout); sa.ci[sa.n] = (unsigned)cin;
+  ++sa.n;
+}
 inline void launch_split(const SplitArgs& a, rt::stream_t stream) {
   if (a.f16) rt_check(rt::launch(weight_absmax_kernel, a, (unsigned)a.n, kThreads, 4 * sizeof(float), stream), "migan::weight_absmax_kernel");
   rt_check(rt::launch(split_weights_kernel, a, (unsigned)(a.n * kSplitBlocksPerTensor), kThreads, 0, stream), "migan::split_weights_kernel");
-}
-
-inline void launch_torgb(const RgbArgs& a, rt::stream_t stream, int stv = 0) {
-  const size_t npix = (size_t)a.B * a.H * a.W;
-  const unsigned grid = (unsigned)((npix * 16 + kThreads - 1) / kThreads);
-  const RgbEntry& e = torgb_entry(stv);
-  rt_check(rt::launch(e.fn, a, grid, kThreads, 0, stream), e.name);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -840,8 +888,7 @@ struct Buf {
 enum : int { BUF_NONE = -1, BUF_X = -2, BUF_Y = -3 };
 
 struct Launch {
-  std::string layer, kernel;
-  mutable std::string kernel_last;   // kernel symbol actually launched by the last forward (persistent variant or not)
+  std::string layer, kernel;         // (kernel: the table name of the plan's own geometry; what a forward launches: Plan::resolve)
   bool is_rgb = false;
   bool is_dwfir = false;
   bool narrow = false;               // fewer than 64 channels on either side (resolutions above 512): narrow_sepconv_kernel<mode, fromrgb>
@@ -850,7 +897,7 @@ struct Launch {
   bool out_dead = false;             // ToRGB is fused into this launch and no later launch reads out_buf: the feature map need not be written
   Geo g;
   std::vector<Geo> g_small;          // small-tile variants of g, smallest tile first: the first one whose tile count for the launch is at
-                                     // most tuning().small_max_wgs runs instead of g
+                                     // most tuning().small_max_wgs runs instead of g (resolve_layer)
   DwGeo dg;
   int cin = 0, cout = 0, hin = 0, win = 0, hout = 0, wout = 0;
   int in_buf = BUF_NONE, out_buf = BUF_NONE, skip_buf = BUF_NONE, imgprev_buf = BUF_NONE, imgout_buf = BUF_NONE;
@@ -872,6 +919,30 @@ struct Plan {
   size_t shared_bytes = 0;
   size_t wsplit_elems = 0;
   int stagger = 0;                   // launch index of the first sub-batch after which the second one starts
+  // What a launch of n images runs, one record per entry of `launches` (kernel forms chosen for nd images: resolve_sepconv).  Not cached: the
+  // knobs may change between forwards, and resolving is a few table look-ups per entry.  A SeparableConv2d is the entry that carries its GEMM,
+  // the dwfir entry in front of it (down=2) and the ToRGB entry behind it (where ToRGB does not fuse): resolve_layer decides them together.
+  std::vector<Resolved> resolve(int n, int nd) const {
+    std::vector<Resolved> out(launches.size() + kMaxLayerLaunches);      // (room for whatever the last layer resolves to)
+    for (size_t li = 0; li < launches.size();) {
+      const Launch& F = launches[li];
+      MIGAN_CHECK(!F.is_rgb && (!F.is_dwfir || li + 1 < launches.size()), MIGAN_EINVAL, "internal: plan entry without its SeparableConv2d");
+      const size_t si = F.is_dwfir ? li + 1 : li;
+      const Launch& L = launches[si];
+      const bool rgb_behind = si + 1 < launches.size() && launches[si + 1].is_rgb;
+      LayerDesc d;
+      d.mode = F.is_dwfir ? MODE_DOWN : L.mode;
+      d.cin = L.cin; d.cout = L.cout; d.hin = F.hin; d.win = F.win; d.hout = L.hout; d.wout = L.wout;
+      d.fromrgb = L.fromrgb; d.torgb = L.w_trgb >= 0 || rgb_behind; d.skip = L.skip_buf != BUF_NONE; d.noise = L.w_noise >= 0; d.out_dead = L.out_dead;
+      if (!L.narrow) { d.g = &L.g; d.small = L.g_small.data(); d.n_small = (int)L.g_small.size(); }
+      if (F.is_dwfir) d.dg = &F.dg;
+      const int k = resolve_layer(d, n, nd, &out[li]);
+      MIGAN_CHECK(k == (int)(si - li) + 1 + (rgb_behind ? 1 : 0), MIGAN_EINVAL, "internal: layer " + L.layer + " resolves to other launches than its plan entries");
+      li += (size_t)k;
+    }
+    out.resize(launches.size());
+    return out;
+  }
 };
 
 inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
@@ -889,6 +960,7 @@ struct migan_handle {
   migan::Plan plan;                   // H = W = resolution
   std::vector<migan::Plan> hw_plans;  // migan_forward_hw sizes seen so far
   std::vector<rt::event_t> events;
+  std::vector<const char*> launched;  // symbols of the launch list resolved last for `plan` (migan_launch_info); empty: no forward since rebuild()
   // two-stream execution
   static constexpr int kMaxStreams = 4;
   rt::stream_t aux_stream[kMaxStreams - 1]{};
@@ -923,6 +995,7 @@ struct migan_handle {
   void rebuild() {
     build_plan(plan, resolution, resolution);
     hw_plans.clear();
+    launched.clear();
     prepared_epoch = 0;
   }
   migan::Plan& plan_for(int H, int W);
@@ -955,7 +1028,7 @@ struct migan_handle {
   }
   void ensure_aux();
   void run_range(const migan::Plan& P, const float* x, float* y, int n, char* sub_ws, char* shared, rt::stream_t stream,
-                 bool timed, int mid_after, int part, const migan_io_u8* u8, int n_geo = 0);
+                 bool timed, int mid_after, int part, const migan_io_u8* u8, int nd);
   // parts (migan_forward_parts): sub-batch k writes its images to parts->y[k] and, for k >= 1, runs on the CALLER's stream parts->streams[k - 1]
   // instead of the handle's own; the streams are not joined (the caller orders whatever follows behind each of them)
   struct Parts {
@@ -1058,7 +1131,7 @@ inline void migan_handle::build_plan(migan::Plan& P, int H, int W) const {
     } else {
       L.g = choose_geo(mode, cin, cout, L.hin, L.win, fromrgb, with_torgb, gemm, stv);
       L.g.torgb = with_torgb && L.g.nchunks == 1;        // one workgroup owns all channels of its pixels: ToRGB fuses
-      L.kernel = kernel_name(L.g);
+      L.kernel = L.g.wide ? wide_entry(L.g).name : pick_kernel(L.g).name;
     }
     if (!L.narrow && tuning().small && has_small_tiles(gemm, stv) && !fromrgb && !L.g.torgb && cout % 128 == 0 &&
         (mode == MODE_UP || (L.hin % 4 == 0 && L.win % (L.hin == 4 && L.win == 4 ? 4 : 8) == 0))) {
@@ -1171,10 +1244,8 @@ inline void migan_handle::build_plan(migan::Plan& P, int H, int W) const {
       l2.imgprev_buf = img_cur; l2.imgout_buf = img_out;
       l2.flops += rgb_flops; l2.bytes += rgb_bytes;
     } else if (l2.g.nchunks == 1) {
-      // one workgroup owns all output channels of its pixels: ToRGB fused into the conv2 epilogue
+      // one workgroup owns all output channels of its pixels: ToRGB fused into the conv2 epilogue (add_sep set g.torgb and named that kernel)
       l2.w_trgb = wt; l2.b_trgb = bt;
-      l2.g.torgb = true;
-      l2.kernel = kernel_name(l2.g);
       l2.imgprev_buf = img_cur; l2.imgout_buf = img_out;
       l2.flops += rgb_flops; l2.bytes += rgb_bytes;
     } else {
@@ -1249,9 +1320,10 @@ inline void migan_handle::ensure_aux() {
   aux_ready = true;
 }
 
-// launches of one sub-batch of n images on `stream`
+// launches of one sub-batch of n images on `stream`.  nd: the batch the kernel forms are chosen for -- the per-launch timing run covers the whole
+// batch in one launch but must time the forms the production forward launches for its sub-batches
 inline void migan_handle::run_range(const migan::Plan& P, const float* x, float* y, int n, char* sub_ws, char* shared,
-                                    rt::stream_t stream, bool timed, int mid_after, int part, const migan_io_u8* u8, int n_geo) {
+                                    rt::stream_t stream, bool timed, int mid_after, int part, const migan_io_u8* u8, int nd) {
   using namespace migan;
   std::vector<size_t> offs(P.bufs.size());
   for (size_t i = 0; i < P.bufs.size(); ++i) offs[i] = sub_offset(P, (int)i, n);
@@ -1263,74 +1335,24 @@ inline void migan_handle::run_range(const migan::Plan& P, const float* x, float*
   };
   auto wptr = [&](int s) -> const float* { return s < 0 ? nullptr : slots[s].ptr; };
   unsigned short* wsplit = reinterpret_cast<unsigned short*>(shared);
-  auto params_of = [&](const Launch& L) {
-    SepParams p;
-    p.wdw = wptr(L.w_dw); p.bdw = wptr(L.b_dw); p.wpw = wptr(L.w_pw);
-    p.wsplit = !L.narrow && L.g.gemmv ? wsplit + L.wsplit_off : nullptr;      // (narrow layers read conv2.weight in fp32)
-    p.noise = L.noise_plane_off >= 0 ? reinterpret_cast<const float*>(shared + L.noise_plane_off) : wptr(L.w_noise);
-    p.noise_strength = wptr(L.w_ns);
-    p.frgb_w = wptr(L.w_frgb); p.frgb_b = wptr(L.b_frgb);
-    p.trgb_w = wptr(L.w_trgb); p.trgb_b = wptr(L.b_trgb);
-    p.img_prev = (const float*)bptr(L.imgprev_buf); p.img_out = (float*)bptr(L.imgout_buf);
-    return p;
-  };
-  // (nd: the sub-batch size the production forward launches with -- the per-launch timing run covers the whole batch in one launch but
-  // must time the kernel forms the throughput run uses)
-  const int nd = n_geo > 0 ? n_geo : n;
-  // a down=2 layer is two plan entries (depthwise + FIR-down, pointwise GEMM); where the fused kernel applies, the first entry launches
-  // nothing and the second launches sepconv_pipedown_kernel on the first one's input: decided at the first entry, for both
-  const DownEntry* down = nullptr;
-  SepArgs down_args{};
+  const std::vector<Resolved> R = P.resolve(n, nd);
+  prepare_kernels();
   for (size_t li = 0; li < P.launches.size(); ++li) {
     const Launch& L = P.launches[li];
+    MIGAN_CHECK(!L.narrow || u8 == nullptr || (L.in_buf != BUF_X && L.imgout_buf != BUF_Y), MIGAN_EUNSUPPORTED,
+                "the uint8-in / uint8-out forward is not available at resolutions above 512");
     if (timed) rt_check(rt::event_record(events[2 * li], stream), "hipEventRecord");
-    if (L.is_dwfir && li + 1 < P.launches.size()) {
-      const Launch& G = P.launches[li + 1];      // the pointwise GEMM of the pair
-      SepParams p = params_of(G);
-      p.wdw = wptr(L.w_dw); p.bdw = wptr(L.b_dw);
-      down_args = sep_args(p, bptr(L.in_buf), bptr(G.out_buf), nullptr, n, L.hin, L.win, G.cin, G.cout, G.hout, G.wout);
-      down = pick_fused_down(down_args, nd, stv, gemm);
-    }
-    if (L.is_dwfir && down) {
-      L.kernel_last = down->name;      // (its bytes belong to that launch)
-    } else if (down) {
-      L.kernel_last = launch_pipedown(*down, down_args, stream);
-      down = nullptr;
-    } else if (L.is_dwfir) {
-      DwFirArgs a{};
-      a.x = bptr(L.in_buf); a.y = (float*)bptr(L.out_buf); a.wdw = wptr(L.w_dw); a.bdw = wptr(L.b_dw);
-      a.B = n; a.H = L.hin; a.W = L.win; a.C = L.cin;
-      launch_dwfir(L.dg, a, stream, dwfir_variant(stv, gemm));
-    } else if (L.narrow) {
-      MIGAN_CHECK(u8 == nullptr || (L.in_buf != BUF_X && L.imgout_buf != BUF_Y), MIGAN_EUNSUPPORTED,
-                  "the uint8-in / uint8-out forward is not available at resolutions above 512");
-      const SepArgs a = sep_args(params_of(L), bptr(L.in_buf), bptr(L.out_buf), bptr(L.skip_buf), n, L.hin, L.win, L.cin, L.cout, L.hout, L.wout);
-      L.kernel_last = launch_narrow(L.mode, L.fromrgb, a, stream);
-    } else if (L.is_rgb) {
-      RgbArgs a{};
-      a.x = bptr(L.in_buf); a.w = wptr(L.w_trgb); a.b = wptr(L.b_trgb);
-      a.img_prev = (const float*)bptr(L.imgprev_buf); a.img_out = (float*)bptr(L.imgout_buf);
-      a.B = n; a.H = L.hout; a.W = L.wout; a.C = L.cin;
-      if (u8 && L.imgout_buf == BUF_Y) { a.u8_img = (const unsigned char*)u8->img; a.u8_mask = (const unsigned char*)u8->mask; a.u8_out = (unsigned char*)u8->out; }
-      launch_torgb(a, stream, stv);
-    } else {
-      SepArgs a = sep_args(params_of(L), bptr(L.in_buf), bptr(L.out_buf), bptr(L.skip_buf), n, L.hin, L.win, L.cin, L.cout, L.hout, L.wout);
-      if (u8 && L.in_buf == BUF_X) { a.u8_img = (const unsigned char*)u8->img; a.u8_mask = (const unsigned char*)u8->mask; }
-      if (u8 && L.imgout_buf == BUF_Y && a.trgb_w) {
-        a.u8_img = (const unsigned char*)u8->img; a.u8_mask = (const unsigned char*)u8->mask; a.u8_out = (unsigned char*)u8->out;
-      }
-      // launches that would leave most CUs idle run the 32-row tiles: a quarter of the work per workgroup, four times the workgroups
-      const Geo* Gp = &L.g;
-      for (const Geo& gs : L.g_small) {
-        // K-split tiles sum K in another order than every other tile (four partial sums): single-image forwards only, so that an
-        // image of a batch of two or more is bit-identical whatever the batch size and the sub-batch grouping
-        if (gs.NT == 32 && nd != 1) continue;
-        if ((int)tiles_of(gs, nd) <= tuning().small_max_wgs) { Gp = &gs; break; }
-      }
-      const Geo& G = *Gp;
-      fill_geo(a, G);
-      L.kernel_last = launch_sepconv(G, a, stream, nd, L.out_dead);
-    }
+    LayerPtrs q;
+    // (the fused down=2 kernel reads what the dwfir entry in front of it would have)
+    q.x = bptr(R[li].whole_down ? P.launches[li - 1].in_buf : L.in_buf); q.y = bptr(L.out_buf); q.skip = bptr(L.skip_buf);
+    q.wdw = wptr(L.w_dw); q.bdw = wptr(L.b_dw); q.wpw = wptr(L.w_pw);
+    q.wsplit = !L.narrow && L.g.gemmv ? wsplit + L.wsplit_off : nullptr;      // (narrow layers read conv2.weight in fp32)
+    q.noise = L.noise_plane_off >= 0 ? reinterpret_cast<const float*>(shared + L.noise_plane_off) : wptr(L.w_noise);
+    q.noise_strength = wptr(L.w_ns); q.frgb_w = wptr(L.w_frgb); q.frgb_b = wptr(L.b_frgb); q.trgb_w = wptr(L.w_trgb); q.trgb_b = wptr(L.b_trgb);
+    q.img_prev = (const float*)bptr(L.imgprev_buf); q.img_out = (float*)bptr(L.imgout_buf);
+    if (L.in_buf == BUF_X) q.u8_in = u8;
+    if (L.imgout_buf == BUF_Y) q.u8_out = u8;
+    launch(R[li], q, stream);
     if (timed) rt_check(rt::event_record(events[2 * li + 1], stream), "hipEventRecord");
     if (!timed && (int)li == mid_after) rt_check(rt::event_record(ev_mid[part], stream), "hipEventRecord");
 #ifdef MIGAN_PHASE_PROF
@@ -1339,6 +1361,10 @@ inline void migan_handle::run_range(const migan::Plan& P, const float* x, float*
       rt_check(rt::prof_read(prof_buffer(), prof_layers()[li].v, 16, true), "prof read");
     }
 #endif
+  }
+  if (&P == &plan) {
+    launched.resize(R.size());
+    for (size_t li = 0; li < R.size(); ++li) launched[li] = R[li].name;
   }
 }
 
@@ -1366,18 +1392,9 @@ inline void migan_handle::forward(migan::Plan& P, const float* x, float* y, int 
   // written, in this workspace and stream order, since the last (re)binding of a weight.
   const bool planes_valid = static_weights && prepared_ws == ws && prepared_epoch == weight_epoch && prepared_stream == stream;
   if (gemm && !planes_valid) {
-    SplitArgs sa{};
-    sa.dst = reinterpret_cast<unsigned short*>(shared);
-    sa.f16 = gemm == 3 ? 2 : (gemm == 2 ? 1 : 0);
-    for (const Launch& L : P.launches) {
-      if (L.is_rgb || L.is_dwfir || L.narrow) continue;      // (narrow layers read conv2.weight in fp32)
-      MIGAN_CHECK(sa.n < 40, MIGAN_EINVAL, "internal: too many layers for the weight-split table");
-      sa.src[sa.n] = slots[L.w_pw].ptr;
-      sa.dst_off[sa.n] = L.wsplit_off;
-      sa.count[sa.n] = (unsigned)(L.cin * L.cout);
-      sa.ci[sa.n] = (unsigned)L.cin;
-      ++sa.n;
-    }
+    SplitArgs sa = split_args(reinterpret_cast<unsigned short*>(shared), gemm);
+    for (const Launch& L : P.launches)
+      if (!L.is_rgb && !L.is_dwfir && !L.narrow) add_split(sa, slots[L.w_pw].ptr, L.wsplit_off, L.cin, L.cout);      // (narrow layers read conv2.weight in fp32)
     launch_split(sa, stream);
     prepared_ws = ws; prepared_epoch = weight_epoch; prepared_stream = stream;     // only reached when every launch succeeded
   }
@@ -1405,35 +1422,31 @@ inline void migan_handle::forward(migan::Plan& P, const float* x, float* y, int 
     }
     *parts_io->out_parts = parts;
   }
-  if (parts > 1) {
-    // staggered sub-batches on separate streams: sub-batch k+1 starts when sub-batch k is `stagger` launches in, so the
-    // small-resolution layers of one (a few dozen workgroups each) and the tail of every launch run beside full-size layers
-    // of the others.  The caller's stream carries sub-batch 0 and is joined to all the others at the end (events only).
-    ensure_aux();
-    int done = 0;
-    char* sub = sub0;
-    for (int k = 0; k < parts; ++k) {
-      rt::stream_t sk = k == 0 ? stream : (parts_io ? (rt::stream_t)parts_io->streams[k - 1] : aux_stream[k - 1]);
-      if (k > 0) rt_check(rt::stream_wait_event(sk, ev_mid[k - 1]), "hipStreamWaitEvent");
-      migan_io_u8 uk{};
-      if (u8) {
-        uk.img = (const unsigned char*)u8->img + (size_t)done * P.H * P.W * 3;
-        uk.mask = (const unsigned char*)u8->mask + (size_t)done * P.H * P.W;
-        uk.out = (unsigned char*)u8->out + (size_t)done * P.H * P.W * 3;
-      }
-      float* yk = parts_io ? static_cast<float*>(parts_io->y[k]) : (y ? y + (size_t)done * out_img : nullptr);
-      run_range(P, x ? x + (size_t)done * in_img : nullptr, yk, nsub[k], sub, shared, sk, false,
-                k + 1 < parts ? P.stagger : -1, k, u8 ? &uk : nullptr);
-      if (k > 0 && !parts_io) rt_check(rt::event_record(ev_join[k - 1], sk), "hipEventRecord");
-      sub += sub_bytes(P, nsub[k]);
-      done += nsub[k];
+  // Staggered sub-batches on separate streams: sub-batch k+1 starts when sub-batch k is `stagger` launches in, so the small-resolution
+  // layers of one (a few dozen workgroups each) and the tail of every launch run beside full-size layers of the others.  The caller's
+  // stream carries sub-batch 0 and is joined to all the others at the end (events only).
+  if (parts > 1) ensure_aux();
+  int done = 0;
+  char* sub = sub0;
+  for (int k = 0; k < parts; ++k) {
+    rt::stream_t sk = k == 0 ? stream : (parts_io ? (rt::stream_t)parts_io->streams[k - 1] : aux_stream[k - 1]);
+    if (k > 0) rt_check(rt::stream_wait_event(sk, ev_mid[k - 1]), "hipStreamWaitEvent");
+    migan_io_u8 uk{};
+    if (u8) {
+      uk.img = (const unsigned char*)u8->img + (size_t)done * P.H * P.W * 3;
+      uk.mask = (const unsigned char*)u8->mask + (size_t)done * P.H * P.W;
+      uk.out = (unsigned char*)u8->out + (size_t)done * P.H * P.W * 3;
     }
-    // (migan_forward_parts: no join -- the caller owns the other streams and orders what follows behind each sub-batch)
-    if (!parts_io)
-      for (int k = 1; k < parts; ++k) rt_check(rt::stream_wait_event(stream, ev_join[k - 1]), "hipStreamWaitEvent");
-  } else {
-    run_range(P, x, parts_io ? static_cast<float*>(parts_io->y[0]) : y, nsub[0], sub0, shared, stream, timed, -1, 0, u8, timed ? n_production : 0);
+    float* yk = parts_io ? static_cast<float*>(parts_io->y[k]) : (y ? y + (size_t)done * out_img : nullptr);
+    run_range(P, x ? x + (size_t)done * in_img : nullptr, yk, nsub[k], sub, shared, sk, timed, k + 1 < parts ? P.stagger : -1, k, u8 ? &uk : nullptr,
+              timed ? n_production : nsub[k]);
+    if (k > 0 && !parts_io) rt_check(rt::event_record(ev_join[k - 1], sk), "hipEventRecord");
+    sub += sub_bytes(P, nsub[k]);
+    done += nsub[k];
   }
+  // (migan_forward_parts: no join -- the caller owns the other streams and orders what follows behind each sub-batch)
+  if (!parts_io)
+    for (int k = 1; k < parts; ++k) rt_check(rt::stream_wait_event(stream, ev_join[k - 1]), "hipStreamWaitEvent");
   if (timed) {
     rt_check(rt::stream_sync(stream), "hipStreamSynchronize");
     for (size_t li = 0; li < P.launches.size(); ++li)
@@ -1701,7 +1714,7 @@ int migan_launch_info(const migan_handle* h, int index, const char** layer, cons
   MIGAN_CHECK(index >= 0 && index < (int)h->plan.launches.size(), MIGAN_EINVAL, "launch index out of range");
   const migan::Launch& L = h->plan.launches[index];
   if (layer) *layer = L.layer.c_str();
-  if (kernel) *kernel = L.kernel_last.empty() ? L.kernel.c_str() : L.kernel_last.c_str();
+  if (kernel) *kernel = h->launched.empty() ? L.kernel.c_str() : h->launched[index];
   if (flops) *flops = L.flops;
   if (mfma_flops) *mfma_flops = L.mfma_flops;
   if (bytes) *bytes = L.bytes;
@@ -1755,86 +1768,68 @@ int migan_sepconv_forward(const migan_sepconv_desc* d, void* stream) {
   const int h_out = d->down == 2 ? h_in / 2 : (d->up == 2 ? h_in * 2 : h_in);
   const int w_out = d->down == 2 ? w_in / 2 : (d->up == 2 ? w_in * 2 : w_in);
   MIGAN_CHECK(d->noise_const == nullptr || d->noise_strength != nullptr, MIGAN_EINVAL, "noise_const without noise_strength");
-  SepParams p;
+  LayerPtrs p;
+  p.x = d->x; p.y = d->y; p.skip = d->skip;
   p.wdw = (const float*)d->conv1_weight; p.bdw = (const float*)d->conv1_bias; p.wpw = (const float*)d->conv2_weight;
   p.noise = (const float*)d->noise_const; p.noise_strength = (const float*)d->noise_strength;
   p.frgb_w = (const float*)d->fromrgb_weight; p.frgb_b = (const float*)d->fromrgb_bias;
   p.trgb_w = (const float*)d->torgb_weight; p.trgb_b = (const float*)d->torgb_bias;
   p.img_prev = (const float*)d->img_prev; p.img_out = (float*)d->img_out;
+  const bool fromrgb = d->fromrgb_weight != nullptr, torgb = d->torgb_weight != nullptr;
+  LayerDesc ld;
+  ld.mode = d->down == 2 ? MODE_DOWN : (d->up == 2 ? MODE_UP : MODE_NORMAL);
+  ld.cin = d->cin; ld.cout = d->cout; ld.hin = h_in; ld.win = w_in; ld.hout = h_out; ld.wout = w_out;
+  ld.fromrgb = fromrgb; ld.torgb = torgb; ld.skip = d->skip != nullptr; ld.noise = d->noise_const != nullptr;
+  Geo g; DwGeo dg; int gemmv = 0;
+  // (every refusal before the first launch: a refused call leaves y, img_out and the scratch tensors untouched)
   if (is_narrow(d->cin, d->cout) && d->cin <= 64 && d->cout <= 64 && d->cin % 4 == 0 && d->cout % 4 == 0) {
     // fewer than 64 channels on either side (the layers of resolutions above 512): the plain kernel, the whole layer in one launch
     MIGAN_CHECK(stv == 0, MIGAN_EUNSUPPORTED, "layers with fewer than 64 channels run with fp32 activation storage only");
-    MIGAN_CHECK(d->torgb_weight == nullptr || (d->up == 1 && d->down == 1 && d->img_out && d->torgb_bias), MIGAN_EINVAL,
+    MIGAN_CHECK(!torgb || (d->up == 1 && d->down == 1 && d->img_out && d->torgb_bias), MIGAN_EINVAL,
                 "ToRGB needs up == down == 1, torgb_bias and img_out");
-    MIGAN_CHECK(d->fromrgb_weight == nullptr || (d->up == 1 && d->down == 1), MIGAN_EINVAL, "fromrgb is only fused into plain layers");
-    MIGAN_CHECK(d->fromrgb_weight == nullptr || d->fromrgb_bias != nullptr, MIGAN_EINVAL, "fromrgb_weight without fromrgb_bias");
-    prepare_kernels();
-    const int nmode = d->down == 2 ? MODE_DOWN : (d->up == 2 ? MODE_UP : MODE_NORMAL);
-    const SepArgs a = sep_args(p, d->x, d->y, d->skip, d->batch, h_in, w_in, d->cin, d->cout, h_out, w_out);
-    launch_narrow(nmode, d->fromrgb_weight != nullptr, a, (rt::stream_t)stream);
-    return MIGAN_OK;
+    MIGAN_CHECK(!fromrgb || (d->up == 1 && d->down == 1), MIGAN_EINVAL, "fromrgb is only fused into plain layers");
+    MIGAN_CHECK(!fromrgb || d->fromrgb_bias != nullptr, MIGAN_EINVAL, "fromrgb_weight without fromrgb_bias");
+  } else {
+    MIGAN_CHECK(!fromrgb || d->fromrgb_bias != nullptr, MIGAN_EINVAL, "fromrgb_weight without fromrgb_bias");
+    MIGAN_CHECK(!torgb || (d->up == 1 && d->img_out && d->torgb_bias), MIGAN_EINVAL, "ToRGB needs up == 1, torgb_bias and img_out");
+    // split GEMM variants need room for the 16-bit weight planes; without it the exact fp32 MFMA path runs
+    const size_t wsplit_need = wsplit_elems_of(d->cin, d->cout) * sizeof(unsigned short);
+    const int want = stv != 0 ? (d->gemm == MIGAN_GEMM_F16X2 ? MIGAN_GEMM_F16X2 : MIGAN_GEMM_F16) : (d->gemm >= 0 ? d->gemm : tuning().gemm);
+    MIGAN_CHECK(want >= 0 && want <= 3 && (stv != 0 || want <= 2), MIGAN_EINVAL, "unknown GEMM variant for this storage format");
+    const bool have_planes = d->wsplit != nullptr && d->wsplit_bytes >= wsplit_need;
+    MIGAN_CHECK(stv == 0 || have_planes, MIGAN_EINVAL, "16-bit activation storage needs the wsplit buffer (fp16 GEMM variants)");
+    gemmv = have_planes ? want : 0;
+    if (gemmv) p.wsplit = (const unsigned short*)d->wsplit + kSplitHeader;
+    if (!torgb) { p.img_prev = nullptr; p.img_out = nullptr; }
+    if (d->down == 2) {
+      MIGAN_CHECK(!fromrgb, MIGAN_EINVAL, "fromrgb is only fused into plain layers");
+      dg = choose_dwfir_geo(d->cin, h_in, w_in); ld.dg = &dg;
+    }
+    // (small tiles not allowed: the generator plan picks them per launch size, this operator runs the layer's regular tile)
+    g = d->down == 2 ? choose_geo(MODE_PW, d->cin, d->cout, h_out, w_out, false, torgb, gemmv, stv)
+                     : choose_geo(ld.mode, d->cin, d->cout, h_in, w_in, fromrgb, torgb, gemmv, stv);
+    ld.g = &g;
   }
-  MIGAN_CHECK(d->fromrgb_weight == nullptr || d->fromrgb_bias != nullptr, MIGAN_EINVAL, "fromrgb_weight without fromrgb_bias");
-  // (every refusal before the first launch: a refused call leaves y, img_out and the scratch tensors untouched)
-  MIGAN_CHECK(d->torgb_weight == nullptr || (d->up == 1 && d->img_out && d->torgb_bias), MIGAN_EINVAL, "ToRGB needs up == 1, torgb_bias and img_out");
-  const void* gemm_in = d->x;
-  int mode = d->up == 2 ? MODE_UP : MODE_NORMAL, gemm_h = h_in, gemm_w = w_in;
-  // split GEMM variants need room for the 16-bit weight planes; without it the exact fp32 MFMA path runs
-  const size_t wsplit_need = wsplit_elems_of(d->cin, d->cout) * sizeof(unsigned short);
-  const int want = stv != 0 ? (d->gemm == MIGAN_GEMM_F16X2 ? MIGAN_GEMM_F16X2 : MIGAN_GEMM_F16) : (d->gemm >= 0 ? d->gemm : tuning().gemm);
-  MIGAN_CHECK(want >= 0 && want <= 3 && (stv != 0 || want <= 2), MIGAN_EINVAL, "unknown GEMM variant for this storage format");
-  const bool have_planes = d->wsplit != nullptr && d->wsplit_bytes >= wsplit_need;
-  MIGAN_CHECK(stv == 0 || have_planes, MIGAN_EINVAL, "16-bit activation storage needs the wsplit buffer (fp16 GEMM variants)");
-  const int gemmv = have_planes ? want : 0;
-  if (gemmv) p.wsplit = (const unsigned short*)d->wsplit + kSplitHeader;
-  if (!p.trgb_w) { p.img_prev = nullptr; p.img_out = nullptr; }
-  const SepArgs whole = sep_args(p, d->x, d->y, d->skip, d->batch, h_in, w_in, d->cin, d->cout, h_out, w_out);
-  if (const DownEntry* fused_down = d->down == 2 ? pick_fused_down(whole, d->batch, stv, gemmv) : nullptr) {
-    // one launch: depthwise + FIR-down feed the 1x1 through LDS (no scratch tensor)
-    SplitArgs sa{};
-    sa.dst = (unsigned short*)d->wsplit;
-    sa.f16 = 1;
-    sa.src[0] = (const float*)d->conv2_weight; sa.dst_off[0] = kSplitHeader; sa.count[0] = (unsigned)(d->cin * d->cout); sa.ci[0] = (unsigned)d->cin; sa.n = 1;
-    launch_split(sa, (rt::stream_t)stream);
-    launch_pipedown(*fused_down, whole, (rt::stream_t)stream);
-    return MIGAN_OK;
-  }
-  if (d->down == 2) {
-    // reference :155-161: depthwise+act+FIR at res_in (dwfir kernel), then the 1x1 at res_in/2
-    MIGAN_CHECK(d->fromrgb_weight == nullptr, MIGAN_EINVAL, "fromrgb is only fused into plain layers");
-    const size_t need = (size_t)d->batch * h_out * w_out * d->cin * sizeof(float);
-    MIGAN_CHECK(d->scratch != nullptr && d->scratch_bytes >= need, MIGAN_EINVAL,
+  Resolved R[kMaxLayerLaunches];
+  const int k = resolve_layer(ld, d->batch, d->batch, R);
+  if (R[0].kind == K_DWFIR)
+    MIGAN_CHECK(d->scratch != nullptr && d->scratch_bytes >= (size_t)d->batch * h_out * w_out * d->cin * sizeof(float), MIGAN_EINVAL,
                 "down=2 needs scratch of batch*(res_in/2)^2*cin floats");
-    const DwGeo dg = choose_dwfir_geo(d->cin, h_in, w_in);
-    DwFirArgs fa{};
-    fa.x = d->x; fa.y = (float*)d->scratch; fa.wdw = (const float*)d->conv1_weight; fa.bdw = (const float*)d->conv1_bias;
-    fa.B = d->batch; fa.H = h_in; fa.W = w_in; fa.C = d->cin;
-    launch_dwfir(dg, fa, (rt::stream_t)stream, dwfir_variant(stv, gemmv));
-    gemm_in = d->scratch;
-    mode = MODE_PW;
-    gemm_h = h_out; gemm_w = w_out;
-  }
-  const Geo g = choose_geo(mode, d->cin, d->cout, gemm_h, gemm_w, d->fromrgb_weight != nullptr, d->torgb_weight != nullptr, gemmv, stv);
-  if (gemmv) {
-    SplitArgs sa{};
-    sa.dst = (unsigned short*)d->wsplit;
-    sa.f16 = gemmv == 3 ? 2 : (gemmv == 2 ? 1 : 0);
-    sa.src[0] = (const float*)d->conv2_weight; sa.dst_off[0] = kSplitHeader; sa.count[0] = (unsigned)(d->cin * d->cout); sa.ci[0] = (unsigned)d->cin; sa.n = 1;
-    launch_split(sa, (rt::stream_t)stream);
-  }
-  // one workgroup owns all output channels of its pixels (cout <= 128, or 256 on whole 8x16 tiles): ToRGB fuses into the epilogue;
-  // otherwise torgb_kernel runs on y afterwards, as in the generator plan
-  const bool fuse_rgb = d->torgb_weight != nullptr && g.nchunks == 1;
-  SepArgs a = sep_args(p, gemm_in, d->y, d->skip, d->batch, gemm_h, gemm_w, d->cin, d->cout, h_out, w_out);
-  if (!fuse_rgb) { a.trgb_w = a.trgb_b = a.img_prev = nullptr; a.img_out = nullptr; }
-  fill_geo(a, g);
-  launch_sepconv(g, a, (rt::stream_t)stream);
-  if (d->torgb_weight != nullptr && !fuse_rgb) {
-    RgbArgs r{};
-    r.x = d->y; r.w = (const float*)d->torgb_weight; r.b = (const float*)d->torgb_bias;
-    r.img_prev = (const float*)d->img_prev; r.img_out = (float*)d->img_out;
-    r.B = d->batch; r.H = h_out; r.W = w_out; r.C = d->cout;
-    launch_torgb(r, (rt::stream_t)stream, stv);
+  prepare_kernels();
+  for (int i = 0; i < k; ++i) {
+    LayerPtrs q = p;
+    if (R[i].kind == K_SEP) {
+      if (gemmv) {
+        SplitArgs sa = split_args((unsigned short*)d->wsplit, gemmv);
+        add_split(sa, p.wpw, kSplitHeader, d->cin, d->cout);
+        launch_split(sa, (rt::stream_t)stream);
+      }
+      if (ld.dg && !R[i].whole_down) q.x = d->scratch;            // the pointwise GEMM of an un-fused down=2 layer reads dwfir_kernel's output
+      if (i + 1 < k) { q.trgb_w = q.trgb_b = q.img_prev = nullptr; q.img_out = nullptr; }      // a ToRGB that does not fuse runs on y afterwards
+    }
+    if (R[i].kind == K_DWFIR) q.y = d->scratch;
+    if (R[i].kind == K_RGB) q.x = d->y;
+    launch(R[i], q, (rt::stream_t)stream);
   }
   MIGAN_API_END
 }

@@ -120,6 +120,12 @@ inline void wave_barrier() {
 
 void run_grid(void (*invoke)(const void*), const void* arg, unsigned grid, unsigned block, size_t lds_bytes);
 
+// Dry run (hipemu_set_dry_run, migan_emu.cpp): a launch that passes rt::launch's checks is appended to a log -- kernel symbol, grid, block,
+// LDS bytes, the raw bytes of its argument struct -- instead of executed.  Nothing is dereferenced, so the launch list of a forward at a
+// production size can be read (and compared between two builds) in milliseconds, with any non-null address for a workspace.
+bool dry_run();
+void log_launch(const void* kernel, unsigned grid, unsigned block, size_t lds_bytes, const void* args, size_t arg_bytes);
+
 }  // namespace hipemu
 
 // ---- the HIP surface the kernels use --------------------------------------------------------------
@@ -408,6 +414,10 @@ template <class Args>
 inline int launch(void (*kernel)(const Args), const Args& a, unsigned grid, unsigned block, size_t lds, stream_t) {
   if (block == 0 || block % 64 != 0 || block > (unsigned)hipemu::kMaxLanes || lds > 160 * 1024) return 1;
   if (lds > kDefaultDynLds && lds > dynamic_lds_limit((const void*)kernel)) return 1;
+  if (hipemu::dry_run()) {
+    hipemu::log_launch((const void*)kernel, grid, block, lds, &a, sizeof(Args));
+    return 0;
+  }
   Thunk<Args> t{kernel, &a};
   hipemu::run_grid(&Thunk<Args>::call, &t, grid, block, lds);
   return 0;

@@ -36,6 +36,8 @@
 #include "../../mi-gan_amd/csrc/migan_host.hpp"
 #include "../../mi-gan_amd/csrc/comodgan_host.hpp"
 
+#include <cxxabi.h>
+#include <dlfcn.h>
 #include <mutex>
 
 asm(R"(
@@ -188,4 +190,42 @@ void run_grid(void (*invoke)(const void*), const void* arg, unsigned grid, unsig
   }
 }
 
+// ---- dry run: the launch log ----
+struct LogEntry {
+  std::string name;
+  unsigned grid, block;
+  size_t lds_bytes;
+  std::vector<unsigned char> args;
+};
+static bool g_dry_run = false;
+static std::vector<LogEntry> g_log;
+
+bool dry_run() { return g_dry_run; }
+void log_launch(const void* kernel, unsigned grid, unsigned block, size_t lds_bytes, const void* args, size_t arg_bytes) {
+  LogEntry e{"?", grid, block, lds_bytes, {}};
+  Dl_info info;
+  if (dladdr(kernel, &info) && info.dli_sname && info.dli_saddr == kernel) {
+    int status = 0;
+    char* d = abi::__cxa_demangle(info.dli_sname, nullptr, nullptr, &status);
+    e.name = d ? d : info.dli_sname;
+    std::free(d);
+  }
+  e.args.assign(static_cast<const unsigned char*>(args), static_cast<const unsigned char*>(args) + arg_bytes);
+  std::lock_guard<std::mutex> lock(g_launch_mutex);
+  g_log.push_back(std::move(e));
+}
+
 }  // namespace hipemu
+
+// exported by the emulator library only (the product has no such switch); turning the switch either way empties the log
+extern "C" void hipemu_set_dry_run(int on) {
+  hipemu::g_dry_run = on != 0;
+  hipemu::g_log.clear();
+}
+extern "C" int hipemu_log_size(void) { return (int)hipemu::g_log.size(); }
+extern "C" int hipemu_log_entry(int i, const char** name, unsigned* grid, unsigned* block, size_t* lds_bytes, const void** args, size_t* arg_bytes) {
+  if (i < 0 || i >= (int)hipemu::g_log.size()) return 1;
+  const hipemu::LogEntry& e = hipemu::g_log[i];
+  *name = e.name.c_str(); *grid = e.grid; *block = e.block; *lds_bytes = e.lds_bytes; *args = e.args.data(); *arg_bytes = e.args.size();
+  return 0;
+}

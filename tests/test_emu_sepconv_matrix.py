@@ -48,8 +48,9 @@ def table_names(lib, pkg):
 
 @pytest.mark.parametrize("res", [1024, 2048, 4096])
 def test_table_covers_the_generator_plans(lib, pkg, table_names, res):
-    """the kernels a default Generator(res) plan names before any forward (the pipelined / pipedown choices depend on the batch and are
-    only known after one: the GPU test runs forwards) -- each must be reported by a case of the table"""
+    """the kernels a default Generator(res) plan names before any forward: the table kernels of its own tile geometry.  (The pipelined /
+    pipedown / small-tile forms depend on the batch, Plan::resolve picks them per forward: tests/test_emu_launch_stream.py lists what
+    production forwards launch, the GPU test runs forwards.)  Each must be reported by a case of the table"""
     h = pkg.hipbind.MiganHandle(lib, res, 0)
     plan = {l["kernel"] for l in h.launches()}
     assert not mx.uncovered(plan, table_names), mx.uncovered(plan, table_names)

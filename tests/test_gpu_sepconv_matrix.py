@@ -45,8 +45,8 @@ def table_names(lib, pkg, mem):
 @pytest.mark.parametrize("res,storage,batch", [(256, "f32", 1), (256, "f32", 32), (256, "bf16", 32), (512, "f32", 1), (512, "f32", 32),
                                                (512, "bf16", 32), (1024, "f32", 1), (2048, "f32", 1)])
 def test_table_covers_the_generator_forwards(pkg, mem, table_names, res, storage, batch):
-    """one forward of the default Generator(res): the kernel each launch ran (kernel_last: the pipelined / pipedown forms depend on the
-    batch) must be reported by some case of the table"""
+    """one forward of the default Generator(res): the kernel each launch ran (migan_launch_info after a forward names what the forward's
+    last sub-batch launched: the pipelined / pipedown forms depend on the batch) must be reported by some case of the table"""
     dev = torch.device("cuda", 0)
     sd = pkg.synth.make_state_dict(res, seed=5)
     m = pkg.Generator(resolution=res, activation_dtype=storage)
