@@ -295,9 +295,35 @@ MIGAN_DEVICE MIGAN_INLINE f4 fromrgb_quad(f4 raw, f4 w0, f4 w1, f4 w2, f4 w3, f4
   return f4{bb.x + t0, bb.y + t1, bb.z + t2, bb.w + t3};
 }
 
-// XCD-aware workgroup order (MI355X: block b runs on XCD b%8, each XCD has a private 4 MiB L2):
-// give every XCD one contiguous range of logical tiles so halo rows shared by neighbouring tiles
-// and the Cout chunks of one tile hit the same L2.  Bijective for any grid size.
+// XCD-aware tile schedule (MI355X: block b runs on XCD b%8, each XCD has a private 4 MiB L2), THE statement of "which tile is mine"
+// of every kernel of the library.  The logical tiles (column chunk fastest, then x, y, image) are split into 8 contiguous ranges, one per
+// XCD, so halo rows shared by neighbouring tiles and the Cout chunks of one tile hit the same L2.  The workgroups of an XCD walk their
+// range with a stride equal to their count, so at any moment an XCD works on consecutive tiles: workgroup `bid` of `nblk` owns the
+// MIGAN_XCD_TILES(xr) tiles tbase + tl0 + k tstep with tl0 + k tstep < tcnt, and which workgroup computes a tile never changes what is
+// computed.  With nblk == ntiles every workgroup owns exactly one tile.
+// PRECONDITION: nblk >= 8 or nblk >= ntiles.  A smaller grid has no workgroup on some XCDs, and the ranges of those XCDs are walked by
+// nobody.  The host launches no such grid: a launch is one workgroup per tile, or min(ntiles, knob) workgroups with the knob a multiple
+// of 8 (migan_host.hpp: grid_of, knob::mult8).  tests/test_emu_schedule.py pins both sides of this line.
+struct XcdRange {
+  int tbase, tcnt, tstep, tl0;        // first tile and tile count of this XCD's range, workgroups on this XCD, my first index inside the range
+};
+// MIGAN_XCD_RANGE(xr, ntiles, bid, nblk); declares `const XcdRange xr` from three int expressions (a kernel passes (int)blockIdx.x and
+// (int)gridDim.x, the schedule test of the CPU suite plain numbers).  A macro and not a function on purpose: a function is optimised on its
+// own before it is inlined, and every kernel that took its numbers from one came out with another prologue and other register numbers
+// throughout; as text in the kernel (bid and nblk read where they are used) each compiles to the code it had with its private copy
+// (profiles/migan_persistent_shared.md)
+#define MIGAN_XCD_RANGE(xr, ntiles_, bid_, nblk_)                                                                                        \
+  const int xr##_nt = (ntiles_), xr##_xcd = (bid_) & 7;                                                                                   \
+  const int xr##_q = xr##_nt >> 3, xr##_r = xr##_nt & 7;                                                                                  \
+  const int xr##_cnt = xr##_q + (xr##_xcd < xr##_r ? 1 : 0);                                                                              \
+  const int xr##_base = xr##_xcd < xr##_r ? xr##_xcd * (xr##_q + 1) : xr##_r * (xr##_q + 1) + (xr##_xcd - xr##_r) * xr##_q;               \
+  const int xr##_step = ((nblk_) + 7 - xr##_xcd) >> 3;                                                                                    \
+  const XcdRange xr{xr##_base, xr##_cnt, xr##_step, (bid_) >> 3}
+// my tiles (the persistent kernels; an expression in the kernel's text for the same reason)
+#define MIGAN_XCD_TILES(xr) ((xr).tl0 < (xr).tcnt ? ((xr).tcnt - (xr).tl0 + (xr).tstep - 1) / (xr).tstep : 0)
+// One tile per workgroup (nblk == ntiles), the kernels outside the SeparableConv2d families: tbase + tl0 of the range above.  Kept as its
+// own five operations (taken from the macro it moved an instruction in the Co-Mod-GAN convolution kernels, which are not to change);
+// tests/test_emu_schedule.py holds the two statements against each other.
 MIGAN_DEVICE MIGAN_INLINE int xcd_remap(int bid, int nblk) {
   const int q = nblk >> 3, r = nblk & 7, xcd = bid & 7, idx = bid >> 3;
   const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
@@ -490,19 +516,10 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, MINW) sepconv_kernel(const SepArgs p)
   const int lgRS = MAINGEO ? 1 : p.lgRS;
   const int GH = 1 << lgGH, GW = 1 << lgGW, IMGS = 1 << lgIMGS;
 
-  // ---- persistent tile schedule -------------------------------------------------------------
-  // Logical tiles (n-chunk fastest, then x, y, image group) are split into 8 contiguous ranges, one
-  // per XCD (block b runs on XCD b%8, each XCD has a private L2: halo rows shared by neighbouring
-  // tiles and the Cout chunks of one tile then hit the same L2).  The workgroups of an XCD walk
-  // their range with a stride equal to their count, so at any moment an XCD works on consecutive
-  // tiles.  With gridDim == #tiles every workgroup does exactly one tile.
-  const int ntiles = p.tiles_x * p.tiles_y * p.nchunks * ((p.B + IMGS - 1) >> lgIMGS);
-  const int xcd = (int)blockIdx.x & 7;
-  const int tq = ntiles >> 3, tr = ntiles & 7;
-  const int tcnt = tq + (xcd < tr ? 1 : 0);                                  // tiles of this XCD
-  const int tbase = xcd < tr ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq;
-  const int tstep = ((int)gridDim.x + 7 - xcd) >> 3;                         // workgroups on this XCD
-  int tl = (int)blockIdx.x >> 3;                                             // my first tile in the range
+  // ---- persistent tile schedule (MIGAN_XCD_RANGE; tiles of image groups here).  With gridDim == #tiles every workgroup does exactly one tile
+  MIGAN_XCD_RANGE(xr, p.tiles_x * p.tiles_y * p.nchunks * ((p.B + IMGS - 1) >> lgIMGS), (int)blockIdx.x, (int)gridDim.x);
+  const int tcnt = xr.tcnt, tbase = xr.tbase, tstep = xr.tstep;
+  int tl = xr.tl0;                                                           // my current tile in the range
   auto decode = [&](int t, int& n0_, int& b0_, int& gy0_, int& gx0_) {
     const int nch = t % p.nchunks; t /= p.nchunks;
     const int tx = t % p.tiles_x;  t /= p.tiles_x;
@@ -1243,12 +1260,9 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(kWideThreads, 2) sepconv_wide_kernel(const
   const int pslot = groupA ? 0 : 4;   // phase profile (debug builds): A waves -> slots 0..3, B waves -> 4..7 [stores+load waits, depthwise, MFMA, barrier]
   (void)pslot;
 
-  // tile schedule: same XCD-contiguous order as sepconv_kernel, one tile per workgroup
-  const int ntiles = p.tiles_x * p.tiles_y * p.nchunks * p.B;
-  const int xcd = (int)blockIdx.x & 7;
-  const int tq = ntiles >> 3, tr = ntiles & 7;
-  const int tbase = xcd < tr ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq;
-  int t = tbase + ((int)blockIdx.x >> 3);
+  // tile schedule (MIGAN_XCD_RANGE), one tile per workgroup
+  MIGAN_XCD_RANGE(xr, p.tiles_x * p.tiles_y * p.nchunks * p.B, (int)blockIdx.x, (int)gridDim.x);
+  int t = xr.tbase + xr.tl0;
   const int nch = t % p.nchunks; t /= p.nchunks;
   const int tx = t % p.tiles_x;  t /= p.tiles_x;
   const int ty = t % p.tiles_y;

@@ -29,6 +29,41 @@ namespace migan {
 constexpr int kPipeBWaves = 8;
 constexpr int pipe_threads(int na) { return (na + kPipeBWaves) * 64; }
 
+// ---- tile walk of a persistent workgroup (sepconv_pipe_kernel, sepconv_pipedown_kernel, sepconv_wide2_kernel) ------------------------
+// Its MIGAN_XCD_TILES(xr) tiles are xr.tstep apart in the logical order (column chunk fastest, then x, y, image; MIGAN_XCD_RANGE,
+// migan_kernels.hpp): every cursor of a kernel (DMA issue, weight planes, depthwise stage, MFMAs, epilogue) starts at the first tile and
+// walks them with a mixed-radix add of tstep (computed once; scalar ALU only) instead of dividing a tile number by run-time extents once
+// per tile.  MIGAN_TILE_WALK(w, xr, nchunks, tiles_x, tiles_y); declares `TileCur w0` (the first tile) and the closure
+// `w_next(TileCur&)`; its other names carry the prefix w_.  It stands AFTER the kernel's T == 0 exit (the divisions stay behind it).
+// Text in the kernel like MIGAN_XCD_RANGE and for the same reason: as a struct with a constructor and a next() member, five of the
+// fourteen instantiations of the two kernels below came out with permuted cursor registers inside their loops, one with another
+// instruction count (profiles/migan_persistent_shared.md).
+struct TileCur {
+  int n, x, y, b;
+};
+#define MIGAN_TILE_WALK(w, xr, nchunks_, tiles_x_, tiles_y_)                                                                             \
+  const int w##_st_n = xr.tstep % (nchunks_), w##_st_r1 = xr.tstep / (nchunks_);                                                          \
+  const int w##_st_x = w##_st_r1 % (tiles_x_), w##_st_r2 = w##_st_r1 / (tiles_x_);                                                        \
+  const int w##_st_y = w##_st_r2 % (tiles_y_), w##_st_b = w##_st_r2 / (tiles_y_);                                                         \
+  TileCur w##0;                                                                                                                           \
+  {                                                                                                                                       \
+    int w##_t = xr.tbase + xr.tl0;                                                                                                        \
+    (w##0).n = w##_t % (nchunks_); w##_t /= (nchunks_);                                                                                   \
+    (w##0).x = w##_t % (tiles_x_); w##_t /= (tiles_x_);                                                                                   \
+    (w##0).y = w##_t % (tiles_y_);                                                                                                        \
+    (w##0).b = w##_t / (tiles_y_);                                                                                                        \
+  }                                                                                                                                       \
+  auto w##_next = [&](TileCur& w##_c) {                                                                                                   \
+    int w##_carry = 0;                                                                                                                    \
+    w##_c.n += w##_st_n;                                                                                                                  \
+    if (w##_c.n >= (nchunks_)) { w##_c.n -= (nchunks_); w##_carry = 1; }                                                                  \
+    w##_c.x += w##_st_x + w##_carry; w##_carry = 0;                                                                                       \
+    if (w##_c.x >= (tiles_x_)) { w##_c.x -= (tiles_x_); w##_carry = 1; }                                                                  \
+    w##_c.y += w##_st_y + w##_carry; w##_carry = 0;                                                                                       \
+    if (w##_c.y >= (tiles_y_)) { w##_c.y -= (tiles_y_); w##_carry = 1; }                                                                  \
+    w##_c.b += w##_st_b + w##_carry;                                                                                                      \
+  }
+
 // LDS carve of one instantiation (bytes), shared with the host plan
 template <int MODE, int NT, int CIN, bool FROMRGB, int R>
 struct PipeLds {
@@ -99,46 +134,15 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(pipe_threads(NA), (NA + kPipeBWaves) / 4) 
   const int wave_u = MIGAN_UNIFORM(tid >> 6);
   const bool groupA = tid < AT;
 
-  // ---- tile schedule: the XCD-contiguous ranges of sepconv_kernel, walked by the persistent workgroups of each XCD ----------------
-  const int ntiles = p.tiles_x * p.tiles_y * p.nchunks * p.B;
-  const int xcd = (int)blockIdx.x & 7;
-  const int tq = ntiles >> 3, tr = ntiles & 7;
-  const int tcnt = tq + (xcd < tr ? 1 : 0);
-  const int tbase = xcd < tr ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq;
-  const int tstep = ((int)gridDim.x + 7 - xcd) >> 3;
-  const int tl0 = (int)blockIdx.x >> 3;
-  const int T = tl0 < tcnt ? (tcnt - tl0 + tstep - 1) / tstep : 0;   // my tiles
+  // ---- tile schedule (MIGAN_XCD_RANGE, MIGAN_TILE_WALK) ------------------------------------------------------------------------------
+  MIGAN_XCD_RANGE(xr, p.tiles_x * p.tiles_y * p.nchunks * p.B, (int)blockIdx.x, (int)gridDim.x);
+  const int T = MIGAN_XCD_TILES(xr);                                                 // my tiles
   if (T == 0) return;                                                 // (uniform: the whole workgroup leaves)
   const int G = T * NKC;                                              // my K steps
   // phase profile (-DMIGAN_PHASE_PROF builds): group A -> slots 0..3 [DMA issue + offsets / tile build, depthwise, vmcnt wait, barrier],
   // group B -> slots 4..7 [MFMAs, epilogue slice, barrier, rest]
   PPROF_BEGIN();
-  // A workgroup's tiles are tstep apart in the logical order (column chunk fastest, then x, y, image): every cursor below walks them with
-  // a mixed-radix add of tstep (computed once; scalar ALU only) instead of dividing a tile number by run-time extents once per tile.
-  struct TileCur {
-    int n, x, y, b;
-  };
-  const int st_n = tstep % p.nchunks, st_r1 = tstep / p.nchunks;
-  const int st_x = st_r1 % p.tiles_x, st_r2 = st_r1 / p.tiles_x;
-  const int st_y = st_r2 % p.tiles_y, st_b = st_r2 / p.tiles_y;
-  TileCur tile0;
-  {
-    int t = tbase + tl0;
-    tile0.n = t % p.nchunks; t /= p.nchunks;
-    tile0.x = t % p.tiles_x; t /= p.tiles_x;
-    tile0.y = t % p.tiles_y;
-    tile0.b = t / p.tiles_y;
-  }
-  auto tile_next = [&](TileCur& c) {
-    int carry = 0;
-    c.n += st_n;
-    if (c.n >= p.nchunks) { c.n -= p.nchunks; carry = 1; }
-    c.x += st_x + carry; carry = 0;
-    if (c.x >= p.tiles_x) { c.x -= p.tiles_x; carry = 1; }
-    c.y += st_y + carry; carry = 0;
-    if (c.y >= p.tiles_y) { c.y -= p.tiles_y; carry = 1; }
-    c.b += st_b + carry;
-  };
+  MIGAN_TILE_WALK(tile, xr, p.nchunks, p.tiles_x, p.tiles_y);              // tile0, tile_next
   auto tile_coords = [&](const TileCur& c, int& n0_, int& b0_, int& gy0_, int& gx0_) {
     n0_ = c.n * NT;
     b0_ = c.b;
@@ -1069,42 +1073,13 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS((NA + NB) * 64, (NA + NB) / 4) sepconv_pip
   const bool groupA = tid < AT;
   const int HO = p.H >> 1, WO = p.W >> 1;                            // p.H, p.W: the full-resolution input; the GEMM runs at HO x WO
 
-  // ---- tile schedule (as sepconv_pipe_kernel) ------------------------------------------------------------------------------------
-  const int ntiles = p.tiles_x * p.tiles_y * p.nchunks * p.B;
-  const int xcd = (int)blockIdx.x & 7;
-  const int tq = ntiles >> 3, tr = ntiles & 7;
-  const int tcnt = tq + (xcd < tr ? 1 : 0);
-  const int tbase = xcd < tr ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq;
-  const int tstep = ((int)gridDim.x + 7 - xcd) >> 3;
-  const int tl0 = (int)blockIdx.x >> 3;
-  const int T = tl0 < tcnt ? (tcnt - tl0 + tstep - 1) / tstep : 0;
+  // ---- tile schedule (MIGAN_XCD_RANGE, MIGAN_TILE_WALK) ------------------------------------------------------------------------------
+  MIGAN_XCD_RANGE(xr, p.tiles_x * p.tiles_y * p.nchunks * p.B, (int)blockIdx.x, (int)gridDim.x);
+  const int T = MIGAN_XCD_TILES(xr);
   if (T == 0) return;
   const int G = T * NKC;
   PPROF_BEGIN();
-  struct TileCur {
-    int n, x, y, b;
-  };
-  const int st_n = tstep % p.nchunks, st_r1 = tstep / p.nchunks;
-  const int st_x = st_r1 % p.tiles_x, st_r2 = st_r1 / p.tiles_x;
-  const int st_y = st_r2 % p.tiles_y, st_b = st_r2 / p.tiles_y;
-  TileCur tile0;
-  {
-    int t = tbase + tl0;
-    tile0.n = t % p.nchunks; t /= p.nchunks;
-    tile0.x = t % p.tiles_x; t /= p.tiles_x;
-    tile0.y = t % p.tiles_y;
-    tile0.b = t / p.tiles_y;
-  }
-  auto tile_next = [&](TileCur& c) {
-    int carry = 0;
-    c.n += st_n;
-    if (c.n >= p.nchunks) { c.n -= p.nchunks; carry = 1; }
-    c.x += st_x + carry; carry = 0;
-    if (c.x >= p.tiles_x) { c.x -= p.tiles_x; carry = 1; }
-    c.y += st_y + carry; carry = 0;
-    if (c.y >= p.tiles_y) { c.y -= p.tiles_y; carry = 1; }
-    c.b += st_b + carry;
-  };
+  MIGAN_TILE_WALK(tile, xr, p.nchunks, p.tiles_x, p.tiles_y);              // tile0, tile_next
 
   if (groupA) {
     MIGAN_SETPRIO(2);                                    // (the critical group of this kernel)

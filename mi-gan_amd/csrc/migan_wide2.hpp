@@ -68,44 +68,15 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(kW2Threads, 3) sepconv_wide2_kernel(const 
   const int CI = p.CI;
   const int nks = CI / KS;                                           // sub-chunks per tile (a multiple of 4: the host checks CI % 64 == 0)
 
-  // ---- tile schedule: XCD-contiguous ranges walked by the persistent workgroups of each XCD (as sepconv_pipe_kernel) ----------------
-  const int ntiles = p.tiles_x * p.tiles_y * p.nchunks * p.B;
-  const int xcd = (int)blockIdx.x & 7;
-  const int tq = ntiles >> 3, tr = ntiles & 7;
-  const int tcnt = tq + (xcd < tr ? 1 : 0);
-  const int tbase = xcd < tr ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq;
-  const int tstep = ((int)gridDim.x + 7 - xcd) >> 3;
-  const int tl0 = (int)blockIdx.x >> 3;
-  const int T = tl0 < tcnt ? (tcnt - tl0 + tstep - 1) / tstep : 0;    // my tiles
+  // ---- tile schedule (MIGAN_XCD_RANGE, MIGAN_TILE_WALK: migan_kernels.hpp, migan_pipe.hpp) ----------------------------------------------
+  MIGAN_XCD_RANGE(xr, p.tiles_x * p.tiles_y * p.nchunks * p.B, (int)blockIdx.x, (int)gridDim.x);
+  const int T = MIGAN_XCD_TILES(xr);                                   // my tiles
   if (T == 0) return;                                                  // (uniform: the whole workgroup leaves)
   const int G = T * nks;                                               // my sub-steps
   // phase profile (-DMIGAN_PHASE_PROF builds): group A -> slots 0..3 [DMA issue, depthwise, vmcnt wait, barrier], group B -> 4 MFMAs (with their
   // fragment reads), 5 epilogue, 6 barrier; slot 8 counts workgroups
   PPROF_BEGIN();
-  struct TileCur {
-    int n, x, y, b;
-  };
-  const int st_n = tstep % p.nchunks, st_r1 = tstep / p.nchunks;
-  const int st_x = st_r1 % p.tiles_x, st_r2 = st_r1 / p.tiles_x;
-  const int st_y = st_r2 % p.tiles_y, st_b = st_r2 / p.tiles_y;
-  TileCur tile0;
-  {
-    int t = tbase + tl0;
-    tile0.n = t % p.nchunks; t /= p.nchunks;
-    tile0.x = t % p.tiles_x; t /= p.tiles_x;
-    tile0.y = t % p.tiles_y;
-    tile0.b = t / p.tiles_y;
-  }
-  auto tile_next = [&](TileCur& c) {
-    int carry = 0;
-    c.n += st_n;
-    if (c.n >= p.nchunks) { c.n -= p.nchunks; carry = 1; }
-    c.x += st_x + carry; carry = 0;
-    if (c.x >= p.tiles_x) { c.x -= p.tiles_x; carry = 1; }
-    c.y += st_y + carry; carry = 0;
-    if (c.y >= p.tiles_y) { c.y -= p.tiles_y; carry = 1; }
-    c.b += st_b + carry;
-  };
+  MIGAN_TILE_WALK(tile, xr, p.nchunks, p.tiles_x, p.tiles_y);              // tile0, tile_next
 
   if (groupA) {
     // =============================================== group A: every DMA + the depthwise stage ========================================

@@ -229,3 +229,22 @@ extern "C" int hipemu_log_entry(int i, const char** name, unsigned* grid, unsign
   *name = e.name.c_str(); *grid = e.grid; *block = e.block; *lds_bytes = e.lds_bytes; *args = e.args.data(); *arg_bytes = e.args.size();
   return 0;
 }
+
+// the tile schedule's shared functions on the host (mi-gan_amd/csrc/migan_kernels.hpp: MIGAN_XCD_RANGE, xcd_remap; migan_pipe.hpp: MIGAN_TILE_WALK), for
+// tests/test_emu_schedule.py.  range4 = {tbase, tcnt, tstep, tl0}; up to `cap` cursors {n, x, y, b} of the workgroup's walk; returns T
+extern "C" int hipemu_tile_walk(int tiles_x, int tiles_y, int nchunks, int B, int bid, int nblk, int* range4, int* cursors, int cap) {
+  using migan::XcdRange;
+  MIGAN_XCD_RANGE(xr, tiles_x * tiles_y * nchunks * B, bid, nblk);
+  range4[0] = xr.tbase; range4[1] = xr.tcnt; range4[2] = xr.tstep; range4[3] = xr.tl0;
+  const int T = MIGAN_XCD_TILES(xr);
+  if (T == 0) return 0;                                  // (as the kernels: no walk is made)
+  using migan::TileCur;
+  MIGAN_TILE_WALK(tile, xr, nchunks, tiles_x, tiles_y);
+  TileCur c = tile0;
+  for (int k = 0; k < T && k < cap; ++k) {
+    cursors[4 * k] = c.n; cursors[4 * k + 1] = c.x; cursors[4 * k + 2] = c.y; cursors[4 * k + 3] = c.b;
+    if (k + 1 < T) tile_next(c);
+  }
+  return T;
+}
+extern "C" int hipemu_xcd_remap(int bid, int nblk) { return migan::xcd_remap(bid, nblk); }
