@@ -26,9 +26,11 @@ SOURCES = [os.path.join(CSRC, f) for f in ("migan_hip.hip", "migan_k_slice.hip",
                                             "migan_wide2.hip", "migan_wide2.hpp", "migan_wide2_table.inc",
                                             "migan_kernels.hpp", "migan_host.hpp", "migan_rt_hip.h",
                                             "comodgan_kernels.hpp", "comodgan_conv_body.inc", "comodgan_fir_body.inc", "comodgan_fromrgb_body.inc",
-                                            "comodgan_torgb_body.inc", "comodgan_host.hpp", "migan_pipeline.hpp")] + [
+                                            "comodgan_torgb_body.inc", "comodgan_host.hpp", "migan_pipeline.hpp",
+                                            "migan_pipeline_pool_body.inc", "migan_pipeline_samples_body.inc")] + [
     os.path.join(ROOT, "include", "migan_hip.h"), os.path.join(ROOT, "include", "comodgan_hip.h"),
     os.path.join(ROOT, "include", "comodgan_samples_hip.h"), os.path.join(ROOT, "include", "migan_pipeline_samples_hip.h"),
+    os.path.join(ROOT, "include", "migan_pipeline_patches_hip.h"),
     os.path.join(ROOT, "include", "comodgan_fp16_hip.h"), os.path.join(ROOT, "include", "comodgan_fp16_storage_hip.h"),
     os.path.join(ROOT, "include", "comodgan_stages_hip.h")]
 ARCH = "gfx950"

@@ -20,6 +20,7 @@
 
 #include "../../include/migan_hip.h"
 #include "../../include/migan_pipeline_samples_hip.h"
+#include "../../include/migan_pipeline_patches_hip.h"
 #include "migan_table.hpp"
 
 namespace migan {
@@ -2098,6 +2099,51 @@ int migan_pipeline_batch_post_samples(const migan_pipeline_item* items, int n, i
     if (total)
       rt_check(rt::launch(pipe_post_samples_kernel, a, (unsigned)total, kThreads, (size_t)kPostLdsBytes, (rt::stream_t)stream),
                "migan::pipe_post_samples_kernel");
+    i0 += (size_t)k;
+  }
+  MIGAN_API_END
+}
+// the same S outputs per item as box-sized patches: item i -> outs[i] = [samples][3][ch_i][cw_i], the crop alone.  The box is on the
+// device, so the grid is pipe_post_batch_kernel's (the tiles of the whole image as an upper bound) and each item carries the
+// capacity of its destination: pipe_post_patches_kernel skips an item that would not fit (PipePatchesArgs)
+int migan_pipeline_batch_post_patches(const migan_pipeline_item* items, int n, int samples, int resolution, const void* y_nchw,
+                                      const int* bbox_dev, const float* gauss25, void* scratch, void* const* outs, const size_t* out_bytes,
+                                      void* stream) {
+  MIGAN_API_BEGIN
+  using namespace migan;
+  migan_pipeline_batch_check(resolution, bbox_dev, scratch);
+  MIGAN_CHECK(y_nchw, MIGAN_EINVAL, "null tensor");
+  MIGAN_CHECK(samples >= 1, MIGAN_EINVAL, "samples must be at least 1");
+  MIGAN_CHECK(outs != nullptr, MIGAN_EINVAL, "null outs");
+  MIGAN_CHECK(out_bytes != nullptr, MIGAN_EINVAL, "null out_bytes");
+  std::vector<PipeBatchItem> its;
+  migan_pipeline_batch_plan(items, n, true, scratch, &its);
+  for (int i = 0; i < n; ++i)
+    MIGAN_CHECK(outs[i] != nullptr || out_bytes[i] == 0, MIGAN_EINVAL, "null destination of item " + std::to_string(i) + " with a capacity");
+  PipePatchesArgs proto{};
+  proto.y = (const float*)y_nchw; proto.bbox = bbox_dev; proto.R = resolution; proto.S = samples;
+  migan_pipeline_gauss(gauss25, proto.gauss);
+  const size_t plane = (size_t)resolution * resolution;
+  for (size_t i0 = 0; i0 < its.size();) {
+    PipePatchesArgs a = proto;
+    unsigned long long total = 0;
+    int k = 0;
+    for (; k < kPipePatchesMax && i0 + k < its.size(); ++k) {
+      const PipeBatchItem& it = its[i0 + k];
+      const unsigned long long t = (unsigned long long)cdiv(it.W, kPostTW) * (unsigned long long)cdiv(it.H, kPostTH);
+      if (k > 0 && total + t > 0x7fffffffull) break;
+      a.item[k] = PipePatchesItem{it.image, it.mask_resized ? it.mask_resized : it.mask_src, (unsigned char*)outs[i0 + k],
+                                  (unsigned long long)out_bytes[i0 + k], it.H, it.W};
+      a.first[k] = (int)total;
+      total += t;
+    }
+    a.first[k] = (int)total;
+    a.n = k;
+    a.y += i0 * (size_t)samples * 3 * plane;
+    a.bbox += i0 * 4;
+    if (total)
+      rt_check(rt::launch(pipe_post_patches_kernel, a, (unsigned)total, kThreads, (size_t)kPostLdsBytes, (rt::stream_t)stream),
+               "migan::pipe_post_patches_kernel");
     i0 += (size_t)k;
   }
   MIGAN_API_END

@@ -13,8 +13,8 @@
 // Two forms: one image per call with the box on the host (PipeArgs; migan_pipeline_bbox / _pre / _post), and a batch of up to
 // kPipeBatchMax images of different sizes per launch with the box kept on the device (PipeBatchArgs; migan_pipeline_batch_pre /
 // _post): 1-D grids, workgroup -> (item, tile) through the prefix table in the argument, no host synchronisation in between.
-// The batch form's post step also exists out of place, for S generator outputs per image (PipeSamplesArgs;
-// migan_pipeline_batch_post_samples).
+// The batch form's post step also exists out of place, for S generator outputs per image: as whole images (PipeSamplesArgs;
+// migan_pipeline_batch_post_samples) and as box-sized patches (PipePatchesArgs; migan_pipeline_batch_post_patches).
 #pragma once
 
 #ifndef MIGAN_HOST_DEVICE          // (the CPU emulator build is host code throughout)
@@ -439,25 +439,8 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_post_samples_kernel(const Pip
   // workgroup-uniform: the tile has a pixel inside the crop
   const bool blend = ty0 < ch && ty0 + kPostTH > 0 && tx0 < cw && tx0 + kPostTW > 0;
   const int t = (int)threadIdx.x;
-  if (blend) {
-    for (int e = t; e < kPostWH * kPostWW; e += kThreads) {
-      const int cy = ty0 - 3 + e / kPostWW, cx = tx0 - 3 + e % kPostWW;
-      win[e] = (cy >= 0 && cy < ch && cx >= 0 && cx < cw) ? it.mask[(size_t)(y_min + cy) * it.W + x_min + cx] : (unsigned char)0;
-    }
-    __syncthreads();
-    for (int e = t; e < kPostPH * kPostPW; e += kThreads) {
-      const unsigned char* w0 = win + e / kPostPW * kPostWW + e % kPostPW;
-      int m = 0;
-#pragma unroll
-      for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-        for (int dx = 0; dx < 3; ++dx) {
-          const int v = w0[dy * kPostWW + dx];
-          m = v > m ? v : m;
-        }
-      pool[e] = (unsigned char)m;
-    }
-    __syncthreads();
+  if (blend) {                                                       // steps 1 and 2: one text with pipe_post_patches_kernel
+#include "migan_pipeline_pool_body.inc"
   }
   const int row = iy0 + t / kPostTW, col = ix0 + t % kPostTW;
   if (row >= it.H || col >= it.W) return;
@@ -471,33 +454,62 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_post_samples_kernel(const Pip
     }
     return;
   }
-  double acc = 0.0;
-  for (int ky = 0; ky < 5; ++ky) {
-    const int yy = pipe_reflect(py + ky - 2, ch) - (ty0 - 2);
-    for (int kx = 0; kx < 5; ++kx) {
-      const int xx = pipe_reflect(px + kx - 2, cw) - (tx0 - 2);
-      acc += (double)p.gauss[ky * 5 + kx] * (double)pool[yy * kPostPW + xx];
-    }
-  }
-  const PipePostCoord c = pipe_post_coord(p.R, cw, ch, py, px, acc);
-  const size_t oplane3 = (size_t)3 * p.R * p.R;
-  const float* y = p.y + (size_t)k * p.S * oplane3;
-  const size_t oplane = (size_t)p.R * p.R;
-  for (int s = 0; s < p.S; ++s) {
-    unsigned char* o = it.out + (size_t)s * 3 * plane + at;
-    // The blend of pipe_post_byte, img * mk + o * (1 - mk), is contracted by the compiler into one rounded product and an FMA, and
-    // which product stays exact follows from where the two are computed.  img * mk does not depend on the sample: lifted out of
-    // this loop it would be the rounded one, the other way round than in pipe_post_pixel, and a result next to an integer would
-    // differ from pipe_post_batch_kernel's by one.  With mk opaque in every pass both products are formed here, as there.
-    PipePostCoord cs = c;
-    MIGAN_OPAQUE_F(cs.mk);
-#pragma unroll
-    for (int ch3 = 0; ch3 < 3; ++ch3) {
-      float t[4];
-      pipe_post_taps(y + ((size_t)s * 3 + ch3) * oplane, p.R, cs, t);
-      o[ch3 * plane] = pipe_post_byte(t, cs, img[ch3]);
-    }
-  }
+  // step 3, pipe_post_coord and the loop over the samples, into plane stride `plane` at offset `at`: one text with pipe_post_patches_kernel
+#include "migan_pipeline_samples_body.inc"
+}
+
+// ---- several completions per image, as box-sized patches ---------------------------------------------------------------------------
+// The same S results per crop pixel as pipe_post_samples_kernel, but only the crop is written: item k's destination is the tightly
+// packed [S][3][ch][cw], byte (s, c, py, px) at out + ((s * 3 + c) * ch + py) * cw + px.  Nothing outside the box is read or
+// written, so the tiles are again those of the CROP, as in pipe_post_batch_kernel: the grid is sized from the image, tile t is
+// (t / ntx, t % ntx) of the crop's ntx = cdiv(cw, TW) columns, and the surplus workgroups leave at once.  The three LDS steps, the
+// per-pixel values and the sample loop are pipe_post_samples_kernel's text (the two .inc bodies), around another destination.
+// The size of the patches is device data (the box), the size of the destination host data: each item carries its destination's
+// capacity, and an item whose S * 3 * ch * cw bytes exceed it is skipped whole, like one whose box does not fit its image -- a wrong
+// size on the host leaves a destination unwritten, it does not become a store out of bounds.
+constexpr int kPipePatchesMax = 32;
+struct PipePatchesItem {
+  const unsigned char* image;        // [3][H][W] uint8, read only, and only inside the box
+  const unsigned char* mask;         // [H][W]: the caller's mask, or its nearest resize in scratch
+  unsigned char* out;                // [S][3][ch][cw] uint8
+  unsigned long long capacity;       // bytes `out` can take
+  int H, W;
+};
+struct PipePatchesArgs {
+  PipePatchesItem item[kPipePatchesMax];
+  int first[kPipePatchesMax + 1];
+  const float* y;                    // [n * S][3][R][R], row k * S + s = sample s of item k
+  const int* bbox;                   // [n][4], as PipeBatchArgs::bbox
+  int n, R, S;
+  float gauss[25];
+};
+static_assert(sizeof(PipePatchesArgs) <= 2048, "the patches argument must stay well under the 4 KB kernel-argument limit");
+
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_post_patches_kernel(const PipePatchesArgs p) {
+  MIGAN_DYN_SMEM(smem);
+  unsigned char* win = reinterpret_cast<unsigned char*>(smem);       // [kPostWH][kPostWW]: crop rows ty0 - 3 ..., columns tx0 - 3 ...
+  unsigned char* pool = win + kPostWinBytes;                         // [kPostPH][kPostPW]: crop rows ty0 - 2 ..., columns tx0 - 2 ...
+  int k = 0;
+  while (k + 1 < p.n && (int)blockIdx.x >= p.first[k + 1]) ++k;      // (wave-uniform, as pipe_batch_item)
+  const PipePatchesItem& it = p.item[k];
+  const int* box = p.bbox + 4 * k;
+  // the box came through device memory: one that does not fit the image has no patch ...
+  if (!pipe_box_valid(box, it.H, it.W)) return;
+  const int x_min = box[0], y_min = box[2], cw = box[1] - box[0], ch = box[3] - box[2];
+  // ... and one whose patches do not fit the destination is not started (ch * cw < 2^30 and S < 2^31: no overflow in 64 bits)
+  const size_t plane = (size_t)ch * cw;                              // the destination's channel stride
+  if ((unsigned long long)p.S * 3ull * plane > it.capacity) return;
+  const int tile = (int)blockIdx.x - p.first[k], ntx = (cw + kPostTW - 1) / kPostTW;
+  const int ty0 = tile / ntx * kPostTH, tx0 = tile % ntx * kPostTW;
+  if (ty0 >= ch) return;                                             // (workgroup-uniform, like the returns above)
+  const int t = (int)threadIdx.x;
+#include "migan_pipeline_pool_body.inc"                              // steps 1 and 2
+  const int py = ty0 + t / kPostTW, px = tx0 + t % kPostTW;
+  if (py >= ch || px >= cw) return;
+  const size_t iplane = (size_t)it.H * it.W, iat = (size_t)(y_min + py) * it.W + x_min + px;
+  const unsigned char img[3] = {it.image[iat], it.image[iplane + iat], it.image[2 * iplane + iat]};
+  const size_t at = (size_t)py * cw + px;                            // the pixel in a plane of the destination
+#include "migan_pipeline_samples_body.inc"                           // step 3, pipe_post_coord, the loop over the samples
 }
 #endif  // MIGAN_TEMPLATE_KERNELS_ONLY
 

@@ -81,6 +81,8 @@ SAMPLES_EXPORTS = ("comodgan_workspace_bytes_samples", "comodgan_forward_samples
                    "comodgan_debug_tensor_samples")
 # include/migan_pipeline_samples_hip.h
 PIPELINE_SAMPLES_EXPORTS = ("migan_pipeline_batch_post_samples",)
+# include/migan_pipeline_patches_hip.h
+PIPELINE_PATCHES_EXPORTS = ("migan_pipeline_batch_post_patches",)
 # include/comodgan_fp16_hip.h
 FP16_EXPORTS = ("comodgan_set_fp16_blocks", "comodgan_get_fp16_blocks")
 # include/comodgan_fp16_storage_hip.h
@@ -150,7 +152,7 @@ class MiganLib:
         except OSError as e:  # pragma: no cover - depends on the machine
             raise MiganError(f"cannot load {self.path}: {e}") from e
         L = self.lib
-        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS:
+        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + PIPELINE_PATCHES_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS:
             if not hasattr(L, name):
                 raise MiganError(f"{self.path} does not export {name}")
         vp, ci = C.c_void_p, C.c_int
@@ -174,6 +176,8 @@ class MiganLib:
         L.migan_pipeline_batch_pre.argtypes = [C.POINTER(PipelineItem), ci, ci, ci, vp, vp, vp, vp]
         L.migan_pipeline_batch_post.argtypes = [C.POINTER(PipelineItem), ci, ci, vp, vp, C.POINTER(C.c_float), vp, vp]
         L.migan_pipeline_batch_post_samples.argtypes = [C.POINTER(PipelineItem), ci, ci, ci, vp, vp, C.POINTER(C.c_float), vp, C.POINTER(vp), vp]
+        L.migan_pipeline_batch_post_patches.argtypes = [C.POINTER(PipelineItem), ci, ci, ci, vp, vp, C.POINTER(C.c_float), vp, C.POINTER(vp),
+                                                        C.POINTER(C.c_size_t), vp]
         L.migan_num_weights.argtypes = [vp, C.POINTER(ci)]
         L.migan_weight_info.argtypes = [vp, ci, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(ci), C.POINTER(ci)]
         L.migan_set_weight.argtypes = [vp, C.c_char_p, vp, C.POINTER(C.c_int64), ci]
@@ -234,7 +238,7 @@ class MiganLib:
         if not allow_test_backend and L.migan_backend().decode() != PRODUCT_BACKEND:
             raise MiganError(f"{self.path} reports backend {L.migan_backend().decode()!r}, not {PRODUCT_BACKEND!r}: only the gfx950 HIP "
                              f"library is a product backend (the CPU emulator build is test infrastructure)")
-        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS:
+        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + PIPELINE_PATCHES_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS:
             if name not in ("migan_last_error", "migan_last_kernel", "migan_nan_policy", "migan_backend", "migan_gemm_variant", "migan_tuning_key"):
                 getattr(L, name).restype = ci
 
@@ -343,6 +347,21 @@ class MiganLib:
             raise ValueError(f"expected one destination per item, got {len(out_ptrs)} for {len(items)} items")
         self.check(self.lib.migan_pipeline_batch_post_samples(pipeline_items(items), len(items), int(samples), int(resolution),
                                                               C.c_void_p(y_ptr), C.c_void_p(bbox_ptr), g, C.c_void_p(scratch_ptr), outs,
+                                                              C.c_void_p(stream)))
+
+    def pipeline_batch_post_patches(self, items, samples: int, resolution: int, y_ptr: int, bbox_ptr: int, scratch_ptr: int, out_ptrs,
+                                    out_bytes, gauss25=None, stream: int = 0) -> None:
+        """include/migan_pipeline_patches_hip.h: y [len(items) * samples, 3, R, R] -> out_ptrs[i] = [samples, 3, ch_i, cw_i] uint8, the
+        crop of item i alone; out_bytes[i] = the capacity of out_ptrs[i] in bytes (an item that needs more is skipped).  One entry of
+        each per item (None passes a null table through)"""
+        g = None if gauss25 is None else (C.c_float * 25)(*[float(v) for v in gauss25])
+        outs = None if out_ptrs is None else (C.c_void_p * max(1, len(out_ptrs)))(*[p or None for p in out_ptrs])
+        caps = None if out_bytes is None else (C.c_size_t * max(1, len(out_bytes)))(*[int(b) for b in out_bytes])
+        for what, table in (("destination", out_ptrs), ("capacity", out_bytes)):
+            if table is not None and len(table) != len(items):
+                raise ValueError(f"expected one {what} per item, got {len(table)} for {len(items)} items")
+        self.check(self.lib.migan_pipeline_batch_post_patches(pipeline_items(items), len(items), int(samples), int(resolution),
+                                                              C.c_void_p(y_ptr), C.c_void_p(bbox_ptr), g, C.c_void_p(scratch_ptr), outs, caps,
                                                               C.c_void_p(stream)))
 
     def sepconv_forward(self, stream: int = 0, **kw) -> None:

@@ -61,7 +61,10 @@ class MIGAN_Pipeline(torch.nn.Module):
     images, with the boxes kept on the device (``migan_pipeline_batch_pre / _post``): no host synchronisation in between.
 
     ``forward_samples(images, masks, z)`` leaves the images as they are and returns S completions of each, [S, 3, H_i, W_i], from one
-    pass over the image per chunk (``migan_pipeline_batch_post_samples``)."""
+    pass over the image per chunk (``migan_pipeline_batch_post_samples``).
+
+    ``forward_patches(images, masks, z)`` returns the same completions as box-sized patches, [S, 3, ch_i, cw_i], and the boxes
+    (``migan_pipeline_batch_post_patches``): the pixels outside a box are the photo's in every completion."""
 
     def __init__(self, model_path, resolution: int, padding: int = 128, device="cuda"):
         super().__init__()
@@ -206,24 +209,9 @@ class MIGAN_Pipeline(torch.nn.Module):
                                         stream=stream)
         return (images, bbox) if return_bbox else images
 
-    @torch.no_grad()
-    def forward_samples(self, images, masks, z=None, samples=None, *, max_rows: int = 32, return_bbox: bool = False, **model_kwargs):
-        """S completions per image, written OUT OF PLACE: images and masks as for ``forward_batch`` and not modified -> a list of
-        uint8 tensors [S, 3, H_i, W_i] (views of one allocation), with ``return_bbox`` also the int32 [N, 4] device tensor of boxes.
-
-        A model with a ``forward_samples`` method (``comodgan.Generator``): ``z`` [N, S, z_dim], or ``samples=S`` draws it;
-        ``model_kwargs`` (truncation_psi, truncation_cutoff, noise_mode) go to the model unchanged.  Per chunk of ``max_rows // S``
-        images: boxes and x once per image -> ``model.forward_samples(x, z)``: the encoder once per image, [n * S, 3, R, R] ->
-        ``migan_pipeline_batch_post_samples``: each image read once, its feathered mask built once, S images written.  No host
-        synchronisation in between.
-
-        Any other model (the MI-GAN generator) gives one completion: ``z`` must be None and S is 1; ``self.model(x)`` runs on
-        ``forward_batch``'s chunks (``max_rows`` images, a lone last chunk at batch 2), so ``forward_samples(images, masks)[i][0]``
-        holds the bytes ``forward_batch`` writes into a copy of images[i].
-
-        Inside its box, sample s of image i is what ``forward_batch`` gives a copy of the image for that generator output; outside
-        it is the image.  An image whose mask yields no usable box is returned as S plain copies."""
-        images, masks = list(images), list(masks)
+    def _samples_plan(self, images, masks, z, samples, max_rows, model_kwargs):
+        """the argument checks forward_samples and forward_patches share -> items, device, the model's forward_samples or None, S,
+        images per chunk, z (drawn here when the caller gave `samples` alone)"""
         if len(images) != len(masks) or not images:
             raise RuntimeError(f"expected as many masks as images and at least one, got {len(images)} images and {len(masks)} masks")
         if int(max_rows) < 1:
@@ -257,6 +245,46 @@ class MIGAN_Pipeline(torch.nn.Module):
             if s > max_rows:
                 raise ValueError(f"{s} samples per image do not fit max_rows={max_rows} generator rows per chunk: raise max_rows")
             per_chunk = max_rows // s
+        return items, device, sampler, s, per_chunk, z
+
+    def _samples_pre(self, lib, items, i0, per_chunk, sampler, box, device, stream):
+        """pipeline_batch_pre of the chunk that starts at image i0 -> its item tuples, scratch and x; `box` = its rows of the box table"""
+        chunk = [it[:6] for it in items[i0:i0 + per_chunk]]
+        scratch = self._scratch_bytes(lib.pipeline_batch_scratch_bytes(chunk), device)
+        # (without a sampler: forward_batch's rule for a lone last chunk, so that the bytes are forward_batch's)
+        pad = 1 if sampler is None and len(chunk) == 1 and len(items) > 1 and per_chunk > 1 else 0
+        x = torch.empty((len(chunk) + pad, 4, self.res, self.res), dtype=torch.float32, device=device)
+        lib.pipeline_batch_pre(chunk, self.res, self.padding, x.data_ptr(), box.data_ptr(), scratch.data_ptr(), stream)
+        if pad:
+            x[1].copy_(x[0])
+        return chunk, scratch, x
+
+    def _samples_generate(self, x, n, sampler, z, s, model_kwargs):
+        """the generator on one chunk of n images -> y, contiguous, rows i * S + s"""
+        if sampler is None:
+            return self.model(x).contiguous()
+        return sampler(x, z, **model_kwargs).reshape(n * s, 3, self.res, self.res).contiguous()
+
+    @torch.no_grad()
+    def forward_samples(self, images, masks, z=None, samples=None, *, max_rows: int = 32, return_bbox: bool = False, **model_kwargs):
+        """S completions per image, written OUT OF PLACE: images and masks as for ``forward_batch`` and not modified -> a list of
+        uint8 tensors [S, 3, H_i, W_i] (views of one allocation), with ``return_bbox`` also the int32 [N, 4] device tensor of boxes.
+
+        A model with a ``forward_samples`` method (``comodgan.Generator``): ``z`` [N, S, z_dim], or ``samples=S`` draws it;
+        ``model_kwargs`` (truncation_psi, truncation_cutoff, noise_mode) go to the model unchanged.  Per chunk of ``max_rows // S``
+        images: boxes and x once per image -> ``model.forward_samples(x, z)``: the encoder once per image, [n * S, 3, R, R] ->
+        ``migan_pipeline_batch_post_samples``: each image read once, its feathered mask built once, S images written.  No host
+        synchronisation in between.
+
+        Any other model (the MI-GAN generator) gives one completion: ``z`` must be None and S is 1; ``self.model(x)`` runs on
+        ``forward_batch``'s chunks (``max_rows`` images, a lone last chunk at batch 2), so ``forward_samples(images, masks)[i][0]``
+        holds the bytes ``forward_batch`` writes into a copy of images[i].
+
+        Inside its box, sample s of image i is what ``forward_batch`` gives a copy of the image for that generator output; outside
+        it is the image.  An image whose mask yields no usable box is returned as S plain copies."""
+        images, masks = list(images), list(masks)
+        items, device, sampler, s, per_chunk, z = self._samples_plan(images, masks, z, samples, max_rows, model_kwargs)
+        n_img = len(items)
         lib = load_library()
         bbox = torch.empty((n_img, 4), dtype=torch.int32, device=device)
         sizes = [3 * it[2] * it[3] for it in items]
@@ -268,19 +296,57 @@ class MIGAN_Pipeline(torch.nn.Module):
         with torch.cuda.device(device):                          # the handle-free entry points launch on the CURRENT device
             stream = int(torch.cuda.current_stream(device).cuda_stream)
             for i0 in range(0, n_img, per_chunk):
-                chunk = [it[:6] for it in items[i0:i0 + per_chunk]]
-                scratch = self._scratch_bytes(lib.pipeline_batch_scratch_bytes(chunk), device)
-                box = bbox[i0:i0 + len(chunk)]
-                # (without a sampler: forward_batch's rule for a lone last chunk, so that the bytes are forward_batch's)
-                pad = 1 if sampler is None and len(chunk) == 1 and n_img > 1 and per_chunk > 1 else 0
-                x = torch.empty((len(chunk) + pad, 4, self.res, self.res), dtype=torch.float32, device=device)
-                lib.pipeline_batch_pre(chunk, self.res, self.padding, x.data_ptr(), box.data_ptr(), scratch.data_ptr(), stream)
-                if pad:
-                    x[1].copy_(x[0])
-                if sampler is None:
-                    y = self.model(x).contiguous()
-                else:
-                    y = sampler(x, z[i0:i0 + len(chunk)], **model_kwargs).reshape(len(chunk) * s, 3, self.res, self.res).contiguous()
+                box = bbox[i0:i0 + per_chunk]
+                chunk, scratch, x = self._samples_pre(lib, items, i0, per_chunk, sampler, box, device, stream)
+                y = self._samples_generate(x, len(chunk), sampler, None if z is None else z[i0:i0 + len(chunk)], s, model_kwargs)
                 lib.pipeline_batch_post_samples(chunk, s, self.res, y.data_ptr(), box.data_ptr(), scratch.data_ptr(),
                                                 [o.data_ptr() for o in outs[i0:i0 + len(chunk)]], gauss25=self._gauss, stream=stream)
         return (outs, bbox) if return_bbox else outs
+
+    @torch.no_grad()
+    def forward_patches(self, images, masks, z=None, samples=None, *, max_rows: int = 32, **model_kwargs):
+        """``forward_samples`` for a caller that wants only what differs between the completions: -> (patches, boxes), where
+        patches[i] is uint8 [S, 3, ch_i, cw_i] on the device, the crop [y_min, y_max) x [x_min, x_max) of image i in every
+        completion, and boxes the int32 CPU tensor [N, 4] of {x_min, x_max, y_min, y_max} rows.  Nothing outside the boxes is read
+        or written, and the result takes S * 3 * ch * cw bytes per image instead of S * 3 * H * W.
+
+        Arguments, checks, chunks (``max_rows // S`` images; for a model without ``forward_samples`` ``max_rows`` images and a lone
+        last chunk at batch 2) and errors are ``forward_samples``'.  With the same model, z, ``model_kwargs`` (``noise_mode="const"``:
+        random noise differs from call to call) and ``max_rows``, byte for byte:
+
+            patches[i] == forward_samples(...)[i][:, :, y_min:y_max, x_min:x_max]
+
+        Per chunk: boxes and x once per image -> the chunk's boxes are copied to the host, which sizes the result: ONE HOST
+        SYNCHRONISATION PER CHUNK, the only one of this mode (``forward_samples`` has none) -> the generator ->
+        ``migan_pipeline_batch_post_patches``.  patches[i] is a view of its chunk's one allocation; an image whose mask yields no
+        usable box gets an empty patch, [S, 3, 0, 0].  Images and masks are not modified."""
+        images, masks = list(images), list(masks)
+        items, device, sampler, s, per_chunk, z = self._samples_plan(images, masks, z, samples, max_rows, model_kwargs)
+        n_img = len(items)
+        lib = load_library()
+        bbox = torch.empty((n_img, 4), dtype=torch.int32, device=device)
+        patches, boxes = [], []
+        with torch.cuda.device(device):                          # the handle-free entry points launch on the CURRENT device
+            stream = int(torch.cuda.current_stream(device).cuda_stream)
+            for i0 in range(0, n_img, per_chunk):
+                box = bbox[i0:i0 + per_chunk]
+                chunk, scratch, x = self._samples_pre(lib, items, i0, per_chunk, sampler, box, device, stream)
+                rows = box.cpu()                                 # (waits for the boxes: the synchronisation of this mode)
+                shapes = []
+                for (x0, x1, y0, y1), it in zip(rows.tolist(), chunk):
+                    # migan_pipeline.hpp: pipe_box_valid -- the kernel skips any other box, and an empty patch has nothing to skip
+                    fits = x0 >= 0 and x1 <= it[3] and y0 >= 0 and y1 <= it[2] and x1 - x0 >= 3 and y1 - y0 >= 3
+                    shapes.append((y1 - y0, x1 - x0) if fits else (0, 0))
+                sizes = [s * 3 * h * w for h, w in shapes]
+                flat = torch.empty(sum(sizes), dtype=torch.uint8, device=device)   # exactly the chunk's patches; the list holds views
+                outs, at = [], 0
+                for (h, w), size in zip(shapes, sizes):
+                    outs.append(flat[at:at + size].view(s, 3, h, w))
+                    at += size
+                y = self._samples_generate(x, len(chunk), sampler, None if z is None else z[i0:i0 + len(chunk)], s, model_kwargs)
+                lib.pipeline_batch_post_patches(chunk, s, self.res, y.data_ptr(), box.data_ptr(), scratch.data_ptr(),
+                                                [o.data_ptr() if size else 0 for o, size in zip(outs, sizes)], sizes,
+                                                gauss25=self._gauss, stream=stream)
+                patches += outs
+                boxes.append(rows)
+        return patches, torch.cat(boxes)
