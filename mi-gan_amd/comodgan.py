@@ -368,6 +368,84 @@ class Generator(nn.Module):
                                None if noise is None else noise.data_ptr(), self._stream(x), timed=_timed)
         return (y, ms) if _timed else y
 
+    # ------------------------------------------------------------------ uint8 in / uint8 out (include/comodgan_u8_hip.h)
+    def _check_uint8(self, img_u8: torch.Tensor, mask_u8: torch.Tensor, what: str) -> None:
+        r = self.img_resolution
+        if not (img_u8.is_cuda and mask_u8.is_cuda):
+            raise RuntimeError(f"mi-gan_amd comodgan.Generator.{what} needs tensors on an MI355X (HIP) device; there is no CPU path")
+        if img_u8.dtype != torch.uint8 or mask_u8.dtype != torch.uint8:
+            raise RuntimeError("image and mask must be uint8 (np.array of the PIL images, reference demo.py:59-60)")
+        if img_u8.dim() != 4 or tuple(img_u8.shape[1:]) != (r, r, 3) or tuple(mask_u8.shape) != tuple(img_u8.shape[:3]):
+            raise RuntimeError(f"expected image [N,{r},{r},3] and mask [N,{r},{r}], got {list(img_u8.shape)} and {list(mask_u8.shape)}")
+        if img_u8.shape[0] == 0:
+            raise RuntimeError("empty batch")
+
+    def _forward_uint8(self, img_u8: torch.Tensor, mask_u8: torch.Tensor, z: torch.Tensor, truncation_psi, truncation_cutoff, noise_mode: str,
+                       _timed: bool = False):
+        """img [N,R,R,3], mask [N,R,R], z [N,S,z_dim] (checked by the callers) -> [N,S,R,R,3]; handle state as in forward_samples"""
+        n, s, r = z.shape[0], z.shape[1], self.img_resolution
+        h = self._engine(img_u8)
+        img_u8, mask_u8 = img_u8.contiguous(), mask_u8.contiguous()
+        z = z.to(device=img_u8.device, dtype=torch.float32).contiguous()
+        noise = None
+        if noise_mode == "random":
+            noise = torch.randn(n * s * h.noise_floats(), dtype=torch.float32, device=img_u8.device)    # one draw per sample and layer
+        cutoff = None if truncation_cutoff is None else int(truncation_cutoff)
+        if cutoff != self._cutoff:                               # (part of the workspace layout: set before sizing it)
+            h.set_truncation_cutoff(cutoff)
+            self._cutoff = cutoff
+        ws = self._workspace(h, n, img_u8.device, s)             # (the layout does not depend on the I/O mode)
+        if self._refreeze:
+            h.assume_static_weights(self._frozen)
+            self._refreeze = False
+        out = torch.empty((n, s, r, r, 3), dtype=torch.uint8, device=img_u8.device)
+        ms = h.forward_u8(img_u8.data_ptr(), mask_u8.data_ptr(), z.data_ptr(), out.data_ptr(), n, s, ws.data_ptr(), ws.numel(),
+                          float(truncation_psi), noise_mode, None if noise is None else noise.data_ptr(), self._stream(img_u8), timed=_timed)
+        return (out, ms) if _timed else out
+
+    def forward_uint8(self, img_u8: torch.Tensor, mask_u8: torch.Tensor, z: Optional[torch.Tensor] = None, truncation_psi: float = 1,
+                      truncation_cutoff=None, noise_mode: str = "random", _timed: bool = False):
+        """scripts/demo.py:56-66 + forward + :135-140 in one call, at network resolution: uint8 image [N,R,R,3] (HWC) and uint8 mask
+        [N,R,R] (255 = known pixel, anything else = hole), z [N,z_dim] (drawn with torch.randn when None) -> composited uint8 image
+        [N,R,R,3].  preprocess() runs inside the FromRGB kernel and the post-processing + composition inside the last ToRGB kernel: no
+        fp32 network input or output tensor exists.  Bit-identical to pipeline.preprocess -> forward -> pipeline.compose with the same
+        options (and, noise_mode "random", the same noise).  The inputs are not modified."""
+        assert noise_mode in ["random", "const", "none"]         # stylegan.py:280
+        if truncation_cutoff is not None and (int(truncation_cutoff) != truncation_cutoff or truncation_cutoff < 0):
+            raise ValueError(f"truncation_cutoff must be a non-negative integer or None, got {truncation_cutoff!r}")
+        self._check_uint8(img_u8, mask_u8, "forward_uint8")
+        n = img_u8.shape[0]
+        if z is None:
+            z = torch.randn([n, self.z_dim]).to(img_u8.device)   # comodgan.py:439
+        if z.shape != (n, self.z_dim):
+            raise RuntimeError(f"expected z of shape [{n}, {self.z_dim}], got {list(z.shape)}")
+        res = self._forward_uint8(img_u8, mask_u8, z.reshape(n, 1, self.z_dim), truncation_psi, truncation_cutoff, noise_mode, _timed)
+        return (res[0][:, 0], res[1]) if _timed else res[:, 0]
+
+    def forward_samples_uint8(self, img_u8: torch.Tensor, mask_u8: torch.Tensor, z: Optional[torch.Tensor] = None, samples: Optional[int] = None,
+                              truncation_psi: float = 1, truncation_cutoff=None, noise_mode: str = "random", _timed: bool = False):
+        """forward_samples on bytes: uint8 image [N,R,R,3] and mask [N,R,R]; z [N,S,z_dim], or None with ``samples=S`` -> uint8
+        [N,S,R,R,3].  ``out[i, s]`` is ``compose(forward_samples(preprocess(img, mask), z)[i, s], img[i], mask[i])`` byte for byte with the
+        same options: completion s of photo i pasted over photo i's known pixels, the encoder once per photo, nothing repeated by the
+        caller and no fp32 image held."""
+        assert noise_mode in ["random", "const", "none"]         # stylegan.py:280
+        if truncation_cutoff is not None and (int(truncation_cutoff) != truncation_cutoff or truncation_cutoff < 0):
+            raise ValueError(f"truncation_cutoff must be a non-negative integer or None, got {truncation_cutoff!r}")
+        self._check_uint8(img_u8, mask_u8, "forward_samples_uint8")
+        n = img_u8.shape[0]
+        if samples is not None and (int(samples) != samples or samples < 1):
+            raise ValueError(f"samples must be a positive integer or None, got {samples!r}")
+        if z is None:
+            if samples is None:
+                raise ValueError("forward_samples_uint8 needs z of shape [N, S, z_dim], or samples=S to draw it")
+            z = torch.randn([n, int(samples), self.z_dim]).to(img_u8.device)
+        else:
+            if z.dim() != 3 or z.shape[0] != n or z.shape[1] < 1 or z.shape[2] != self.z_dim:
+                raise RuntimeError(f"expected z of shape [{n}, S, {self.z_dim}] (S latents per image), got {list(z.shape)}")
+            if samples is not None and int(samples) != z.shape[1]:
+                raise ValueError(f"samples={samples} contradicts z of shape {list(z.shape)}")
+        return self._forward_uint8(img_u8, mask_u8, z, truncation_psi, truncation_cutoff, noise_mode, _timed)
+
     # ------------------------------------------------------------------ the stages (include/comodgan_stages_hip.h)
     def _stage_workspace(self, h: CoModGANHandle, batch: int, samples: int, device: torch.device) -> torch.Tensor:
         """One workspace for the stage calls and the fused forward: the prepared weight planes at its head serve all of them."""

@@ -10,6 +10,7 @@
 #include "../../include/comodgan_fp16_hip.h"
 #include "../../include/comodgan_fp16_storage_hip.h"
 #include "../../include/comodgan_stages_hip.h"
+#include "../../include/comodgan_u8_hip.h"
 
 namespace migan {
 
@@ -241,9 +242,10 @@ struct CmPlanKey {
   bool fp16_storage = false;         // comodgan_set_fp16_storage: those blocks keep their activations in fp16
   int stage = 0;                     // CM_STAGE_*: the fused forward, or one stage of include/comodgan_stages_hip.h
   unsigned parts = 0;                // comodgan_synthesize: bit log2(res) set = the ToRGB of block b<res> also stores its un-added output
+  bool u8 = false;                   // comodgan_forward_u8: photo and mask bytes in, composited bytes out (the first and the last launch differ)
   bool operator==(const CmPlanKey& o) const {
     return batch == o.batch && samples == o.samples && debug == o.debug && trunc_cutoff == o.trunc_cutoff && forced == o.forced &&
-           fp16_enc == o.fp16_enc && fp16_syn == o.fp16_syn && fp16_storage == o.fp16_storage && stage == o.stage && parts == o.parts;
+           fp16_enc == o.fp16_enc && fp16_syn == o.fp16_syn && fp16_storage == o.fp16_storage && stage == o.stage && parts == o.parts && u8 == o.u8;
   }
 };
 // What a walk runs: everything (comodgan_forward / comodgan_forward_samples), or one stage with its stage tensors in caller memory
@@ -290,7 +292,7 @@ struct comodgan_handle {
   // Workspace bytes of a forward at this batch (images) and sample count.  Sizes the network again unless the cached plan was made
   // for the same batch, samples, debug flag, truncation cutoff and forced kernel forms: infos / debug_tensors / events can never
   // belong to another launch sequence.
-  size_t ensure_planned(int batch, int samples = 1, int stage = 0, unsigned parts = 0) const;
+  size_t ensure_planned(int batch, int samples = 1, int stage = 0, unsigned parts = 0, bool u8 = false) const;
 };
 
 // Mirror of mi-gan_amd/comodgan_schema.py::entries (the state_dict's registration order) and, from the same loops, the network as
@@ -418,6 +420,12 @@ struct CmWalk {
   const float* ws_rows = nullptr;
   float *w0_ext = nullptr, *feat_ext[16] = {}, *rgb_ext[16] = {}, *img_ext[16] = {};
   bool staged() const { return stage != CM_STAGE_FUSED; }
+  // The I/O mode (CmPlanKey::u8, fused forward only): fromrgb() reads the caller's photo and mask bytes instead of x, the res == R
+  // call of torgb() writes the caller's composited bytes instead of y.  Neither x nor y exists, and nothing in the workspace does
+  // in their place: the layout is the fp32 mode's.
+  bool u8 = false;
+  const unsigned char *img_u8 = nullptr, *mask_u8 = nullptr;    // [N][R][R][3], [N][R][R]
+  unsigned char* out_u8 = nullptr;                              // [B][R][R][3]
 
   CmWalk(comodgan_handle& handle, int batch, int samples, const CmForced& f, bool size_only)
       : h(handle), net(handle.net), N(batch), S(samples), B(batch * samples), nb(batch), forced(f), sizing(size_only) {}
@@ -553,11 +561,19 @@ struct CmWalk {
 
   // The streaming layers.  `half` flags (fp16 storage) pick the typed twin of a kernel; the reported bytes follow from esz() of each
   // tensor, so the fp32 figures are the esz == 4 case of one formula.
-  // FromRGB of the first encoder block: the network input (4 fp32 planes) -> out ([R][R][c0])
+  // FromRGB of the first encoder block: the network input (4 fp32 planes; uint8 mode: 3 + 1 bytes per pixel) -> out ([R][R][c0])
   void fromrgb(float* out, bool yh) {
     const int R = h.cfg.resolution, c0 = h.channels(R);
     CmFromRgbArgs a{};
     a.x = x; a.w = weight(net.fromrgb.w); a.b = weight(net.fromrgb.b); a.y = out; a.wgain = 0.5f; a.B = N; a.R = R; a.C = c0;
+    if (u8) {
+      CmFromRgbU8Args q{};
+      q.f = a; q.f.x = nullptr; q.img = img_u8; q.mask = mask_u8;
+      const CmFromRgbU8Form k = cm_fromrgb_u8_form(yh);
+      emit(net.fromrgb.name.c_str(), "", k.name, 2.0 * 4 * c0 * R * R, 0, (3.0 + 1.0 + (double)esz(yh) * c0) * R * R, k.fn, q,
+           grid1d((size_t)N * R * R * (c0 / 4) / 8), 0);
+      return;
+    }
     emit(net.fromrgb.name.c_str(), "", yh ? "migan::cm_fromrgb_h_kernel" : "migan::cm_fromrgb_kernel", 2.0 * 4 * c0 * R * R, 0,
          (4.0 * 4 + (double)esz(yh) * c0) * R * R, yh ? cm_fromrgb_h_kernel : cm_fromrgb_kernel, a,
          grid1d((size_t)N * R * R * (c0 / 4) / 8), 0);      // 8 pixels per thread: the weights are read once per thread
@@ -605,8 +621,9 @@ struct CmWalk {
   }
   // ToRGB of a synthesis block: xin ([res][res][c], fp16 if xh) and the running image prev -> out; weights, images and output are fp32
   // parts (staged walk): the un-added ToRGB output goes there as well, from the same launch
+  // bytes (uint8 mode, res == R): out is unused; the image is composed over the photo into out_u8 by the same launch
   void torgb(const CmRgbL& L, const float* xin, int res, const float* prev, float* out, bool xh = false, float* parts_out = nullptr,
-             bool with_parts = false) {
+             bool with_parts = false, bool bytes = false) {
     const int c = L.c, lpp = c <= 64 ? 4 : (c <= 128 ? 8 : 16);      // lanes per pixel
     static const struct { void (*fn)(const CmRgbArgs); const char* name; } kernels[2][3] = {
         {{cm_torgb_kernel<4>, "migan::cm_torgb_kernel<4>"}, {cm_torgb_kernel<8>, "migan::cm_torgb_kernel<8>"}, {cm_torgb_kernel<16>, "migan::cm_torgb_kernel<16>"}},
@@ -615,6 +632,16 @@ struct CmWalk {
     CmRgbArgs a{};
     a.x = xin; a.wm = job_ws[L.job].wm; a.bias = weight(L.b); a.img_prev = prev; a.img_out = out; a.B = B; a.H = res; a.W = res; a.C = c;
     const unsigned grid = (unsigned)(((size_t)B * res * res * lpp + kThreads - 1) / kThreads);
+    if (bytes) {
+      MIGAN_CHECK(!with_parts, MIGAN_EINVAL, "internal: the uint8 ToRGB keeps no un-added output");
+      const CmRgbU8Form ku = cm_torgb_u8_form(lpp, xh);
+      CmRgbU8Args au{};
+      au.r = a; au.r.img_out = nullptr; au.img = img_u8; au.mask = mask_u8; au.out = out_u8; au.S = S;
+      // the upsampled running image in (fp32), 3 + 1 bytes of photo and mask in, 3 bytes out
+      emit(L.name.c_str(), "", ku.name, 2.0 * 3 * c * res * res, 0, (double)esz(xh) * c * res * res + (4.0 * 0.75 + 3.0 + 1.0 + 3.0) * res * res,
+           ku.fn, au, grid, 0);
+      return;
+    }
     if (with_parts) {
       static const struct { void (*fn)(const CmRgbPartsArgs); const char* name; } parts_kernels[2][3] = {
           {{cm_torgb_parts_kernel<4>, "migan::cm_torgb_parts_kernel<4>"}, {cm_torgb_parts_kernel<8>, "migan::cm_torgb_parts_kernel<8>"},
@@ -882,9 +909,9 @@ struct CmWalk {
       conv(blk.conv1, "", CM_CONV_NORMAL, 0, x0, x1, res, res, res, res, nz1, false, bh, bh);
       // img = upsample2d(img) + torgb(x) (comodgan.py:334-343)
       const int lv = ilog2(res);
-      float* imo = (res == R) ? y : (h.debug ? alloc((size_t)3 * res * res * B * 4) : (img_ext[lv] ? img_ext[lv] : img[flip]));
+      float* imo = (res == R) ? (u8 ? nullptr : y) : (h.debug ? alloc((size_t)3 * res * res * B * 4) : (img_ext[lv] ? img_ext[lv] : img[flip]));
       if (res != R) reg_debug(blk.name.c_str(), ".img", imo, {B, 3, res, res});
-      torgb(blk.rgb, x1, res, imprev, imo, bh, rgb_ext[lv], (parts >> lv) & 1u);
+      torgb(blk.rgb, x1, res, imprev, imo, bh, rgb_ext[lv], (parts >> lv) & 1u, u8 && res == R);
       imprev = imo; flip ^= 1; xcur = x1; xcur_h = bh;
     }
   }
@@ -924,13 +951,13 @@ struct CmWalk {
 
 }  // namespace migan
 
-inline size_t comodgan_handle::ensure_planned(int batch, int samples, int stage, unsigned parts) const {
-  const migan::CmPlanKey key{batch, trunc_cutoff, debug, migan::cm_read_forced(), samples, fp16_enc, fp16_syn, fp16_storage, stage, parts};
+inline size_t comodgan_handle::ensure_planned(int batch, int samples, int stage, unsigned parts, bool u8) const {
+  const migan::CmPlanKey key{batch, trunc_cutoff, debug, migan::cm_read_forced(), samples, fp16_enc, fp16_syn, fp16_storage, stage, parts, u8};
   if (!(key == planned)) {
     comodgan_handle* m = const_cast<comodgan_handle*>(this);      // the queries of the C ABI take a const handle; the plan is a cache
     m->planned = migan::CmPlanKey{};                              // (nothing planned if the walk throws)
     migan::CmWalk walk(*m, batch, samples, key.forced, true);
-    walk.stage = stage; walk.parts = parts;
+    walk.stage = stage; walk.parts = parts; walk.u8 = u8;
     m->planned_need = walk.run(nullptr, nullptr);
     m->planned = key;
   }
@@ -1054,20 +1081,24 @@ static void comodgan_check_samples(int batch, int samples) {
   MIGAN_CHECK((long long)batch * samples <= (long long)INT_MAX, MIGAN_EINVAL, "batch * samples does not fit an int");
 }
 
+// u8 (include/comodgan_u8_hip.h): x is the photo, y the composited bytes, mask the mask; else mask is unused
 static int comodgan_forward_impl(comodgan_handle* h, const void* x, const void* z, void* y, int batch, int samples, float psi, int noise_mode,
-                                 const void* noise, void* ws, size_t ws_bytes, void* stream, float* ms, int n_ms) {
+                                 const void* noise, void* ws, size_t ws_bytes, void* stream, float* ms, int n_ms, bool u8 = false,
+                                 const void* mask = nullptr) {
   MIGAN_API_BEGIN
   using namespace migan;
   MIGAN_CHECK(h, MIGAN_EINVAL, "null handle");
   MIGAN_CHECK(h->committed, MIGAN_ESTATE, "comodgan_forward before comodgan_commit");
-  MIGAN_CHECK(x && z && y && batch > 0, MIGAN_EINVAL, "null tensor or empty batch");
+  MIGAN_CHECK(x && z && y && (mask || !u8) && batch > 0, MIGAN_EINVAL, "null tensor or empty batch");
   comodgan_check_samples(batch, samples);
   MIGAN_CHECK(noise_mode == COMODGAN_NOISE_NONE || noise_mode == COMODGAN_NOISE_CONST || noise_mode == COMODGAN_NOISE_RANDOM, MIGAN_EINVAL,
               "noise_mode must be none, const or random");
   MIGAN_CHECK(noise_mode != COMODGAN_NOISE_RANDOM || noise != nullptr, MIGAN_EINVAL, "noise_mode random needs the noise tensor");
   MIGAN_CHECK(ws != nullptr && ((uintptr_t)ws % 256) == 0, MIGAN_EINVAL, "null or misaligned workspace (256 bytes)");
-  MIGAN_CHECK(((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0 && ((uintptr_t)z % 4) == 0, MIGAN_EINVAL, "misaligned tensor");
-  const size_t need = h->ensure_planned(batch, samples);
+  // (the byte tensors of the uint8 mode are read and written a byte at a time: no alignment to check)
+  MIGAN_CHECK(u8 || (((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0), MIGAN_EINVAL, "misaligned tensor");
+  MIGAN_CHECK(((uintptr_t)z % 4) == 0, MIGAN_EINVAL, "misaligned tensor");
+  const size_t need = h->ensure_planned(batch, samples, CM_STAGE_FUSED, 0, u8);
   MIGAN_CHECK(ws_bytes >= need, MIGAN_EINVAL, "workspace too small for this batch");
   if (ms) {
     MIGAN_CHECK(n_ms >= (int)h->infos.size(), MIGAN_EINVAL, "launch_ms array too small");
@@ -1079,7 +1110,13 @@ static int comodgan_forward_impl(comodgan_handle* h, const void* x, const void* 
   }
   DeviceGuard guard(h->device);
   CmWalk walk(*h, batch, samples, h->planned.forced, false);      // the forced forms the plan was just checked against
-  walk.x = (const float*)x; walk.z = (const float*)z; walk.y = (float*)y; walk.noise = (const float*)noise;
+  if (u8) {
+    walk.u8 = true;
+    walk.img_u8 = (const unsigned char*)x; walk.mask_u8 = (const unsigned char*)mask; walk.out_u8 = (unsigned char*)y;
+  } else {
+    walk.x = (const float*)x; walk.y = (float*)y;
+  }
+  walk.z = (const float*)z; walk.noise = (const float*)noise;
   walk.psi = psi; walk.noise_mode = noise_mode; walk.stream = (rt::stream_t)stream;
   walk.run(ws, ms);
   MIGAN_API_END
@@ -1121,10 +1158,25 @@ int comodgan_forward_timed(comodgan_handle* h, const void* x, const void* z, voi
   return comodgan_forward_impl(h, x, z, y, batch, 1, psi, noise_mode, noise, ws, ws_bytes, stream, launch_ms, n_launch_ms);
 }
 
+// ---------------------------------------------------------------- include/comodgan_u8_hip.h
+int comodgan_forward_u8(comodgan_handle* h, const void* img, const void* mask, const void* z, void* out, int batch, int samples, float psi,
+                        int noise_mode, const void* noise, void* ws, size_t ws_bytes, void* stream) {
+  return comodgan_forward_impl(h, img, z, out, batch, samples, psi, noise_mode, noise, ws, ws_bytes, stream, nullptr, 0, true, mask);
+}
+
+int comodgan_forward_u8_timed(comodgan_handle* h, const void* img, const void* mask, const void* z, void* out, int batch, int samples, float psi,
+                              int noise_mode, const void* noise, void* ws, size_t ws_bytes, void* stream, float* launch_ms, int n_launch_ms) {
+  if (!launch_ms) {
+    migan::last_error_ref() = "null launch_ms";
+    return MIGAN_EINVAL;
+  }
+  return comodgan_forward_impl(h, img, z, out, batch, samples, psi, noise_mode, noise, ws, ws_bytes, stream, launch_ms, n_launch_ms, true, mask);
+}
+
 int comodgan_num_launches(const comodgan_handle* h, int* n) {
   MIGAN_API_BEGIN
   MIGAN_CHECK(h && n, MIGAN_EINVAL, "null argument");
-  h->ensure_planned(std::max(h->planned.batch, 1), h->planned.samples, h->planned.stage, h->planned.parts);      // the launches of the plan made last, in the forms forced now
+  h->ensure_planned(std::max(h->planned.batch, 1), h->planned.samples, h->planned.stage, h->planned.parts, h->planned.u8);      // the launches of the plan made last, in the forms forced now
   *n = (int)h->infos.size();
   MIGAN_API_END
 }
@@ -1133,7 +1185,7 @@ int comodgan_launch_info(const comodgan_handle* h, int index, const char** layer
                          double* bytes) {
   MIGAN_API_BEGIN
   MIGAN_CHECK(h, MIGAN_EINVAL, "null handle");
-  h->ensure_planned(std::max(h->planned.batch, 1), h->planned.samples, h->planned.stage, h->planned.parts);
+  h->ensure_planned(std::max(h->planned.batch, 1), h->planned.samples, h->planned.stage, h->planned.parts, h->planned.u8);
   MIGAN_CHECK(index >= 0 && index < (int)h->infos.size(), MIGAN_EINVAL, "launch index out of range");
   const migan::CmInfo& L = h->infos[index];
   if (layer) *layer = L.layer.c_str();

@@ -33,6 +33,9 @@
 //                       The first is the FIR body with SAMP set, the second shares cm_affine_job with cm_dense_multi_kernel
 //   cm_fromrgb_kernel   1x1 conv 4 -> C with bias and activation, NCHW planes -> NHWC
 //   cm_torgb_kernel     modulated 1x1 conv C -> 3 (no demodulation) + bias + 2x FIR upsample of the running image
+//   cm_fromrgb_u8_kernel, cm_torgb_u8_kernel   the first and the last launch of a uint8 forward (comodgan_forward_u8): the same two
+//                       bodies with migan_pack_input's arithmetic in front and migan_compose_output's behind, photo and mask bytes in,
+//                       composited bytes out
 //   cm_dense_kernel     fully connected layers (mapping, affine, encoder fc, synthesis fc): weight streaming, fp32 FMA
 //   cm_wprep_kernel     per-tensor statistics: max |w| per output channel (fp16 range scale), demodulation sums of w^2
 //   cm_style_multi_kernel  styles -> normalised input scales (with the per-sample power-of-two fp16 range scale) and
@@ -40,6 +43,8 @@
 //   cm_split_conv_kernel  3x3 weights -> two fp16 planes, [plane][tap][Cin/32][Cout][32]
 //
 // Compiled twice like migan_kernels.hpp: by hipcc for gfx950 and by the host compiler against tests/emu/hip_emu.h.
+// MIGAN_TEMPLATE_KERNELS_ONLY (as in migan_kernels.hpp): a unit that only instantiates kernel templates (comodgan_u8.hip) leaves out
+// the kernels that are no templates, which belong to migan_hip.hip.
 #pragma once
 
 namespace migan {
@@ -146,6 +151,7 @@ struct CmWprepArgs {
   float* wn2;          // [CO] or null
   int CO, CI;
 };
+#ifndef MIGAN_TEMPLATE_KERNELS_ONLY
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_wprep_kernel(const CmWprepArgs p) {
   MIGAN_DYN_SMEM(red);
   const int co = (int)blockIdx.x;
@@ -176,6 +182,7 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_wprep_kernel(const CmWprepArgs 
     p.amax[co] = fmaxf(fmaxf(red[4], red[5]), fmaxf(red[6], red[7]));
   }
 }
+#endif  // MIGAN_TEMPLATE_KERNELS_ONLY
 
 // 3x3 weights [CO][CI][3][3] fp32 -> two fp16 planes [plane][tap][CI/32][CO][32] of w * wscale, wscale = the power of
 // two that maps max|w| into [2^13, 2^14) (every workgroup derives it from amax[]; workgroup 0 also writes it to the
@@ -186,6 +193,7 @@ struct CmSplitArgs {
   unsigned short* dst;        // plane 0; a 16-byte header precedes it
   int CO, CI;
 };
+#ifndef MIGAN_TEMPLATE_KERNELS_ONLY
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_split_conv_kernel(const CmSplitArgs p) {
   MIGAN_DYN_SMEM(red);
   float m = 0.0f;
@@ -219,6 +227,7 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_split_conv_kernel(const CmSplit
     }
   }
 }
+#endif  // MIGAN_TEMPLATE_KERNELS_ONLY
 
 // ------------------------------------------------------------------------------------------------
 // styles [B][CI] (output of the affine dense layer) ->
@@ -307,11 +316,13 @@ struct CmStyleMultiArgs {
   int blk0[kCmMaxStyle + 1];     // first workgroup of each job
   int njobs;
 };
+#ifndef MIGAN_TEMPLATE_KERNELS_ONLY
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_style_multi_kernel(const CmStyleMultiArgs p) {
   int j = 0;
   while (j + 1 < p.njobs && (int)blockIdx.x >= p.blk0[j + 1]) ++j;
   cm_style_block(p.job[j], (int)blockIdx.x - p.blk0[j]);
 }
+#endif  // MIGAN_TEMPLATE_KERNELS_ONLY
 
 // ------------------------------------------------------------------------------------------------
 // dense (stylegan.py:64-99): y[n][o] = act((sum_k x[n][k] W[o][k]) * wgain + b[o] * bgain)
@@ -421,7 +432,9 @@ MIGAN_DEVICE MIGAN_INLINE void cm_dense_block(const CmDenseArgs& p, int block, i
   }
 }
 
+#ifndef MIGAN_TEMPLATE_KERNELS_ONLY
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_dense_kernel(const CmDenseArgs p) { cm_dense_block(p, (int)blockIdx.x); }
+#endif  // MIGAN_TEMPLATE_KERNELS_ONLY
 
 // All affine layers of the synthesis network in one launch (they depend only on the latent w and the global code w0,
 // stylegan.py:282): a table of (weight, bias, output, out_features); same input cat([w, w0]), no activation.
@@ -451,11 +464,13 @@ MIGAN_DEVICE MIGAN_INLINE int cm_affine_job(P p, CmDenseArgs& a, int* job = null
   a.wgain = p.wgain; a.bgain = 1.0f; a.psi = 1.0f; a.N = p.N; a.K = p.K; a.K1 = p.K1; a.O = p.O[j];
   return (int)blockIdx.x - p.blk0[j];
 }
+#ifndef MIGAN_TEMPLATE_KERNELS_ONLY
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_dense_multi_kernel(const CmDenseMultiArgs p) {
   CmDenseArgs a{};
   const int block = cm_affine_job<const CmDenseMultiArgs>(p, a);
   cm_dense_block(a, block);
 }
+#endif  // MIGAN_TEMPLATE_KERNELS_ONLY
 // The same launch of an S-samples forward (comodgan_forward_samples): N = images x S rows of x / x_alt (the latents, one per
 // sample, image-major) against the global code x2 of N / S images.  A symbol of its own, so that the launch above keeps its
 // arguments and its code.
@@ -463,11 +478,13 @@ struct CmDenseMultiSamplesArgs {
   CmDenseMultiArgs m;
   int S;
 };
+#ifndef MIGAN_TEMPLATE_KERNELS_ONLY
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_dense_multi_samples_kernel(const CmDenseMultiSamplesArgs q) {
   CmDenseArgs a{};
   const int block = cm_affine_job<const CmDenseMultiArgs&>(q.m, a);
   cm_dense_block<true>(a, block, q.S);
 }
+#endif  // MIGAN_TEMPLATE_KERNELS_ONLY
 // The same launch of the staged walk (comodgan_synthesize, include/comodgan_stages_hip.h): the latents are the caller's
 // ws [N][num_ws][w_dim], N = images x S rows; job j reads row widx[j] of each (comodgan.py:399-405), so the row stride of x is
 // num_ws * w_dim and whatever truncation the caller wants is already in the rows: no x_alt, alt_mask = 0.  x2 = w0 of N / S images.
@@ -476,6 +493,7 @@ struct CmDenseMultiRowsArgs {
   int widx[kCmMaxAffine];
   int S, num_ws;
 };
+#ifndef MIGAN_TEMPLATE_KERNELS_ONLY
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_dense_multi_rows_kernel(const CmDenseMultiRowsArgs q) {
   CmDenseArgs a{};
   int j = 0;
@@ -483,6 +501,7 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_dense_multi_rows_kernel(const C
   a.x += (size_t)q.widx[j] * q.m.K1;
   cm_dense_block<true, true>(a, block, q.S, q.num_ws * q.m.K1);
 }
+#endif  // MIGAN_TEMPLATE_KERNELS_ONLY
 
 // ws of the mapping stage (comodgan_mapping; stylegan.py:429-437): the mapping output w [B][D] repeated to [B][num_ws][D], rows
 // below `cutoff` from w (truncated towards w_avg by the last dense launch), the others from w_raw (the value before the lerp).
@@ -492,6 +511,7 @@ struct CmWsRowsArgs {
   float* ws;           // [B][num_ws][D]
   int B, num_ws, D, cutoff;      // D a multiple of 4
 };
+#ifndef MIGAN_TEMPLATE_KERNELS_ONLY
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_ws_rows_kernel(const CmWsRowsArgs p) {
   const int dq = p.D >> 2;
   const size_t total = (size_t)p.B * p.num_ws * dq;
@@ -504,6 +524,7 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_ws_rows_kernel(const CmWsRowsAr
     st4(p.ws + br * p.D + q * 4, ld4(src + b * p.D + q * 4));
   }
 }
+#endif  // MIGAN_TEMPLATE_KERNELS_ONLY
 
 // Head of synthesis.b4 of an S-samples forward: x4 = fc(w0) + feat[4] depends on the image only and is computed at batch N;
 // this copies it to the [N * S][4][4][C] tensor cm_conv_kernel reads (image-major: rows i * S ... i * S + S - 1 = image i).
@@ -513,6 +534,7 @@ struct CmBcastArgs {
   float* y;            // [N * S][M]
   int N, S, M;         // M: floats per image, a multiple of 4
 };
+#ifndef MIGAN_TEMPLATE_KERNELS_ONLY
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_bcast_kernel(const CmBcastArgs p) {
   const int mq = p.M >> 2;
   const size_t total = (size_t)p.N * p.S * mq;
@@ -522,6 +544,7 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_bcast_kernel(const CmBcastArgs 
     st4(p.y + (size_t)b * p.M + q * 4, ld4(p.x + (size_t)(b / p.S) * p.M + q * 4));
   }
 }
+#endif  // MIGAN_TEMPLATE_KERNELS_ONLY
 
 // ------------------------------------------------------------------------------------------------
 // conv2d_layer(4 -> C, kernel 1, bias, activation) of the first encoder block (comodgan.py:46-48, stylegan.py:231-244):
@@ -537,12 +560,32 @@ struct CmFromRgbArgs {
 // cm_fromrgb_h_kernel writes _Float16 (encoder block b<R> is half precision and fp16 storage is on; p.y is reinterpreted): values
 // are bounded by the +-256 clamp, rounded to nearest even, 8 bytes per channel quad.  One text, comodgan_fromrgb_body.inc, and a
 // symbol per output type, so that the fp32 launch keeps its name.
+#ifndef MIGAN_TEMPLATE_KERNELS_ONLY
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_fromrgb_kernel(const CmFromRgbArgs p) {
-  constexpr bool YH = false;
+  constexpr bool YH = false, U8 = false;
+  const unsigned char *const u8_img = nullptr, *const u8_mask = nullptr;
 #include "comodgan_fromrgb_body.inc"
 }
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_fromrgb_h_kernel(const CmFromRgbArgs p) {
-  constexpr bool YH = true;
+  constexpr bool YH = true, U8 = false;
+  const unsigned char *const u8_img = nullptr, *const u8_mask = nullptr;
+#include "comodgan_fromrgb_body.inc"
+}
+#endif  // MIGAN_TEMPLATE_KERNELS_ONLY
+// The FromRGB of a uint8 forward (comodgan_forward_u8, include/comodgan_u8_hip.h): the network input cat([mask - 0.5, img * mask])
+// (migan_pack_input, pack_pixel) is formed in registers from the photo [B][R][R][3] and the mask [B][R][R]; f.x is unused, no fp32
+// input tensor exists.  Symbols of their own, so that the launches above keep their arguments and their code, and templates: they are
+// instantiated by comodgan_u8.hip alone (cm_fromrgb_u8_form below).
+struct CmFromRgbU8Args {
+  CmFromRgbArgs f;             // x: null
+  const unsigned char* img;    // [B][R][R][3]
+  const unsigned char* mask;   // [B][R][R], 255 = known pixel
+};
+template <bool YH>
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_fromrgb_u8_kernel(const CmFromRgbU8Args q) {
+  constexpr bool U8 = true;
+  const CmFromRgbArgs& p = q.f;
+  const unsigned char *const u8_img = q.img, *const u8_mask = q.mask;
 #include "comodgan_fromrgb_body.inc"
 }
 
@@ -611,6 +654,7 @@ struct CmFirSamplesArgs {
   CmFirArgs f;                 // B = N * S; skip: [N]
   int S;
 };
+#ifndef MIGAN_TEMPLATE_KERNELS_ONLY
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_fir_samples_kernel(const CmFirSamplesArgs q) {
   constexpr int EPI = 1;
   constexpr bool SAMP = true, XH = false, YH = false, SH = false;
@@ -618,6 +662,7 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_fir_samples_kernel(const CmFirS
   const int S = q.S;
 #include "comodgan_fir_body.inc"
 }
+#endif  // MIGAN_TEMPLATE_KERNELS_ONLY
 // The typed twins (fp16 activation storage): XH / YH / SH say which of x, y and the skip tensor hold _Float16 (the pointers of
 // CmFirArgs are reinterpreted).  The skip tensor is the encoder's and typed by the encoder block's marking, x (the raw
 // transposed-convolution output) and y by the synthesis block's, so every combination but fp16 x with fp32 y occurs.  These reach
@@ -657,13 +702,19 @@ struct CmRgbArgs {
 // comodgan_torgb_body.inc, and a symbol family per feature-map type, so that the fp32 launches keep their names.
 template <int LPP>
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_torgb_kernel(const CmRgbArgs p) {
-  constexpr bool XH = false, PARTS = false;
+  constexpr bool XH = false, PARTS = false, U8 = false;
+  const unsigned char *const u8_img = nullptr, *const u8_mask = nullptr;
+  unsigned char* const u8_out = nullptr;
+  constexpr int u8_S = 1;
   float* const rgb_out = nullptr;
 #include "comodgan_torgb_body.inc"
 }
 template <int LPP>
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_torgb_h_kernel(const CmRgbArgs p) {
-  constexpr bool XH = true, PARTS = false;
+  constexpr bool XH = true, PARTS = false, U8 = false;
+  const unsigned char *const u8_img = nullptr, *const u8_mask = nullptr;
+  unsigned char* const u8_out = nullptr;
+  constexpr int u8_S = 1;
   float* const rgb_out = nullptr;
 #include "comodgan_torgb_body.inc"
 }
@@ -676,17 +727,67 @@ struct CmRgbPartsArgs {
 };
 template <int LPP>
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_torgb_parts_kernel(const CmRgbPartsArgs q) {
-  constexpr bool XH = false, PARTS = true;
+  constexpr bool XH = false, PARTS = true, U8 = false;
+  const unsigned char *const u8_img = nullptr, *const u8_mask = nullptr;
+  unsigned char* const u8_out = nullptr;
+  constexpr int u8_S = 1;
   const CmRgbArgs& p = q.r;
   float* const rgb_out = q.rgb_out;
 #include "comodgan_torgb_body.inc"
 }
 template <int LPP>
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_torgb_parts_h_kernel(const CmRgbPartsArgs q) {
-  constexpr bool XH = true, PARTS = true;
+  constexpr bool XH = true, PARTS = true, U8 = false;
+  const unsigned char *const u8_img = nullptr, *const u8_mask = nullptr;
+  unsigned char* const u8_out = nullptr;
+  constexpr int u8_S = 1;
   const CmRgbArgs& p = q.r;
   float* const rgb_out = q.rgb_out;
 #include "comodgan_torgb_body.inc"
 }
+
+// The last ToRGB (res == R) of a uint8 forward (comodgan_forward_u8, include/comodgan_u8_hip.h): the same reduction and upsampled
+// running image, then migan_compose_output's arithmetic (compose_pixel) instead of the fp32 store -- row b of the B = N * S rows is
+// composed over photo b / S and written as HWC bytes; r.img_out is unused, no fp32 output tensor exists.  S is an argument: one
+// family serves S = 1 and S > 1.  Symbols of their own again; XH: the feature map holds _Float16.
+struct CmRgbU8Args {
+  CmRgbArgs r;                 // img_out: null
+  const unsigned char* img;    // [B / S][H][W][3]
+  const unsigned char* mask;   // [B / S][H][W], 255 = known pixel
+  unsigned char* out;          // [B][H][W][3]
+  int S;
+};
+template <int LPP, bool XH>
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) cm_torgb_u8_kernel(const CmRgbU8Args q) {
+  constexpr bool PARTS = false, U8 = true;
+  const CmRgbArgs& p = q.r;
+  float* const rgb_out = nullptr;
+  const unsigned char *const u8_img = q.img, *const u8_mask = q.mask;
+  unsigned char* const u8_out = q.out;
+  const int u8_S = q.S;
+#include "comodgan_torgb_body.inc"
+}
+
+// The uint8 kernels by form, for the host walk.  Their instantiations live in a translation unit of their own, comodgan_u8.hip:
+// compiled into the unit that holds pack_input_kernel, a second user of unit_image() changes that kernel's code (the optimiser's
+// result for one function depends on what else the module holds), and every symbol the library had keeps its code.  The unit that
+// holds the host walk declares them (MIGAN_CM_U8_ELSEWHERE); the CPU test harness, a single unit, defines them here.
+struct CmFromRgbU8Form { void (*fn)(const CmFromRgbU8Args); const char* name; };
+struct CmRgbU8Form { void (*fn)(const CmRgbU8Args); const char* name; };
+CmFromRgbU8Form cm_fromrgb_u8_form(bool yh);
+CmRgbU8Form cm_torgb_u8_form(int lpp, bool xh);       // lpp: 4, 8 or 16
+#ifndef MIGAN_CM_U8_ELSEWHERE
+CmFromRgbU8Form cm_fromrgb_u8_form(bool yh) {
+  if (yh) return {cm_fromrgb_u8_kernel<true>, "migan::cm_fromrgb_u8_kernel<true>"};
+  return {cm_fromrgb_u8_kernel<false>, "migan::cm_fromrgb_u8_kernel<false>"};
+}
+CmRgbU8Form cm_torgb_u8_form(int lpp, bool xh) {
+#define CM_TORGB_U8_FORM(LPP, XH) {cm_torgb_u8_kernel<LPP, XH>, "migan::cm_torgb_u8_kernel<" #LPP ", " #XH ">"}
+  static const CmRgbU8Form forms[2][3] = {{CM_TORGB_U8_FORM(4, false), CM_TORGB_U8_FORM(8, false), CM_TORGB_U8_FORM(16, false)},
+                                          {CM_TORGB_U8_FORM(4, true), CM_TORGB_U8_FORM(8, true), CM_TORGB_U8_FORM(16, true)}};
+#undef CM_TORGB_U8_FORM
+  return forms[xh][lpp / 8];
+}
+#endif  // MIGAN_CM_U8_ELSEWHERE
 
 }  // namespace migan

@@ -1,6 +1,7 @@
-// Body of cm_torgb_kernel<LPP>, cm_torgb_h_kernel<LPP> and their _parts twins (comodgan_kernels.hpp), included into each like
-// comodgan_fir_body.inc.  The enclosing kernel supplies p (its CmRgbArgs), LPP, XH: the feature map p.x holds _Float16, and
-// PARTS: torgb(x) before the running image is added goes to rgb_out as well.
+// Body of cm_torgb_kernel<LPP>, cm_torgb_h_kernel<LPP>, their _parts twins and their _u8 twins (comodgan_kernels.hpp), included into
+// each like comodgan_fir_body.inc.  The enclosing kernel supplies p (its CmRgbArgs), LPP, XH: the feature map p.x holds _Float16,
+// PARTS: torgb(x) before the running image is added goes to rgb_out as well, and U8 with u8_img / u8_mask / u8_out / u8_S: the
+// image is not stored to p.img_out but composed over the caller's photo (compose_pixel) into HWC bytes, row b against photo b / u8_S.
   static_assert(LPP == 4 || LPP == 8 || LPP == 16, "lanes per pixel");
   const int sub = threadIdx.x & (LPP - 1);
   const size_t pixel = ((size_t)blockIdx.x * 256 + threadIdx.x) / LPP;
@@ -9,6 +10,16 @@
   const bool ok = pixel < npix;
   float r0 = 0.f, r1 = 0.f, r2 = 0.f;
   const int b = ok ? (int)(pixel / plane) : 0;
+  // U8: lane ch of the group requests byte ch of the photo's pixel and its mask byte ahead of the channel walk; nothing uses them
+  // before the store
+  unsigned u8_px = 0u, u8_mk = 0u;
+  if constexpr (U8) {
+    if (ok && sub < 3) {
+      const size_t src = (size_t)(b / u8_S) * plane + pixel % plane;
+      u8_px = u8_img[src * 3 + sub];
+      u8_mk = u8_mask[src];
+    }
+  }
   if (ok) {
     // the pixel's channels, fp16 or fp32, each in the element arithmetic its symbol has always had: unified they are the same
     // addresses and other code (profiles/comodgan_stream_bodies.md)
@@ -38,7 +49,10 @@
     const float sum = sub == 0 ? r0 : (sub == 1 ? r1 : r2);
     float up = 0.0f;
     if (p.img_prev) up = up_prev3(p.img_prev + ((size_t)b * 3 + sub) * (plane >> 2), p.H >> 1, p.W >> 1, oy, ox);
-    if (PARTS) {
+    if constexpr (U8) {
+      // compose_pixel's arithmetic on one channel: a known pixel keeps the photo's byte
+      u8_out[pixel * 3 + sub] = u8_mk == 255u ? (unsigned char)u8_px : unit_to_u8(up + (sum + p.bias[sub]));
+    } else if (PARTS) {
       // both stores behind every load: a load issued after a store waits for it (vmcnt retires in order)
       const float rgb = sum + p.bias[sub];
       rgb_out[((size_t)b * 3 + sub) * plane + rem] = rgb;

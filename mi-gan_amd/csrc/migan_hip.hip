@@ -5,6 +5,7 @@
 #include "migan_table.hpp"
 #include "migan_pipe.hpp"
 #include "migan_wide2.hpp"
+#define MIGAN_CM_U8_ELSEWHERE     // the uint8 Co-Mod-GAN kernels are comodgan_u8.hip's
 #include "comodgan_kernels.hpp"
 #include "migan_host.hpp"
 #include "comodgan_host.hpp"

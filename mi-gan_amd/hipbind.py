@@ -90,6 +90,8 @@ FP16_STORAGE_EXPORTS = ("comodgan_set_fp16_storage", "comodgan_get_fp16_storage"
 # include/comodgan_stages_hip.h
 STAGES_EXPORTS = ("comodgan_stages_workspace_bytes", "comodgan_mapping", "comodgan_encode", "comodgan_synthesize",
                   "comodgan_weight_preparations")
+# include/comodgan_u8_hip.h
+U8_EXPORTS = ("comodgan_forward_u8", "comodgan_forward_u8_timed")
 COMODGAN_DTYPE_F32, COMODGAN_DTYPE_F16 = 0, 2
 
 
@@ -152,7 +154,7 @@ class MiganLib:
         except OSError as e:  # pragma: no cover - depends on the machine
             raise MiganError(f"cannot load {self.path}: {e}") from e
         L = self.lib
-        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + PIPELINE_PATCHES_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS:
+        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + PIPELINE_PATCHES_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS + U8_EXPORTS:
             if not hasattr(L, name):
                 raise MiganError(f"{self.path} does not export {name}")
         vp, ci = C.c_void_p, C.c_int
@@ -228,6 +230,8 @@ class MiganLib:
         L.comodgan_encode.argtypes = [vp, vp, vp, C.POINTER(vp), ci, vp, C.c_size_t, vp]
         L.comodgan_synthesize.argtypes = [vp, vp, C.POINTER(vp), vp, vp, ci, ci, ci, vp, C.POINTER(vp), C.POINTER(vp), vp, C.c_size_t, vp]
         L.comodgan_weight_preparations.argtypes = [vp, C.POINTER(C.c_ulonglong)]
+        L.comodgan_forward_u8.argtypes = [vp, vp, vp, vp, vp, ci, ci, C.c_float, ci, vp, vp, C.c_size_t, vp]
+        L.comodgan_forward_u8_timed.argtypes = [vp, vp, vp, vp, vp, ci, ci, C.c_float, ci, vp, vp, C.c_size_t, vp, fp, ci]
         L.migan_last_error.restype = C.c_char_p
         L.migan_last_kernel.restype = C.c_char_p
         L.migan_nan_policy.restype = C.c_char_p
@@ -238,7 +242,7 @@ class MiganLib:
         if not allow_test_backend and L.migan_backend().decode() != PRODUCT_BACKEND:
             raise MiganError(f"{self.path} reports backend {L.migan_backend().decode()!r}, not {PRODUCT_BACKEND!r}: only the gfx950 HIP "
                              f"library is a product backend (the CPU emulator build is test infrastructure)")
-        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + PIPELINE_PATCHES_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS:
+        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + PIPELINE_PATCHES_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS + U8_EXPORTS:
             if name not in ("migan_last_error", "migan_last_kernel", "migan_nan_policy", "migan_backend", "migan_gemm_variant", "migan_tuning_key"):
                 getattr(L, name).restype = ci
 
@@ -592,6 +596,25 @@ class CoModGANHandle:
         n = len(self.launches())
         ms = (C.c_float * n)()
         self.lib.check(self.lib.lib.comodgan_forward_samples_timed(*args, ms, n))
+        return [float(v) for v in ms]
+
+    def forward_u8(self, img_ptr: int, mask_ptr: int, z_ptr: int, out_ptr: int, batch: int, samples: int, ws_ptr: int, ws_bytes: int,
+                   truncation_psi: float = 1.0, noise_mode: str = "const", noise_ptr: Optional[int] = None, stream: int = 0,
+                   timed: bool = False):
+        """include/comodgan_u8_hip.h: uint8 img [batch,R,R,3] and mask [batch,R,R] (255 = known), z [batch*samples,z_dim] -> uint8
+        out [batch*samples,R,R,3], row i * samples + s composed over photo i; a workspace of workspace_bytes_samples(batch, samples)"""
+        if noise_mode not in NOISE_MODES:
+            raise AssertionError(noise_mode)             # stylegan.py:280
+        args = [self._h, C.c_void_p(img_ptr), C.c_void_p(mask_ptr), C.c_void_p(z_ptr), C.c_void_p(out_ptr), int(batch), int(samples),
+                C.c_float(truncation_psi), NOISE_MODES[noise_mode], C.c_void_p(noise_ptr), C.c_void_p(ws_ptr), C.c_size_t(ws_bytes),
+                C.c_void_p(stream)]
+        if not timed:
+            self.lib.check(self.lib.lib.comodgan_forward_u8(*args))
+            return None
+        self.workspace_bytes_samples(batch, samples)     # the uint8 plan has the launches of the fp32-I/O plan, two of them under other names
+        n = len(self.launches())
+        ms = (C.c_float * n)()
+        self.lib.check(self.lib.lib.comodgan_forward_u8_timed(*args, ms, n))
         return [float(v) for v in ms]
 
     # -- include/comodgan_stages_hip.h: the three stages as calls of their own, stage tensors in caller memory
