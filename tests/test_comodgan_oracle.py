@@ -80,3 +80,41 @@ def test_float64_oracle_bounds_fp32_rounding():
     y32 = orc.generator(x, z, sd, cfg.resolution, cfg.num_ws)
     y64 = orc.generator(x, z, sd, cfg.resolution, cfg.num_ws, dtype=torch.float64)
     assert np.abs(y32 - y64).max() <= 1e-4 * np.abs(y64).max()
+
+
+@pytest.mark.parametrize("up,down", [(1, 1), (2, 1), (1, 2)])
+def test_factored_convolutions_equal_the_reference_pinned_ones(up, down):
+    """conv2d_factored / modulated_conv2d_factored (the arithmetic as the product's kernels arrange it: scaled activations, range
+    scaled weights, one coefficient per output channel) with operand_dtype=None are conv2d_layer / modulated_conv2d reassociated:
+    equal to float64 rounding.  With fp16 operands they differ by the operand rounding, 2^-11 relative per operand."""
+    f64 = torch.float64
+    g = torch.Generator().manual_seed(5)
+    n, ci, co, r = 3, 32, 64, 10
+    x = torch.randn(n, ci, r, r, generator=g, dtype=f64) * 3
+    w = torch.randn(co, ci, 3, 3, generator=g, dtype=f64) * 0.7
+    styles = torch.randn(n, ci, generator=g, dtype=f64) * 2 + 1
+    f = orc.fir(f64)
+    # plain layer (encoder): against conv2d_layer without activation, bias zero
+    sd = {"l.weight": w, "l.bias": torch.zeros(co, dtype=f64)}
+    if up == 1:
+        want = orc.conv2d_layer(x, sd, "l", down=down, activation=False)
+        xin = orc.upfirdn_pad(x, f, (2, 2, 2, 2)) if down == 2 else x
+        got = orc.conv2d_factored(xin, w, down=down)
+        assert float((got - want).abs().max()) <= 1e-13 * float(want.abs().max())
+        got16 = orc.conv2d_factored(xin, w, down=down, operand_dtype=torch.float16)
+        d = float((got16 - want).abs().max()) / float(want.abs().max())
+        assert 1e-6 < d < 2 ** -10
+    if down == 1:
+        want = orc.modulated_conv2d(x, w, styles, None, up, 1, True)
+        got = orc.modulated_conv2d_factored(x, w, styles, up=up)
+        if up == 2:
+            got = orc.upfirdn_pad(got, f, (1, 1, 1, 1), gain=4.0)
+        assert float((got - want).abs().max()) <= 1e-13 * float(want.abs().max())
+        got16 = orc.modulated_conv2d_factored(x, w, styles, up=up, operand_dtype=torch.float16)
+        if up == 2:
+            got16 = orc.upfirdn_pad(got16, f, (1, 1, 1, 1), gain=4.0)
+        d = float((got16 - want).abs().max()) / float(want.abs().max())
+        assert 1e-6 < d < 2 ** -10
+        # the operands stay inside fp16: |x * sa| < 2^15 for |x| <= 512, max |w * sw| in [2^13, 2^14)
+        sa, sw, _ = orc.modulated_factors(w, styles, torch.float16)
+        assert float(sa.abs().max()) * 512 <= 2 ** 15 and 2 ** 13 <= float(w.abs().max() * sw) < 2 ** 14
