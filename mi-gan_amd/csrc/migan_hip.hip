@@ -7,5 +7,6 @@
 #include "migan_wide2.hpp"
 #define MIGAN_CM_U8_ELSEWHERE     // the uint8 Co-Mod-GAN kernels are comodgan_u8.hip's
 #include "comodgan_kernels.hpp"
+#define MIGAN_METRICS_ELSEWHERE   // the PSNR / SSIM kernels are migan_metrics.hip's
 #include "migan_host.hpp"
 #include "comodgan_host.hpp"

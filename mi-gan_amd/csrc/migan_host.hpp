@@ -21,7 +21,9 @@
 #include "../../include/migan_hip.h"
 #include "../../include/migan_pipeline_samples_hip.h"
 #include "../../include/migan_pipeline_patches_hip.h"
+#include "../../include/migan_metrics_hip.h"
 #include "migan_table.hpp"
+#include "migan_metrics.hpp"
 
 namespace migan {
 
@@ -2199,5 +2201,96 @@ const char* migan_gemm_variant(void) {
   return g == 2 ? "f16x2" : (g == 1 ? "bf16x3" : "f32");
 }
 int migan_version(void) { return 2; }
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// include/migan_metrics_hip.h: PSNR / SSIM of completions against the photo (kernels: migan_metrics.hpp)
+namespace migan {
+struct MetLaunch {
+  int i0, k;                         // items [i0, i0 + k)
+  unsigned long long tiles;
+};
+// The launches of a batch (kMetItemsMax items and fewer than 2^31 workgroups each) and the scratch the largest of them needs: per
+// tile S * 3 partial pairs and one pair of counts.  Launches follow each other on one stream, so they share the scratch.  One
+// statement for _scratch_bytes and _batch; it also checks the sizes.
+static size_t metrics_plan(const migan_metrics_item* items, int n, int samples, std::vector<MetLaunch>* out) {
+  MIGAN_CHECK(items != nullptr && n >= 1, MIGAN_EINVAL, "the batch needs at least one item");
+  MIGAN_CHECK(samples >= 1 && samples <= (1 << 24), MIGAN_EINVAL, "samples must be at least 1 (and at most 2^24)");
+  size_t bytes = 0;
+  for (int i0 = 0; i0 < n;) {
+    unsigned long long total = 0;
+    int k = 0;
+    for (; k < kMetItemsMax && i0 + k < n; ++k) {
+      const migan_metrics_item& it = items[i0 + k];
+      MIGAN_CHECK(it.H >= 1 && it.W >= 1, MIGAN_EINVAL, "item " + std::to_string(i0 + k) + ": empty image");
+      const unsigned long long t = (unsigned long long)cdiv(it.W, kMetTW) * (unsigned long long)cdiv(it.H, kMetTH);
+      MIGAN_CHECK(t <= 0x7fffffffull, MIGAN_EINVAL, "item " + std::to_string(i0 + k) + ": image too large");
+      if (k > 0 && total + t > 0x7fffffffull) break;
+      total += t;
+    }
+    if (out) out->push_back(MetLaunch{i0, k, total});
+    bytes = std::max(bytes, align256((size_t)total * samples * 3 * sizeof(MetPart<true>)) + align256((size_t)total * 2 * sizeof(unsigned)));
+    i0 += k;
+  }
+  return bytes;
+}
+}  // namespace migan
+
+extern "C" {
+
+size_t migan_metrics_scratch_bytes(const migan_metrics_item* items, int n, int samples) {
+  try {
+    return migan::metrics_plan(items, n, samples, nullptr);
+  } catch (const std::exception& e) {
+    migan::last_error_ref() = e.what();
+    return 0;
+  }
+}
+
+int migan_metrics_batch(const migan_metrics_item* items, int n, int samples, int dtype, int layout, int shave, float lo, float hi,
+                        void* scratch, double* out_mse, double* out_ssim, void* stream) {
+  MIGAN_API_BEGIN
+  using namespace migan;
+  MIGAN_CHECK(dtype == MIGAN_METRICS_U8 || dtype == MIGAN_METRICS_F32, MIGAN_EINVAL, "dtype must be MIGAN_METRICS_U8 or MIGAN_METRICS_F32");
+  MIGAN_CHECK(layout == MIGAN_METRICS_CHW || layout == MIGAN_METRICS_HWC, MIGAN_EINVAL, "layout must be MIGAN_METRICS_CHW or MIGAN_METRICS_HWC");
+  MIGAN_CHECK(shave >= 0, MIGAN_EINVAL, "shave must not be negative");
+  const float span = hi - lo;
+  MIGAN_CHECK(std::isfinite(lo) && std::isfinite(hi) && std::isfinite(span) && hi != lo, MIGAN_EINVAL,
+              "the value range needs two different finite ends");
+  MIGAN_CHECK(scratch && out_mse && out_ssim, MIGAN_EINVAL, "null scratch or output");
+  std::vector<MetLaunch> launches;
+  metrics_plan(items, n, samples, &launches);
+  for (int i = 0; i < n; ++i) {
+    const migan_metrics_item& it = items[i];
+    MIGAN_CHECK(it.gt && it.pred, MIGAN_EINVAL, "null gt or pred in item " + std::to_string(i));
+    MIGAN_CHECK(dtype != MIGAN_METRICS_F32 || ((uintptr_t)it.gt % 4 == 0 && (uintptr_t)it.pred % 4 == 0), MIGAN_EINVAL,
+                "item " + std::to_string(i) + ": float32 data must be 4-byte aligned");
+    MIGAN_CHECK((long long)it.H - 2ll * shave >= 1 && (long long)it.W - 2ll * shave >= 1, MIGAN_EINVAL,
+                "item " + std::to_string(i) + ": nothing of " + std::to_string(it.H) + " x " + std::to_string(it.W) + " is left after shaving " +
+                    std::to_string(shave) + " from every side");
+  }
+  const MetForm form = metrics_form(dtype == MIGAN_METRICS_U8);
+  for (const MetLaunch& l : launches) {
+    MetArgs a{};
+    unsigned long long total = 0;
+    for (int k = 0; k < l.k; ++k) {
+      const migan_metrics_item& it = items[l.i0 + k];
+      a.item[k] = MetItem{it.gt, it.pred, it.mask, it.H, it.W};
+      a.first[k] = (int)total;
+      total += (unsigned long long)cdiv(it.W, kMetTW) * (unsigned long long)cdiv(it.H, kMetTH);
+    }
+    a.first[l.k] = (int)total;
+    a.part = scratch;
+    a.cnt = (unsigned*)((char*)scratch + align256((size_t)total * samples * 3 * sizeof(MetPart<true>)));
+    a.out_mse = out_mse + (size_t)l.i0 * samples;
+    a.out_ssim = out_ssim + (size_t)l.i0 * samples;
+    a.n = l.k; a.S = samples; a.shave = shave; a.hwc = layout == MIGAN_METRICS_HWC;
+    a.lo = lo; a.span = span;
+    rt_check(rt::launch(form.tile, a, (unsigned)total, kMetThreads, (size_t)kMetLdsBytes, (rt::stream_t)stream), form.tile_name);
+    rt_check(rt::launch(form.final, a, (unsigned)(l.k * samples), kMetThreads, (size_t)kMetFinalLdsBytes, (rt::stream_t)stream), form.final_name);
+  }
+  MIGAN_API_END
+}
 
 }  // extern "C"

@@ -93,6 +93,26 @@ STAGES_EXPORTS = ("comodgan_stages_workspace_bytes", "comodgan_mapping", "comodg
 # include/comodgan_u8_hip.h
 U8_EXPORTS = ("comodgan_forward_u8", "comodgan_forward_u8_timed")
 COMODGAN_DTYPE_F32, COMODGAN_DTYPE_F16 = 0, 2
+# include/migan_metrics_hip.h
+METRICS_EXPORTS = ("migan_metrics_scratch_bytes", "migan_metrics_batch")
+METRICS_U8, METRICS_F32 = 0, 1
+METRICS_CHW, METRICS_HWC = 0, 1
+
+
+class MetricsItem(C.Structure):
+    """struct migan_metrics_item"""
+    _fields_ = [("gt", C.c_void_p), ("pred", C.c_void_p), ("mask", C.c_void_p), ("H", C.c_int), ("W", C.c_int)]
+
+
+def metrics_items(items):
+    """[(gt_ptr, pred_ptr, mask_ptr or None, H, W), ...] -> a migan_metrics_item array (None passes a null table through)"""
+    if items is None:
+        return None
+    arr = (MetricsItem * max(1, len(items)))()
+    for a, (gt, pred, mask, h, w) in zip(arr, items):
+        a.gt, a.pred, a.mask = gt or None, pred or None, mask or None
+        a.H, a.W = int(h), int(w)
+    return arr
 
 
 class PipelineItem(C.Structure):
@@ -154,7 +174,8 @@ class MiganLib:
         except OSError as e:  # pragma: no cover - depends on the machine
             raise MiganError(f"cannot load {self.path}: {e}") from e
         L = self.lib
-        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + PIPELINE_PATCHES_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS + U8_EXPORTS:
+        for name in (EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + PIPELINE_PATCHES_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS
+                     + U8_EXPORTS + METRICS_EXPORTS):
             if not hasattr(L, name):
                 raise MiganError(f"{self.path} does not export {name}")
         vp, ci = C.c_void_p, C.c_int
@@ -232,6 +253,10 @@ class MiganLib:
         L.comodgan_weight_preparations.argtypes = [vp, C.POINTER(C.c_ulonglong)]
         L.comodgan_forward_u8.argtypes = [vp, vp, vp, vp, vp, ci, ci, C.c_float, ci, vp, vp, C.c_size_t, vp]
         L.comodgan_forward_u8_timed.argtypes = [vp, vp, vp, vp, vp, ci, ci, C.c_float, ci, vp, vp, C.c_size_t, vp, fp, ci]
+        L.migan_metrics_scratch_bytes.argtypes = [C.POINTER(MetricsItem), ci, ci]
+        L.migan_metrics_scratch_bytes.restype = C.c_size_t
+        L.migan_metrics_batch.argtypes = [C.POINTER(MetricsItem), ci, ci, ci, ci, ci, C.c_float, C.c_float, vp, vp, vp, vp]
+        L.migan_metrics_batch.restype = ci
         L.migan_last_error.restype = C.c_char_p
         L.migan_last_kernel.restype = C.c_char_p
         L.migan_nan_policy.restype = C.c_char_p
@@ -367,6 +392,20 @@ class MiganLib:
         self.check(self.lib.migan_pipeline_batch_post_patches(pipeline_items(items), len(items), int(samples), int(resolution),
                                                               C.c_void_p(y_ptr), C.c_void_p(bbox_ptr), g, C.c_void_p(scratch_ptr), outs, caps,
                                                               C.c_void_p(stream)))
+
+    # PSNR / SSIM of completions against the photo (include/migan_metrics_hip.h): `items` = [(gt_ptr, pred_ptr, mask_ptr or None, H, W), ...]
+    def metrics_scratch_bytes(self, items, samples: int) -> int:
+        n = self.lib.migan_metrics_scratch_bytes(metrics_items(items), 0 if items is None else len(items), int(samples))
+        if n == 0:
+            raise ValueError((self.lib.migan_last_error() or b"").decode())
+        return int(n)
+
+    def metrics_batch(self, items, samples: int, dtype: int, layout: int, shave: int, lo: float, hi: float, scratch_ptr: int,
+                      out_mse_ptr: int, out_ssim_ptr: int, stream: int = 0) -> None:
+        """out_mse / out_ssim: device float64 [len(items) * samples], row i * samples + s = sample s of item i"""
+        self.check(self.lib.migan_metrics_batch(metrics_items(items), 0 if items is None else len(items), int(samples), int(dtype), int(layout),
+                                                int(shave), C.c_float(lo), C.c_float(hi), C.c_void_p(scratch_ptr), C.c_void_p(out_mse_ptr),
+                                                C.c_void_p(out_ssim_ptr), C.c_void_p(stream)))
 
     def sepconv_forward(self, stream: int = 0, **kw) -> None:
         d = SepConvDesc()
