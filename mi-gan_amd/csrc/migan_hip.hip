@@ -8,5 +8,6 @@
 #define MIGAN_CM_U8_ELSEWHERE     // the uint8 Co-Mod-GAN kernels are comodgan_u8.hip's
 #include "comodgan_kernels.hpp"
 #define MIGAN_METRICS_ELSEWHERE   // the PSNR / SSIM kernels are migan_metrics.hip's
+#define MIGAN_PHOTO_ELSEWHERE     // the photo-loading kernels are migan_photo.hip's
 #include "migan_host.hpp"
 #include "comodgan_host.hpp"

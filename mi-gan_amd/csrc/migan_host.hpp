@@ -22,8 +22,10 @@
 #include "../../include/migan_pipeline_samples_hip.h"
 #include "../../include/migan_pipeline_patches_hip.h"
 #include "../../include/migan_metrics_hip.h"
+#include "../../include/migan_photo_hip.h"
 #include "migan_table.hpp"
 #include "migan_metrics.hpp"
+#include "migan_photo.hpp"
 
 namespace migan {
 
@@ -2289,6 +2291,132 @@ int migan_metrics_batch(const migan_metrics_item* items, int n, int samples, int
     a.lo = lo; a.span = span;
     rt_check(rt::launch(form.tile, a, (unsigned)total, kMetThreads, (size_t)kMetLdsBytes, (rt::stream_t)stream), form.tile_name);
     rt_check(rt::launch(form.final, a, (unsigned)(l.k * samples), kMetThreads, (size_t)kMetFinalLdsBytes, (rt::stream_t)stream), form.final_name);
+  }
+  MIGAN_API_END
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// include/migan_photo_hip.h: Pillow-exact BICUBIC / NEAREST resize of uint8 images (kernels: migan_photo.hpp)
+namespace migan {
+// One chunk of up to kPhItemsMax items laid out in scratch: the int32 tables first, then (256-byte aligned) the uint8 intermediates
+// of the items that need both passes.
+struct PhChunk {
+  PhItem item[kPhItemsMax];          // sizes, table offsets, ksizes; src / dst unset
+  size_t mid[kPhItemsMax];           // byte offset of the item's [sh][dw][C] intermediate behind the tables, or SIZE_MAX
+  int k = 0;
+  size_t tab_bytes = 0, bytes = 0;
+};
+inline int photo_ksize(int inS, int outS) {
+  const double scale = (double)inS / (double)outS;
+  const double support = 2.0 * (scale < 1.0 ? 1.0 : scale);
+  return (int)std::ceil(support) * 2 + 1;
+}
+// items [i0, i0 + k) of the batch; checks the domain.  One statement for _scratch_bytes and _resize_batch.
+static PhChunk photo_chunk(const migan_photo_item* items, int i0, int k, int channels, int filter) {
+  PhChunk c;
+  c.k = k;
+  size_t ints = 0, mid = 0;
+  for (int j = 0; j < k; ++j) {
+    const migan_photo_item& s = items[i0 + j];
+    const std::string who = "item " + std::to_string(i0 + j) + ": ";
+    MIGAN_CHECK(s.src_height >= 1 && s.src_height <= kPhSrcMax && s.src_width >= 1 && s.src_width <= kPhSrcMax, MIGAN_EINVAL,
+                who + "source sides must be in 1 .. " + std::to_string(kPhSrcMax));
+    MIGAN_CHECK(s.dst_height >= 1 && s.dst_height <= kPhDstMax && s.dst_width >= 1 && s.dst_width <= kPhDstMax, MIGAN_EINVAL,
+                who + "destination sides must be in 1 .. " + std::to_string(kPhDstMax));
+    MIGAN_CHECK(std::max(s.src_height, s.src_width) <= kPhAspectMax * std::min(s.src_height, s.src_width), MIGAN_EINVAL,
+                who + "source aspect ratio above " + std::to_string(kPhAspectMax) + " : 1 (Pillow resamples such an image in another order)");
+    PhItem& it = c.item[j];
+    it = PhItem{nullptr, nullptr, s.src_height, s.src_width, s.dst_height, s.dst_width, 0, 0, 0, 0};
+    const bool same = it.sh == it.dh && it.sw == it.dw;
+    if (filter == MIGAN_PHOTO_NEAREST || same) {
+      it.ks_h = it.ks_v = -1;                            // index tables (the identity for a BICUBIC copy)
+      it.tab_h = (unsigned)ints; ints += (size_t)it.dw;
+      it.tab_v = (unsigned)ints; ints += (size_t)it.dh;
+      c.mid[j] = SIZE_MAX;
+    } else {
+      if (it.sw != it.dw) { it.ks_h = photo_ksize(it.sw, it.dw); it.tab_h = (unsigned)ints; ints += (size_t)(2 + it.ks_h) * it.dw; }
+      if (it.sh != it.dh) { it.ks_v = photo_ksize(it.sh, it.dh); it.tab_v = (unsigned)ints; ints += (size_t)(2 + it.ks_v) * it.dh; }
+      c.mid[j] = SIZE_MAX;
+      if (it.ks_h > 0 && it.ks_v > 0) { c.mid[j] = mid; mid += align256((size_t)it.sh * it.dw * channels); }
+    }
+  }
+  c.tab_bytes = align256(ints * sizeof(int));            // (at most 32 * 2 * (4 * 16384 + 5 * 4096) ints: far below 2^32)
+  c.bytes = c.tab_bytes + mid;
+  return c;
+}
+static void photo_check_common(const migan_photo_item* items, int n, int channels, int filter) {
+  MIGAN_CHECK(items != nullptr && n >= 1, MIGAN_EINVAL, "the batch needs at least one item");
+  MIGAN_CHECK(channels == 1 || channels == 3, MIGAN_EINVAL, "channels must be 1 or 3");
+  MIGAN_CHECK(filter == MIGAN_PHOTO_NEAREST || filter == MIGAN_PHOTO_BICUBIC, MIGAN_EINVAL, "filter must be MIGAN_PHOTO_NEAREST or MIGAN_PHOTO_BICUBIC");
+}
+// one launch over the chunk's items: `tiles(item)` workgroups each (0: the item takes no part)
+template <class Tiles>
+static void photo_launch(void (*kernel)(const PhArgs), const char* name, PhArgs& a, Tiles tiles, size_t lds, void* stream) {
+  long long total = 0;
+  for (int j = 0; j < a.n; ++j) {
+    a.first[j] = (int)total;
+    total += tiles(a.item[j]);
+  }
+  a.first[a.n] = (int)total;
+  MIGAN_CHECK(total <= 0x7fffffffll, MIGAN_EINVAL, "too many workgroups in one launch");      // (32 largest items stay far below)
+  if (total > 0) rt_check(rt::launch(kernel, a, (unsigned)total, kPhThreads, lds, (rt::stream_t)stream), name);
+}
+}  // namespace migan
+
+extern "C" {
+
+int migan_photo_scratch_bytes(const migan_photo_item* items, int n, int channels, int filter, size_t* bytes) {
+  MIGAN_API_BEGIN
+  using namespace migan;
+  MIGAN_CHECK(bytes != nullptr, MIGAN_EINVAL, "null bytes");
+  photo_check_common(items, n, channels, filter);
+  size_t need = 0;
+  for (int i0 = 0; i0 < n; i0 += kPhItemsMax)            // launches follow each other on one stream, so the chunks share the scratch
+    need = std::max(need, photo_chunk(items, i0, std::min(kPhItemsMax, n - i0), channels, filter).bytes);
+  *bytes = need;
+  MIGAN_API_END
+}
+
+int migan_photo_resize_batch(const migan_photo_item* items, int n, int channels, int filter, int flags, void* scratch, void* stream) {
+  MIGAN_API_BEGIN
+  using namespace migan;
+  photo_check_common(items, n, channels, filter);
+  MIGAN_CHECK((flags & ~(MIGAN_PHOTO_INVERT | MIGAN_PHOTO_THRESHOLD)) == 0, MIGAN_EINVAL, "unknown flag");
+  MIGAN_CHECK(filter == MIGAN_PHOTO_NEAREST || flags == 0, MIGAN_EINVAL, "inversion and threshold go with MIGAN_PHOTO_NEAREST only");
+  MIGAN_CHECK(scratch != nullptr, MIGAN_EINVAL, "null scratch");
+  std::vector<PhChunk> chunks;
+  for (int i0 = 0; i0 < n; i0 += kPhItemsMax) chunks.push_back(photo_chunk(items, i0, std::min(kPhItemsMax, n - i0), channels, filter));
+  for (int i = 0; i < n; ++i) MIGAN_CHECK(items[i].src_u8 && items[i].dst_u8, MIGAN_EINVAL, "null src_u8 or dst_u8 in item " + std::to_string(i));
+  const PhForm form = photo_form();
+  const int C = channels;
+  for (size_t ci = 0; ci < chunks.size(); ++ci) {
+    const PhChunk& c = chunks[ci];
+    const migan_photo_item* src = items + ci * kPhItemsMax;
+    unsigned char* mid = (unsigned char*)scratch + c.tab_bytes;
+    PhArgs a{};
+    a.tab = (int*)scratch; a.n = c.k; a.C = C; a.flags = 0;
+    for (int j = 0; j < c.k; ++j) a.item[j] = c.item[j];
+    photo_launch(form.table, "migan::photo_table_kernel", a, [](const PhItem& it) { return ph_table_groups(it); }, 0, stream);
+    // horizontal pass: the source into the intermediate, or straight into the destination where no vertical pass follows
+    for (int j = 0; j < c.k; ++j) {
+      a.item[j].src = (const unsigned char*)src[j].src_u8;
+      a.item[j].dst = c.mid[j] != SIZE_MAX ? mid + c.mid[j] : (unsigned char*)src[j].dst_u8;
+    }
+    photo_launch(form.hpass[C == 3], C == 3 ? "migan::photo_hpass_kernel<3>" : "migan::photo_hpass_kernel<1>", a,
+                 [](const PhItem& it) { return it.ks_h > 0 ? ph_cdiv(it.dw, kPhTW) * ph_cdiv(it.sh, kPhTR) : 0; }, (size_t)kPhLdsBytes, stream);
+    // vertical pass: [sh][dw][C], the intermediate or (sw == dw) the source, into the destination
+    for (int j = 0; j < c.k; ++j) {
+      a.item[j].src = c.mid[j] != SIZE_MAX ? mid + c.mid[j] : (const unsigned char*)src[j].src_u8;
+      a.item[j].dst = (unsigned char*)src[j].dst_u8;
+    }
+    const auto bytes_tiles = [C](const PhItem& it) { return (int)(((size_t)it.dh * it.dw * C + kPhThreads - 1) / kPhThreads); };
+    photo_launch(form.vpass[C == 3], "migan::photo_vpass_kernel", a, [&](const PhItem& it) { return it.ks_v > 0 ? bytes_tiles(it) : 0; }, 0, stream);
+    // NEAREST, and the copies of BICUBIC
+    for (int j = 0; j < c.k; ++j) a.item[j].src = (const unsigned char*)src[j].src_u8;
+    a.flags = flags;
+    photo_launch(form.gather[C == 3], "migan::photo_gather_kernel", a, [&](const PhItem& it) { return it.ks_h < 0 ? bytes_tiles(it) : 0; }, 0, stream);
   }
   MIGAN_API_END
 }

@@ -97,6 +97,10 @@ COMODGAN_DTYPE_F32, COMODGAN_DTYPE_F16 = 0, 2
 METRICS_EXPORTS = ("migan_metrics_scratch_bytes", "migan_metrics_batch")
 METRICS_U8, METRICS_F32 = 0, 1
 METRICS_CHW, METRICS_HWC = 0, 1
+# include/migan_photo_hip.h
+PHOTO_EXPORTS = ("migan_photo_scratch_bytes", "migan_photo_resize_batch")
+PHOTO_NEAREST, PHOTO_BICUBIC = 0, 1
+PHOTO_INVERT, PHOTO_THRESHOLD = 1, 2
 
 
 class MetricsItem(C.Structure):
@@ -112,6 +116,22 @@ def metrics_items(items):
     for a, (gt, pred, mask, h, w) in zip(arr, items):
         a.gt, a.pred, a.mask = gt or None, pred or None, mask or None
         a.H, a.W = int(h), int(w)
+    return arr
+
+
+class PhotoItem(C.Structure):
+    """struct migan_photo_item"""
+    _fields_ = [("src_u8", C.c_void_p), ("dst_u8", C.c_void_p)] + [(n, C.c_int) for n in ("src_height", "src_width", "dst_height", "dst_width")]
+
+
+def photo_items(items):
+    """[(src_ptr, dst_ptr, src_height, src_width, dst_height, dst_width), ...] -> a migan_photo_item array (None passes a null table through)"""
+    if items is None:
+        return None
+    arr = (PhotoItem * max(1, len(items)))()
+    for a, (src, dst, sh, sw, dh, dw) in zip(arr, items):
+        a.src_u8, a.dst_u8 = src or None, dst or None
+        a.src_height, a.src_width, a.dst_height, a.dst_width = int(sh), int(sw), int(dh), int(dw)
     return arr
 
 
@@ -175,7 +195,7 @@ class MiganLib:
             raise MiganError(f"cannot load {self.path}: {e}") from e
         L = self.lib
         for name in (EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + PIPELINE_PATCHES_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS
-                     + U8_EXPORTS + METRICS_EXPORTS):
+                     + U8_EXPORTS + METRICS_EXPORTS + PHOTO_EXPORTS):
             if not hasattr(L, name):
                 raise MiganError(f"{self.path} does not export {name}")
         vp, ci = C.c_void_p, C.c_int
@@ -257,6 +277,8 @@ class MiganLib:
         L.migan_metrics_scratch_bytes.restype = C.c_size_t
         L.migan_metrics_batch.argtypes = [C.POINTER(MetricsItem), ci, ci, ci, ci, ci, C.c_float, C.c_float, vp, vp, vp, vp]
         L.migan_metrics_batch.restype = ci
+        L.migan_photo_scratch_bytes.argtypes = [C.POINTER(PhotoItem), ci, ci, ci, C.POINTER(C.c_size_t)]
+        L.migan_photo_resize_batch.argtypes = [C.POINTER(PhotoItem), ci, ci, ci, ci, vp, vp]
         L.migan_last_error.restype = C.c_char_p
         L.migan_last_kernel.restype = C.c_char_p
         L.migan_nan_policy.restype = C.c_char_p
@@ -406,6 +428,16 @@ class MiganLib:
         self.check(self.lib.migan_metrics_batch(metrics_items(items), 0 if items is None else len(items), int(samples), int(dtype), int(layout),
                                                 int(shave), C.c_float(lo), C.c_float(hi), C.c_void_p(scratch_ptr), C.c_void_p(out_mse_ptr),
                                                 C.c_void_p(out_ssim_ptr), C.c_void_p(stream)))
+
+    # Pillow-exact resize of uint8 images (include/migan_photo_hip.h): `items` = [(src_ptr, dst_ptr, src_h, src_w, dst_h, dst_w), ...]
+    def photo_scratch_bytes(self, items, channels: int, filter: int) -> int:
+        n = C.c_size_t(0)
+        self.check(self.lib.migan_photo_scratch_bytes(photo_items(items), 0 if items is None else len(items), int(channels), int(filter), C.byref(n)))
+        return int(n.value)
+
+    def photo_resize_batch(self, items, channels: int, filter: int, flags: int, scratch_ptr: int, stream: int = 0) -> None:
+        self.check(self.lib.migan_photo_resize_batch(photo_items(items), 0 if items is None else len(items), int(channels), int(filter), int(flags),
+                                                     C.c_void_p(scratch_ptr), C.c_void_p(stream)))
 
     def sepconv_forward(self, stream: int = 0, **kw) -> None:
         d = SepConvDesc()
