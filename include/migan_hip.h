@@ -223,6 +223,10 @@ int migan_set_debug(migan_handle* h, int keep_intermediates);
  * NHWC [batch][r][r][c] for "<block>.conv1|conv2", planar [batch][3][r][r] for "<block>.img". */
 int migan_debug_tensor(const migan_handle* h, int batch, const char* layer,
                        size_t* byte_offset, int64_t shape[4]);
+/* The same for the plan of migan_forward_hw at height x width (shapes [batch][h][w][c] and [batch][3][h][w] of the layer's own size);
+ * at height = width = resolution the answer of migan_debug_tensor.  Host code only: nothing is launched. */
+int migan_debug_tensor_hw(migan_handle* h, int batch, int height, int width, const char* layer,
+                          size_t* byte_offset, int64_t shape[4]);
 
 /* ---- single operator --------------------------------------------------------------------- */
 

@@ -1735,11 +1735,8 @@ int migan_set_debug(migan_handle* h, int keep) {
   MIGAN_API_END
 }
 
-int migan_debug_tensor(const migan_handle* h, int batch, const char* layer, size_t* byte_offset, int64_t shape[4]) {
-  MIGAN_API_BEGIN
-  MIGAN_CHECK(h && layer && byte_offset && shape, MIGAN_EINVAL, "null argument");
-  MIGAN_CHECK(h->debug, MIGAN_ESTATE, "migan_set_debug(h, 1) first");
-  const migan::Plan& P = h->plan;
+// where the debug plan P keeps the output of `layer` for a forward of `batch` images, and its shape
+static void migan_debug_tensor_of(const migan::Plan& P, int batch, const char* layer, size_t* byte_offset, int64_t shape[4]) {
   for (const auto& kv : P.debug_tensors) {
     if (kv.first != layer) continue;
     *byte_offset = migan::align256(P.shared_bytes) + migan_handle::sub_offset(P, kv.second, batch);     // debug plans never split the batch
@@ -1747,14 +1744,32 @@ int migan_debug_tensor(const migan_handle* h, int batch, const char* layer, size
     const bool is_img = n.size() > 4 && n.compare(n.size() - 4, 4, ".img") == 0;
     for (const auto& L : P.launches) {
       if (is_img) {
-        if (L.imgout_buf == kv.second) { shape[0] = batch; shape[1] = 3; shape[2] = L.hout; shape[3] = L.wout; return MIGAN_OK; }
+        if (L.imgout_buf == kv.second) { shape[0] = batch; shape[1] = 3; shape[2] = L.hout; shape[3] = L.wout; return; }
       } else if (!L.is_rgb && !L.is_dwfir && L.layer == n) {
         shape[0] = batch; shape[1] = L.hout; shape[2] = L.wout; shape[3] = L.cout;
-        return MIGAN_OK;
+        return;
       }
     }
   }
   throw migan::Error(MIGAN_EINVAL, std::string("no such debug tensor: ") + layer);
+}
+
+int migan_debug_tensor(const migan_handle* h, int batch, const char* layer, size_t* byte_offset, int64_t shape[4]) {
+  MIGAN_API_BEGIN
+  MIGAN_CHECK(h && layer && byte_offset && shape, MIGAN_EINVAL, "null argument");
+  MIGAN_CHECK(h->debug, MIGAN_ESTATE, "migan_set_debug(h, 1) first");
+  migan_debug_tensor_of(h->plan, batch, layer, byte_offset, shape);
+  MIGAN_API_END
+}
+
+int migan_debug_tensor_hw(migan_handle* h, int batch, int height, int width, const char* layer, size_t* byte_offset, int64_t shape[4]) {
+  MIGAN_API_BEGIN
+  MIGAN_CHECK(h && layer && byte_offset && shape, MIGAN_EINVAL, "null argument");
+  MIGAN_CHECK(h->debug, MIGAN_ESTATE, "migan_set_debug(h, 1) first");
+  MIGAN_CHECK(batch > 0, MIGAN_EINVAL, "empty batch");
+  // the same size rule as migan_forward_hw; plan_for caches the plan the forward at this size uses (the handle's own at H = W = resolution)
+  migan_check_hw(h, height, width);
+  migan_debug_tensor_of(h->plan_for(height, width), batch, layer, byte_offset, shape);
   MIGAN_API_END
 }
 

@@ -65,7 +65,7 @@ EXPORTS = (
     "migan_num_weights", "migan_weight_info", "migan_set_weight",
     "migan_commit", "migan_workspace_bytes", "migan_forward", "migan_workspace_bytes_hw", "migan_forward_hw", "migan_forward_u8",
     "migan_num_launches", "migan_launch_info",
-    "migan_forward_timed", "migan_set_debug", "migan_debug_tensor", "migan_sepconv_forward",
+    "migan_forward_timed", "migan_set_debug", "migan_debug_tensor", "migan_debug_tensor_hw", "migan_sepconv_forward",
     "migan_pack_input", "migan_compose_output",
     "migan_pipeline_mask_resize", "migan_pipeline_scratch_bytes", "migan_pipeline_bbox", "migan_pipeline_pre", "migan_pipeline_post",
     "migan_pipeline_batch_scratch_bytes", "migan_pipeline_batch_pre", "migan_pipeline_batch_post",
@@ -233,6 +233,7 @@ class MiganLib:
         L.migan_forward_timed.argtypes = [vp, vp, vp, ci, vp, C.c_size_t, vp, C.POINTER(C.c_float), ci]
         L.migan_set_debug.argtypes = [vp, ci]
         L.migan_debug_tensor.argtypes = [vp, ci, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]
+        L.migan_debug_tensor_hw.argtypes = [vp, ci, ci, ci, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]
         L.migan_sepconv_forward.argtypes = [C.POINTER(SepConvDesc), vp]
         L.migan_set_tuning.argtypes = [C.c_char_p, ci]
         L.migan_get_tuning.argtypes = [C.c_char_p, C.POINTER(ci)]
@@ -576,6 +577,13 @@ class MiganHandle:
         off = C.c_size_t()
         shape = (C.c_int64 * 4)()
         self.lib.check(self.lib.lib.migan_debug_tensor(self._h, int(batch), layer.encode(), C.byref(off), shape))
+        return int(off.value), tuple(int(s) for s in shape)
+
+    def debug_tensor_hw(self, batch: int, height: int, width: int, layer: str) -> Tuple[int, Tuple[int, ...]]:
+        """debug_tensor for the plan of forward_hw at height x width"""
+        off = C.c_size_t()
+        shape = (C.c_int64 * 4)()
+        self.lib.check(self.lib.lib.migan_debug_tensor_hw(self._h, int(batch), int(height), int(width), layer.encode(), C.byref(off), shape))
         return int(off.value), tuple(int(s) for s in shape)
 
 

@@ -83,11 +83,11 @@ def check_hw_case(pkg, lib, mem, hw, batch, grid, symbol, seed=23, res=512):
         yd, rawd, named = g.forward_hw(x)
         assert named == name, (named, name)
         np.testing.assert_array_equal(yd, y)
-        # (migan_debug_tensor describes the fixed-size plan only, so at H x W the map is found by layout: a debug plan gives every layer a
-        # buffer of its own in launch order, the last layer's is the last of the workspace.  tests/test_gpu_last_store.py reads it through
-        # migan_debug_tensor at the network's own size.)
+        # (migan_debug_tensor_hw: the plan at H x W.  By layout the map is the last buffer of the workspace -- a debug plan gives every
+        # layer a buffer of its own in launch order -- and the two must agree.)
         nbytes = batch * hh * ww * cl * 4
-        off = rawd.size - (nbytes + 255) // 256 * 256
+        off, shape = g.h.debug_tensor_hw(batch, hh, ww, last)
+        assert shape == (batch, hh, ww, cl) and off == rawd.size - (nbytes + 255) // 256 * 256, (off, shape, rawd.size)
         got = rawd[off:off + nbytes].view(np.float32).reshape(batch, hh, ww, cl)
         np.testing.assert_allclose(np.transpose(got, (0, 3, 1, 2)), tap, rtol=0, atol=TAP_TOL * max(1.0, float(np.abs(tap).max())), err_msg=last)
         g.h.set_debug(False)

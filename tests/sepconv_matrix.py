@@ -22,7 +22,8 @@ NON_SEPCONV = (
 )
 # SeparableConv2d forms the generator picks per launch size that migan_sepconv_forward does not offer: the small-launch tiles of
 # MIGAN_GEOMETRIES_SMALL (32-row tiles of plain / pointwise / FIR-up layers, the 32 x 32 K-split tile, the 64-row FIR-up tile), chosen for
-# launches of few workgroups.  No operator case can reach them; the generator tests cover them.
+# launches of few workgroups.  No operator case can reach them; tests/migan_layers_case.py checks each of their launches in isolation, in
+# plan context, and asserts that all 11 of every slice that has them run.
 PLAN_ONLY = re.compile(r"^migan::sepconv_kernel<(\d, 32|2, 64), ")
 
 
