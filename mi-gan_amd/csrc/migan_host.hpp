@@ -21,6 +21,7 @@
 #include "../../include/migan_hip.h"
 #include "../../include/migan_pipeline_samples_hip.h"
 #include "../../include/migan_pipeline_patches_hip.h"
+#include "../../include/migan_pipeline_regions_hip.h"
 #include "../../include/migan_metrics_hip.h"
 #include "../../include/migan_photo_hip.h"
 #include "migan_table.hpp"
@@ -2165,6 +2166,178 @@ int migan_pipeline_batch_post_patches(const migan_pipeline_item* items, int n, i
                "migan::pipe_post_patches_kernel");
     i0 += (size_t)k;
   }
+  MIGAN_API_END
+}
+
+// ---- one crop per hole region (include/migan_pipeline_regions_hip.h; kernels: migan_pipeline_regions.inc) ----
+// Scratch of regions_find: per item the nearest resize of its mask when that has another size, the row pass of the dilation
+// (1 byte per pixel), the union-find forest (4 bytes per pixel) and the item's counter, root list and extents.  One layout for
+// _scratch_bytes and _find; it also checks the items.
+static size_t migan_pipeline_regions_plan(const migan_pipeline_item* items, int n, int gap, int max_regions, void* scratch,
+                                          void* const* labels, std::vector<migan::PipeRegionsItem>* out) {
+  using namespace migan;
+  MIGAN_CHECK(items != nullptr && n >= 1, MIGAN_EINVAL, "the batch needs at least one item");
+  MIGAN_CHECK(gap >= 2 && gap <= kRegionsGapMax, MIGAN_EINVAL,
+              "gap must be in 2 ... 64 (below 2 a region's feathered mask would reach another region's hole pixels)");
+  MIGAN_CHECK(max_regions >= 1 && max_regions <= kRegionsCap, MIGAN_EINVAL, "max_regions must be in 1 ... 64");
+  size_t bytes = 0;
+  if (out) out->resize((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    const migan_pipeline_item& it = items[i];
+    MIGAN_CHECK(!out || (it.mask_u8 && labels[i]), MIGAN_EINVAL, "null mask or label map of item " + std::to_string(i));
+    MIGAN_CHECK(it.height >= 3 && it.width >= 3 && (unsigned long long)it.height * it.width < (1ull << 30), MIGAN_EINVAL,
+                "item " + std::to_string(i) + ": image must be at least 3x3 (reflect padding of the 5x5 blur) and below 2^30 pixels");
+    MIGAN_CHECK(it.mask_height > 0 && it.mask_width > 0 && (unsigned long long)it.mask_height * it.mask_width < (1ull << 30), MIGAN_EINVAL,
+                "item " + std::to_string(i) + ": bad mask size");
+    const bool resize = it.mask_height != it.height || it.mask_width != it.width;
+    const size_t plane = align256((size_t)it.height * it.width);
+    if (out) {
+      PipeRegionsItem& b = (*out)[(size_t)i];
+      char* at = (char*)scratch + bytes;
+      b.mask_src = (const unsigned char*)it.mask_u8;
+      b.mask_resized = resize ? (unsigned char*)at : nullptr;
+      at += resize ? plane : 0;
+      b.rowdil = (unsigned char*)at;
+      b.parent = (int*)(at + plane);
+      b.meta = (int*)(at + plane + align256((size_t)it.height * it.width * sizeof(int)));
+      b.labels = (unsigned char*)labels[i];
+      b.H = it.height; b.W = it.width; b.mh = it.mask_height; b.mw = it.mask_width;
+    }
+    bytes += (resize ? plane : 0) + plane + align256((size_t)it.height * it.width * sizeof(int)) + align256(kRegMetaInts * sizeof(int));
+  }
+  return bytes;
+}
+int migan_pipeline_regions_scratch_bytes(const migan_pipeline_item* items, int n, int gap, int max_regions, size_t* bytes) {
+  MIGAN_API_BEGIN
+  MIGAN_CHECK(bytes, MIGAN_EINVAL, "bad argument");
+  *bytes = migan_pipeline_regions_plan(items, n, gap, max_regions, nullptr, nullptr, nullptr);
+  MIGAN_API_END
+}
+// the nine kernels of migan_pipeline_regions.inc, each over all items (kRegionsFindMax and fewer than 2^31 workgroups per launch),
+// all on `stream`, nothing read back
+int migan_pipeline_regions_find(const migan_pipeline_item* items, int n, int resolution, int padding, int gap, int max_regions,
+                                void* const* labels, int* count_dev, int* boxes_dev, void* scratch, void* stream) {
+  MIGAN_API_BEGIN
+  using namespace migan;
+  MIGAN_CHECK(resolution >= 8 && (resolution & (resolution - 1)) == 0, MIGAN_EINVAL, "resolution must be a power of two >= 8");
+  MIGAN_CHECK(labels && count_dev && boxes_dev && scratch && padding >= 0, MIGAN_EINVAL, "bad argument");
+  std::vector<PipeRegionsItem> its;
+  migan_pipeline_regions_plan(items, n, gap, max_regions, scratch, labels, &its);
+  PipeRegionsArgs proto{};
+  proto.count = count_dev; proto.boxes = boxes_dev;
+  proto.R = resolution; proto.padding = padding; proto.gap = gap; proto.max_regions = max_regions;
+  auto run = [&](void (*kernel)(const PipeRegionsArgs), const char* name, auto tiles, size_t lds) {
+    for (size_t i0 = 0; i0 < its.size();) {
+      PipeRegionsArgs a = proto;
+      unsigned long long total = 0;
+      int k = 0;
+      for (; k < kRegionsFindMax && i0 + k < its.size(); ++k) {
+        const unsigned long long t = tiles(its[i0 + k]);
+        if (k > 0 && total + t > 0x7fffffffull) break;
+        a.item[k] = its[i0 + k];
+        a.first[k] = (int)total;
+        total += t;
+      }
+      a.first[k] = (int)total;
+      a.n = k;
+      a.count += i0;
+      a.boxes += i0 * (size_t)(max_regions + 1) * 4;
+      if (total) rt_check(rt::launch(kernel, a, (unsigned)total, kThreads, lds, (rt::stream_t)stream), name);
+      i0 += (size_t)k;
+    }
+  };
+  auto pixels = [](const PipeRegionsItem& it) { return (unsigned long long)cdiv(it.H * it.W, kThreads); };
+  auto tiles32 = [](const PipeRegionsItem& it) { return (unsigned long long)cdiv(it.W, kRegTile) * (unsigned long long)cdiv(it.H, kRegTile); };
+  auto one = [](const PipeRegionsItem&) { return 1ull; };
+  run(regions_mask_resize_kernel, "migan::regions_mask_resize_kernel", [&](const PipeRegionsItem& it) { return it.mask_resized ? pixels(it) : 0ull; }, 0);
+  run(regions_dilate_rows_kernel, "migan::regions_dilate_rows_kernel",
+      [](const PipeRegionsItem& it) { return (unsigned long long)cdiv(it.W, kThreads) * (unsigned long long)it.H; }, kRegRowWords * sizeof(unsigned));
+  run(regions_dilate_cols_kernel, "migan::regions_dilate_cols_kernel",
+      [](const PipeRegionsItem& it) { return (unsigned long long)cdiv(it.W, kRegTile) * (unsigned long long)cdiv(it.H, kRegColRows); },
+      kRegTile * kRegColStride * sizeof(unsigned));
+  run(regions_label_tile_kernel, "migan::regions_label_tile_kernel", tiles32, kRegTile * kRegTile * sizeof(int));
+  run(regions_merge_kernel, "migan::regions_merge_kernel", tiles32, 0);
+  run(regions_roots_kernel, "migan::regions_roots_kernel", pixels, 0);
+  run(regions_sort_kernel, "migan::regions_sort_kernel", one, 0);
+  run(regions_labels_kernel, "migan::regions_labels_kernel", pixels, 5 * (kRegionsCap + 1) * sizeof(int));
+  run(regions_boxes_kernel, "migan::regions_boxes_kernel", one, 0);
+  MIGAN_API_END
+}
+// the rows of regions_pre / _post -> the kernels' table; checks everything the kernels index with
+static void migan_pipeline_rows_plan(const migan_pipeline_region_row* rows, int m, int resolution, std::vector<migan::PipeRowItem>* out) {
+  using namespace migan;
+  MIGAN_CHECK(rows != nullptr && m >= 1, MIGAN_EINVAL, "the call needs at least one row");
+  MIGAN_CHECK(resolution >= 8 && (resolution & (resolution - 1)) == 0, MIGAN_EINVAL, "resolution must be a power of two >= 8");
+  out->resize((size_t)m);
+  for (int i = 0; i < m; ++i) {
+    const migan_pipeline_region_row& r = rows[i];
+    const std::string who = "row " + std::to_string(i);
+    MIGAN_CHECK(r.image_chw_u8 && r.mask_u8, MIGAN_EINVAL, "null image or mask in " + who);
+    MIGAN_CHECK(r.height >= 3 && r.width >= 3 && (unsigned long long)r.height * r.width < (1ull << 30), MIGAN_EINVAL,
+                who + ": image must be at least 3x3 (reflect padding of the 5x5 blur) and below 2^30 pixels");
+    MIGAN_CHECK(r.label >= 0 && r.label <= kRegionsCap, MIGAN_EINVAL, who + ": label must be in 0 ... 64");
+    MIGAN_CHECK(r.label == 0 || r.labels_u8, MIGAN_EINVAL, who + ": a label above 0 needs the label map");
+    MIGAN_CHECK(r.box[0] >= 0 && r.box[1] <= r.width && r.box[2] >= 0 && r.box[3] <= r.height && r.box[1] - r.box[0] >= 3 &&
+                r.box[3] - r.box[2] >= 3, MIGAN_EINVAL, who + ": box = {x_min, x_max, y_min, y_max} must lie inside the image and be at least 3x3");
+    PipeRowItem& b = (*out)[(size_t)i];
+    b.image = (unsigned char*)r.image_chw_u8; b.mask = (const unsigned char*)r.mask_u8; b.labels = (const unsigned char*)r.labels_u8;
+    b.H = r.height; b.W = r.width; b.label = r.label;
+    for (int j = 0; j < 4; ++j) b.box[j] = r.box[j];
+  }
+}
+// one kernel over all rows, kPipeRowsMax (and fewer than 2^31 workgroups) per launch: tiles(row) workgroups for each
+extern "C++" template <class Tiles>
+static void migan_pipeline_rows_run(void (*kernel)(const migan::PipeRowsArgs), const char* name, const migan::PipeRowsArgs& proto,
+                                    const std::vector<migan::PipeRowItem>& rows, Tiles tiles, size_t lds, void* stream) {
+  using namespace migan;
+  const size_t plane = (size_t)proto.R * proto.R;
+  for (size_t i0 = 0; i0 < rows.size();) {
+    PipeRowsArgs a = proto;
+    unsigned long long total = 0;
+    int k = 0;
+    for (; k < kPipeRowsMax && i0 + k < rows.size(); ++k) {
+      const unsigned long long t = tiles(rows[i0 + k]);
+      if (k > 0 && total + t > 0x7fffffffull) break;
+      a.item[k] = rows[i0 + k];
+      a.first[k] = (int)total;
+      total += t;
+    }
+    a.first[k] = (int)total;
+    a.n = k;
+    if (a.x) a.x += i0 * 4 * plane;
+    if (a.y) a.y += i0 * 3 * plane;
+    if (total) rt_check(rt::launch(kernel, a, (unsigned)total, kThreads, lds, (rt::stream_t)stream), name);
+    i0 += (size_t)k;
+  }
+}
+int migan_pipeline_regions_pre(const migan_pipeline_region_row* rows, int m, int resolution, void* x_nchw, void* stream) {
+  MIGAN_API_BEGIN
+  using namespace migan;
+  MIGAN_CHECK(x_nchw, MIGAN_EINVAL, "null tensor");
+  std::vector<PipeRowItem> its;
+  migan_pipeline_rows_plan(rows, m, resolution, &its);
+  PipeRowsArgs a{};
+  a.x = (float*)x_nchw; a.R = resolution;
+  const unsigned long long per_row = (unsigned long long)cdiv(resolution * resolution, kThreads);
+  migan_pipeline_rows_run(pipe_pre_rows_kernel, "migan::pipe_pre_rows_kernel", a, its, [=](const PipeRowItem&) { return per_row; }, 0, stream);
+  MIGAN_API_END
+}
+// the box is host data: the grid has exactly the crop's tiles
+int migan_pipeline_regions_post(const migan_pipeline_region_row* rows, int m, int resolution, const void* y_nchw, const float* gauss25,
+                                void* stream) {
+  MIGAN_API_BEGIN
+  using namespace migan;
+  MIGAN_CHECK(y_nchw, MIGAN_EINVAL, "null tensor");
+  std::vector<PipeRowItem> its;
+  migan_pipeline_rows_plan(rows, m, resolution, &its);
+  PipeRowsArgs a{};
+  a.y = (const float*)y_nchw; a.R = resolution;
+  migan_pipeline_gauss(gauss25, a.gauss);
+  migan_pipeline_rows_run(pipe_post_rows_kernel, "migan::pipe_post_rows_kernel", a, its,
+                          [](const PipeRowItem& it) {
+                            return (unsigned long long)cdiv(it.box[1] - it.box[0], kPostTW) * (unsigned long long)cdiv(it.box[3] - it.box[2], kPostTH);
+                          },
+                          (size_t)kPostLdsBytes + 16, stream);
   MIGAN_API_END
 }
 

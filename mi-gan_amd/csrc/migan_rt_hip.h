@@ -79,6 +79,12 @@ __device__ __forceinline__ float migan_sum8(float v) {
 #define MIGAN_OPAQUE_F(x) asm volatile("" : "+v"(x))
 #define MIGAN_CLOCK() __builtin_readcyclecounter()
 #define MIGAN_ATOMIC_ADD_U64(p, v) atomicAdd((p), (v))
+// 32-bit integer atomics at device scope, on global memory or LDS (migan_pipeline_regions.inc), and a load that bypasses the CU's cache
+#define MIGAN_ATOMIC_MIN_I32(p, v) atomicMin((p), (v))
+#define MIGAN_ATOMIC_MAX_I32(p, v) atomicMax((p), (v))
+#define MIGAN_ATOMIC_ADD_I32(p, v) atomicAdd((p), (v))
+#define MIGAN_ATOMIC_OR_U32(p, v) atomicOr((p), (v))
+#define MIGAN_LOAD_AGENT_I32(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 
 // ---- LDS-DMA staging (sepconv_wide_kernel<..., DMA>) ---------------------------------------------------------------------------
 // wave-uniform value the compiler can keep in an SGPR (threadIdx-derived values are divergent to it even when they are not)

@@ -83,6 +83,9 @@ SAMPLES_EXPORTS = ("comodgan_workspace_bytes_samples", "comodgan_forward_samples
 PIPELINE_SAMPLES_EXPORTS = ("migan_pipeline_batch_post_samples",)
 # include/migan_pipeline_patches_hip.h
 PIPELINE_PATCHES_EXPORTS = ("migan_pipeline_batch_post_patches",)
+# include/migan_pipeline_regions_hip.h
+PIPELINE_REGIONS_EXPORTS = ("migan_pipeline_regions_scratch_bytes", "migan_pipeline_regions_find", "migan_pipeline_regions_pre",
+                            "migan_pipeline_regions_post")
 # include/comodgan_fp16_hip.h
 FP16_EXPORTS = ("comodgan_set_fp16_blocks", "comodgan_get_fp16_blocks")
 # include/comodgan_fp16_storage_hip.h
@@ -150,6 +153,25 @@ def pipeline_items(items):
     return arr
 
 
+class PipelineRegionRow(C.Structure):
+    """struct migan_pipeline_region_row"""
+    _fields_ = [("image_chw_u8", C.c_void_p), ("mask_u8", C.c_void_p), ("labels_u8", C.c_void_p), ("height", C.c_int), ("width", C.c_int),
+                ("label", C.c_int), ("box", C.c_int * 4)]
+
+
+def pipeline_region_rows(rows):
+    """[(image_ptr, mask_ptr, labels_ptr or None, height, width, label, (x_min, x_max, y_min, y_max)), ...] -> a migan_pipeline_region_row
+    array (None passes a null table through)"""
+    if rows is None:
+        return None
+    arr = (PipelineRegionRow * max(1, len(rows)))()
+    for a, (img, msk, lab, h, w, label, box) in zip(arr, rows):
+        a.image_chw_u8, a.mask_u8, a.labels_u8 = img or None, msk or None, lab or None
+        a.height, a.width, a.label = int(h), int(w), int(label)
+        a.box[:] = [int(v) for v in box]
+    return arr
+
+
 class CoModGANConfig(C.Structure):
     """struct comodgan_config"""
     _fields_ = [(n, C.c_int) for n in ("resolution", "ch_base", "ch_max", "z_dim", "w_dim", "w0_dim", "map_layers", "num_ws")]
@@ -194,7 +216,7 @@ class MiganLib:
         except OSError as e:  # pragma: no cover - depends on the machine
             raise MiganError(f"cannot load {self.path}: {e}") from e
         L = self.lib
-        for name in (EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + PIPELINE_PATCHES_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS
+        for name in (EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + PIPELINE_PATCHES_EXPORTS + PIPELINE_REGIONS_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS
                      + U8_EXPORTS + METRICS_EXPORTS + PHOTO_EXPORTS):
             if not hasattr(L, name):
                 raise MiganError(f"{self.path} does not export {name}")
@@ -221,6 +243,10 @@ class MiganLib:
         L.migan_pipeline_batch_post_samples.argtypes = [C.POINTER(PipelineItem), ci, ci, ci, vp, vp, C.POINTER(C.c_float), vp, C.POINTER(vp), vp]
         L.migan_pipeline_batch_post_patches.argtypes = [C.POINTER(PipelineItem), ci, ci, ci, vp, vp, C.POINTER(C.c_float), vp, C.POINTER(vp),
                                                         C.POINTER(C.c_size_t), vp]
+        L.migan_pipeline_regions_scratch_bytes.argtypes = [C.POINTER(PipelineItem), ci, ci, ci, C.POINTER(C.c_size_t)]
+        L.migan_pipeline_regions_find.argtypes = [C.POINTER(PipelineItem), ci, ci, ci, ci, ci, C.POINTER(vp), vp, vp, vp, vp]
+        L.migan_pipeline_regions_pre.argtypes = [C.POINTER(PipelineRegionRow), ci, ci, vp, vp]
+        L.migan_pipeline_regions_post.argtypes = [C.POINTER(PipelineRegionRow), ci, ci, vp, C.POINTER(C.c_float), vp]
         L.migan_num_weights.argtypes = [vp, C.POINTER(ci)]
         L.migan_weight_info.argtypes = [vp, ci, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(ci), C.POINTER(ci)]
         L.migan_set_weight.argtypes = [vp, C.c_char_p, vp, C.POINTER(C.c_int64), ci]
@@ -290,7 +316,7 @@ class MiganLib:
         if not allow_test_backend and L.migan_backend().decode() != PRODUCT_BACKEND:
             raise MiganError(f"{self.path} reports backend {L.migan_backend().decode()!r}, not {PRODUCT_BACKEND!r}: only the gfx950 HIP "
                              f"library is a product backend (the CPU emulator build is test infrastructure)")
-        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + PIPELINE_PATCHES_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS + U8_EXPORTS:
+        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + PIPELINE_PATCHES_EXPORTS + PIPELINE_REGIONS_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS + U8_EXPORTS:
             if name not in ("migan_last_error", "migan_last_kernel", "migan_nan_policy", "migan_backend", "migan_gemm_variant", "migan_tuning_key"):
                 getattr(L, name).restype = ci
 
@@ -415,6 +441,32 @@ class MiganLib:
         self.check(self.lib.migan_pipeline_batch_post_patches(pipeline_items(items), len(items), int(samples), int(resolution),
                                                               C.c_void_p(y_ptr), C.c_void_p(bbox_ptr), g, C.c_void_p(scratch_ptr), outs, caps,
                                                               C.c_void_p(stream)))
+
+    # one crop per hole region (include/migan_pipeline_regions_hip.h): `items` as for the batch form; `rows` =
+    # [(image_ptr, mask_ptr, labels_ptr or None, height, width, label, box), ...], the mask at the image's size
+    def pipeline_regions_scratch_bytes(self, items, gap: int, max_regions: int) -> int:
+        n = C.c_size_t()
+        self.check(self.lib.migan_pipeline_regions_scratch_bytes(pipeline_items(items), len(items), int(gap), int(max_regions), C.byref(n)))
+        return int(n.value)
+
+    def pipeline_regions_find(self, items, resolution: int, padding: int, gap: int, max_regions: int, label_ptrs, count_ptr: int,
+                              boxes_ptr: int, scratch_ptr: int, stream: int = 0) -> None:
+        """label_ptrs[i] -> uint8 [H_i, W_i]; count int32 [n]; boxes int32 [n, max_regions + 1, 4], slot 0 = the single box"""
+        labels = None if label_ptrs is None else (C.c_void_p * max(1, len(label_ptrs)))(*[p or None for p in label_ptrs])
+        if labels is not None and len(label_ptrs) != len(items):
+            raise ValueError(f"expected one label map per item, got {len(label_ptrs)} for {len(items)} items")
+        self.check(self.lib.migan_pipeline_regions_find(pipeline_items(items), len(items), int(resolution), int(padding), int(gap),
+                                                        int(max_regions), labels, C.c_void_p(count_ptr), C.c_void_p(boxes_ptr),
+                                                        C.c_void_p(scratch_ptr), C.c_void_p(stream)))
+
+    def pipeline_regions_pre(self, rows, resolution: int, x_ptr: int, stream: int = 0) -> None:
+        self.check(self.lib.migan_pipeline_regions_pre(pipeline_region_rows(rows), 0 if rows is None else len(rows), int(resolution),
+                                                       C.c_void_p(x_ptr), C.c_void_p(stream)))
+
+    def pipeline_regions_post(self, rows, resolution: int, y_ptr: int, gauss25=None, stream: int = 0) -> None:
+        g = None if gauss25 is None else (C.c_float * 25)(*[float(v) for v in gauss25])
+        self.check(self.lib.migan_pipeline_regions_post(pipeline_region_rows(rows), 0 if rows is None else len(rows), int(resolution),
+                                                        C.c_void_p(y_ptr), g, C.c_void_p(stream)))
 
     # PSNR / SSIM of completions against the photo (include/migan_metrics_hip.h): `items` = [(gt_ptr, pred_ptr, mask_ptr or None, H, W), ...]
     def metrics_scratch_bytes(self, items, samples: int) -> int:

@@ -64,7 +64,10 @@ class MIGAN_Pipeline(torch.nn.Module):
     pass over the image per chunk (``migan_pipeline_batch_post_samples``).
 
     ``forward_patches(images, masks, z)`` returns the same completions as box-sized patches, [S, 3, ch_i, cw_i], and the boxes
-    (``migan_pipeline_batch_post_patches``): the pixels outside a box are the photo's in every completion."""
+    (``migan_pipeline_batch_post_patches``): the pixels outside a box are the photo's in every completion.
+
+    ``forward_regions(images, masks)`` is ``forward_batch`` with one crop per hole region instead of one per image: a photo with
+    several marked objects far apart gets each of them completed at its own scale (``migan_pipeline_regions_find / _pre / _post``)."""
 
     def __init__(self, model_path, resolution: int, padding: int = 128, device="cuda"):
         super().__init__()
@@ -350,3 +353,87 @@ class MIGAN_Pipeline(torch.nn.Module):
                 patches += outs
                 boxes.append(rows)
         return patches, torch.cat(boxes)
+
+    @torch.no_grad()
+    def forward_regions(self, images, masks, *, gap=None, max_regions: int = 8, max_batch: int = 32, return_regions: bool = False):
+        """``forward_batch`` with ONE CROP PER HOLE REGION.  ``forward_batch`` puts one box around every hole pixel of an image, so two
+        small holes in opposite corners of a large photo share one crop squeezed to the network resolution; here the mask is split
+        into regions on the device and every region gets a box of its own by the same box rule.  Arguments, checks and error types
+        are ``forward_batch``'s; the images are modified in place and returned as a list.
+
+        Regions: with hole pixel = ``mask != 255`` (the mask nearest-resized to the image first), D = every pixel within Chebyshev
+        distance ``gap`` of a hole pixel, a region is an 8-connected component of D, numbered 1 ... K in raster order of its first
+        pixel.  Region k's box is ``get_masked_bbox`` of its hole pixels, its network input is the crop with the FULL mask, and its
+        result is ``forward_batch``'s post-processing of that crop stored only where the label is k.  ``gap`` defaults to
+        ``max(2, padding // 4)`` and must be in 2 ... 64: the feathered mask at a pixel depends on the mask within 3 pixels of it and
+        every other region's hole pixel is at least ``gap + 2`` away, so with ``gap >= 2`` a region's bytes are those a mask holding
+        that region alone would give, and no pixel has two writers.
+
+        When not to split: an image with K <= 1, with K > ``max_regions`` (1 ... 64), or whose single box has both sides <= the
+        network resolution (its crop is not downscaled: splitting gains nothing) runs as one row with ``forward_batch``'s box, and
+        its bytes are ``forward_batch``'s.  An image without a hole pixel has no row and is left untouched.
+
+        Per call: ``migan_pipeline_regions_find`` for all images -> ONE copy of the counts and boxes to the host, which sizes the
+        generator batch: ONE HOST SYNCHRONISATION PER CALL (``forward_batch`` has none) -> the rows of all images in one list -> the
+        network input of ALL rows (an image's rows may straddle chunks, and every input must be formed before any result is stored
+        into its image: ``rows * 4 * R * R * 4`` bytes are held at once) -> per chunk of at most ``max_batch`` rows ONE
+        ``self.model(x)`` and ``migan_pipeline_regions_post``.  A lone last chunk runs at batch 2, as in ``forward_batch``, so the
+        result does not depend on ``max_batch``.
+
+        With ``return_regions`` also returns, per image, the int32 CPU tensor [rows_i, 4] of the boxes used ({x_min, x_max, y_min,
+        y_max}; one row when not split, none without a hole) and the uint8 label map [H_i, W_i] on the device (unspecified for an
+        image with more than ``max_regions`` regions)."""
+        images, masks = list(images), list(masks)
+        if len(images) != len(masks) or not images:
+            raise RuntimeError(f"expected as many masks as images and at least one, got {len(images)} images and {len(masks)} masks")
+        if int(max_batch) < 1:
+            raise RuntimeError(f"max_batch must be at least 1, got {max_batch}")
+        gap = max(2, self.padding // 4) if gap is None else int(gap)
+        max_regions, max_batch = int(max_regions), int(max_batch)
+        if not 2 <= gap <= 64:
+            raise ValueError(f"gap must be in 2 ... 64, got {gap}")
+        if not 1 <= max_regions <= 64:
+            raise ValueError(f"max_regions must be in 1 ... 64, got {max_regions}")
+        items, device = self._batch_items(images, masks)
+        lib = load_library()
+        n, cap, res = len(items), max_regions + 1, self.res
+        with torch.cuda.device(device):                          # the handle-free entry points launch on the CURRENT device
+            stream = int(torch.cuda.current_stream(device).cuda_stream)
+            table = [it[:6] for it in items]
+            scratch = self._scratch_bytes(lib.pipeline_regions_scratch_bytes(table, gap, max_regions), device)
+            labels = [torch.empty((it[2], it[3]), dtype=torch.uint8, device=device) for it in items]
+            found = torch.empty(n + n * cap * 4, dtype=torch.int32, device=device)       # the counts, then the boxes: one copy
+            count, boxes = found[:n], found[n:]
+            lib.pipeline_regions_find(table, res, self.padding, gap, max_regions, [t.data_ptr() for t in labels], count.data_ptr(),
+                                      boxes.data_ptr(), scratch.data_ptr(), stream)
+            host = found.cpu()                                   # (waits for the labelling: the synchronisation of this mode)
+            counts, host_boxes = host[:n].tolist(), host[n:].view(n, cap, 4)
+            full, rows, used = [], [], []
+            for i, it in enumerate(items):
+                mask = it[6]
+                if (it[4], it[5]) != (it[2], it[3]):             # the rows take the mask at the image's size (:256)
+                    mask = torch.empty((it[2], it[3]), dtype=torch.uint8, device=device)
+                    lib.pipeline_mask_resize(it[1], it[4], it[5], mask.data_ptr(), it[2], it[3], stream)
+                full.append(mask)
+                k, box = counts[i], host_boxes[i]
+                single = box[0].tolist()
+                if k == 0:
+                    mine = []
+                elif k < 2 or k > max_regions or (single[1] - single[0] <= res and single[3] - single[2] <= res):
+                    mine = [(0, single)]
+                else:
+                    mine = [(r, box[r].tolist()) for r in range(1, k + 1)]
+                rows += [(it[0], mask.data_ptr(), labels[i].data_ptr(), it[2], it[3], label, b) for label, b in mine]
+                used.append(torch.tensor([b for _, b in mine], dtype=torch.int32).view(len(mine), 4))
+            if rows:
+                # forward_batch's rule for a lone last chunk: it runs at batch 2 (its x twice), so no row sees a batch-1 forward
+                lone = len(rows) % max_batch == 1 and len(rows) > 1 and max_batch > 1
+                x = torch.empty((len(rows) + (1 if lone else 0), 4, res, res), dtype=torch.float32, device=device)
+                lib.pipeline_regions_pre(rows, res, x.data_ptr(), stream)
+                if lone:
+                    x[-1].copy_(x[-2])
+                for r0 in range(0, len(rows), max_batch):
+                    chunk = rows[r0:r0 + max_batch]
+                    y = self.model(x[r0:r0 + len(chunk) + (1 if lone and len(chunk) == 1 else 0)]).contiguous()
+                    lib.pipeline_regions_post(chunk, res, y.data_ptr(), gauss25=self._gauss, stream=stream)
+        return (images, used, labels) if return_regions else images
