@@ -10,7 +10,7 @@ The directory name contains a dash, so import it with
 ``importlib.import_module("mi-gan_amd")`` or through the ``migan_amd`` alias
 module at the repository root.
 """
-from . import comodgan, comodgan_schema, convert, distributed, hipbind, metrics, photo, pipeline, schema, synth  # noqa: F401
+from . import comodgan, comodgan_schema, convert, distributed, hipbind, masks, metrics, photo, pipeline, schema, synth  # noqa: F401
 from .migan_inference import Generator  # noqa: F401
 from .hipbind import MiganLib, MiganError, load_library, library_path  # noqa: F401
 
@@ -41,4 +41,4 @@ def install_into_reference(migan: bool = True, comodgan_too: bool = True) -> Non
             pass
 
 
-__all__ = ["install_into_reference", "Generator", "MiganLib", "MiganError", "load_library", "library_path", "schema", "synth", "pipeline", "convert", "comodgan", "metrics", "photo"]
+__all__ = ["install_into_reference", "Generator", "MiganLib", "MiganError", "load_library", "library_path", "schema", "synth", "pipeline", "convert", "comodgan", "metrics", "photo", "masks"]

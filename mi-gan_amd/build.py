@@ -28,13 +28,15 @@ SOURCES = [os.path.join(CSRC, f) for f in ("migan_hip.hip", "migan_k_slice.hip",
                                             "comodgan_kernels.hpp", "comodgan_conv_body.inc", "comodgan_fir_body.inc", "comodgan_fromrgb_body.inc",
                                             "comodgan_torgb_body.inc", "comodgan_host.hpp", "comodgan_u8.hip", "migan_pipeline.hpp",
                                             "migan_pipeline_pool_body.inc", "migan_pipeline_samples_body.inc", "migan_pipeline_regions.inc",
-                                            "migan_metrics.hpp", "migan_metrics.hip", "migan_photo.hpp", "migan_photo.hip")] + [
+                                            "migan_metrics.hpp", "migan_metrics.hip", "migan_photo.hpp", "migan_photo.hip",
+                                            "migan_masks.hpp", "migan_masks_host.hpp", "migan_masks.hip")] + [
     os.path.join(ROOT, "include", "migan_hip.h"), os.path.join(ROOT, "include", "comodgan_hip.h"),
     os.path.join(ROOT, "include", "comodgan_samples_hip.h"), os.path.join(ROOT, "include", "migan_pipeline_samples_hip.h"),
     os.path.join(ROOT, "include", "migan_pipeline_patches_hip.h"), os.path.join(ROOT, "include", "migan_pipeline_regions_hip.h"),
     os.path.join(ROOT, "include", "comodgan_fp16_hip.h"), os.path.join(ROOT, "include", "comodgan_fp16_storage_hip.h"),
     os.path.join(ROOT, "include", "comodgan_stages_hip.h"), os.path.join(ROOT, "include", "comodgan_u8_hip.h"),
-    os.path.join(ROOT, "include", "migan_metrics_hip.h"), os.path.join(ROOT, "include", "migan_photo_hip.h")]
+    os.path.join(ROOT, "include", "migan_metrics_hip.h"), os.path.join(ROOT, "include", "migan_photo_hip.h"),
+    os.path.join(ROOT, "include", "migan_masks_hip.h")]
 ARCH = "gfx950"
 # (GEMM variant, activation storage format) slices of the sepconv_kernel table; 16-bit storage is built for the fp16 GEMM variants (f16x2 = 2, f16 = 3)
 SLICES: Sequence[Tuple[int, int]] = ((0, 0), (1, 0), (2, 0), (2, 1), (2, 2), (3, 1), (3, 2))
@@ -59,7 +61,8 @@ def units(extra: Sequence[str] = ()) -> List[Tuple[str, List[str]]]:
            (os.path.join(OBJ, "migan_wide2.o"), [cc, *FLAGS, *extra, "-c", os.path.join(CSRC, "migan_wide2.hip")]),
            (os.path.join(OBJ, "comodgan_u8.o"), [cc, *FLAGS, *extra, "-c", os.path.join(CSRC, "comodgan_u8.hip")]),
            (os.path.join(OBJ, "migan_metrics.o"), [cc, *FLAGS, *extra, "-c", os.path.join(CSRC, "migan_metrics.hip")]),
-           (os.path.join(OBJ, "migan_photo.o"), [cc, *FLAGS, *extra, "-c", os.path.join(CSRC, "migan_photo.hip")])]
+           (os.path.join(OBJ, "migan_photo.o"), [cc, *FLAGS, *extra, "-c", os.path.join(CSRC, "migan_photo.hip")]),
+           (os.path.join(OBJ, "migan_masks.o"), [cc, *FLAGS, *extra, "-c", os.path.join(CSRC, "migan_masks.hip")])]
     for g, s in SLICES:
         out.append((os.path.join(OBJ, f"migan_k_g{g}s{s}.o"),
                     [cc, *FLAGS, *extra, f"-DMIGAN_SLICE_G={g}", f"-DMIGAN_SLICE_S={s}", "-c", os.path.join(CSRC, "migan_k_slice.hip")]))

@@ -9,5 +9,6 @@
 #include "comodgan_kernels.hpp"
 #define MIGAN_METRICS_ELSEWHERE   // the PSNR / SSIM kernels are migan_metrics.hip's
 #define MIGAN_PHOTO_ELSEWHERE     // the photo-loading kernels are migan_photo.hip's
+#define MIGAN_MASKS_ELSEWHERE     // the random-mask kernel is migan_masks.hip's
 #include "migan_host.hpp"
 #include "comodgan_host.hpp"

@@ -24,9 +24,12 @@
 #include "../../include/migan_pipeline_regions_hip.h"
 #include "../../include/migan_metrics_hip.h"
 #include "../../include/migan_photo_hip.h"
+#include "../../include/migan_masks_hip.h"
 #include "migan_table.hpp"
 #include "migan_metrics.hpp"
 #include "migan_photo.hpp"
+#include "migan_masks.hpp"
+#include "migan_masks_host.hpp"
 
 namespace migan {
 
@@ -2606,6 +2609,66 @@ int migan_photo_resize_batch(const migan_photo_item* items, int n, int channels,
     a.flags = flags;
     photo_launch(form.gather[C == 3], "migan::photo_gather_kernel", a, [&](const PhItem& it) { return it.ks_h < 0 ? bytes_tiles(it) : 0; }, 0, stream);
   }
+  MIGAN_API_END
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// include/migan_masks_hip.h: the reference's RandomMask for a numpy seed (draws: migan_masks_host.hpp; kernel: migan_masks.hpp)
+static_assert(sizeof(migan_masks_rng) == sizeof(migan::MkRng) && offsetof(migan_masks_rng, gauss) == offsetof(migan::MkRng, gauss),
+              "migan_masks_rng is MkRng");
+static_assert(MIGAN_MASKS_PLAN_WORDS_MAX == migan::kMkPlanWordsMax && MIGAN_MASKS_BAND == migan::kMkBand, "the header states the kernel's constants");
+
+extern "C" {
+
+int migan_masks_draw(migan_masks_rng* rng, int resolution, double coef, int count, int32_t* plans, size_t capacity_words, size_t* used_words,
+                     migan_masks_rng* states) {
+  MIGAN_API_BEGIN
+  using namespace migan;
+  MIGAN_CHECK(rng != nullptr, MIGAN_EINVAL, "null rng");
+  MIGAN_CHECK(rng->pos >= 0 && rng->pos <= kMkMtN, MIGAN_EINVAL, "the generator's pos must be in 0 .. 624");
+  MIGAN_CHECK(resolution >= kMkResMin && resolution <= kMkResMax, MIGAN_EINVAL,
+              "resolution must be in " + std::to_string(kMkResMin) + " .. " + std::to_string(kMkResMax));
+  MIGAN_CHECK(count >= 1 && count <= kMkCountMax, MIGAN_EINVAL, "count must be in 1 .. " + std::to_string(kMkCountMax));
+  MIGAN_CHECK(std::isfinite(coef) && coef <= 1.0 && (int)(5 * coef) >= 1, MIGAN_EINVAL,
+              "coef = hole_range[0] + hole_range[1] must be at least 0.2 (below, the reference's randint(int(5 * coef)) raises) and at most 1");
+  if (plans != nullptr) {
+    MIGAN_CHECK(used_words != nullptr, MIGAN_EINVAL, "null used_words");
+    MIGAN_CHECK(capacity_words >= (size_t)count + 1 + (size_t)count * kMkPlanWordsMax, MIGAN_EINVAL,
+                "the plan buffer needs count + 1 + count * MIGAN_MASKS_PLAN_WORDS_MAX words");
+  }
+  MkRng g;
+  std::memcpy(&g, rng, sizeof(g));
+  size_t off = (size_t)count + 1;
+  for (int c = 0; c < count; ++c) {
+    if (plans) plans[c] = (int32_t)off;
+    off += (size_t)mk_draw_candidate(g, resolution, coef, plans ? plans + off : nullptr);
+    if (states) std::memcpy(states + c, &g, sizeof(g));
+  }
+  if (plans) {
+    plans[count] = (int32_t)off;
+    *used_words = off;
+  }
+  std::memcpy(rng, &g, sizeof(g));
+  MIGAN_API_END
+}
+
+int migan_masks_raster(const int32_t* plans_dev, size_t words, int count, int resolution, void* out_u8, int32_t* holes, void* stream) {
+  MIGAN_API_BEGIN
+  using namespace migan;
+  MIGAN_CHECK(plans_dev && out_u8 && holes, MIGAN_EINVAL, "null plans_dev, out_u8 or holes");
+  MIGAN_CHECK(resolution >= kMkResMin && resolution <= kMkResMax, MIGAN_EINVAL,
+              "resolution must be in " + std::to_string(kMkResMin) + " .. " + std::to_string(kMkResMax));
+  MIGAN_CHECK(count >= 1 && count <= kMkCountMax, MIGAN_EINVAL, "count must be in 1 .. " + std::to_string(kMkCountMax));
+  MIGAN_CHECK(words >= (size_t)count + 1 && words < ((size_t)1 << 31), MIGAN_EINVAL, "words must be in count + 1 .. 2^31 - 1");
+  MIGAN_CHECK((uintptr_t)plans_dev % 4 == 0 && (uintptr_t)holes % 4 == 0, MIGAN_EINVAL, "plans_dev and holes must be 4-byte aligned");
+  MkArgs a{};
+  a.plans = plans_dev; a.out = (unsigned char*)out_u8; a.holes = holes;
+  a.words = (unsigned)words; a.count = count; a.R = resolution;
+  a.wide = resolution % 16 == 0 && (uintptr_t)out_u8 % 16 == 0;
+  const unsigned grid = (unsigned)count * (unsigned)mk_bands(resolution);      // (at most 65536 * 32)
+  rt_check(rt::launch(masks_form(), a, grid, kMkThreads, (size_t)kMkLdsBytes, (rt::stream_t)stream), "migan::masks_raster_kernel");
   MIGAN_API_END
 }
 

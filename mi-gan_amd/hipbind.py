@@ -104,6 +104,9 @@ METRICS_CHW, METRICS_HWC = 0, 1
 PHOTO_EXPORTS = ("migan_photo_scratch_bytes", "migan_photo_resize_batch")
 PHOTO_NEAREST, PHOTO_BICUBIC = 0, 1
 PHOTO_INVERT, PHOTO_THRESHOLD = 1, 2
+# include/migan_masks_hip.h
+MASKS_EXPORTS = ("migan_masks_draw", "migan_masks_raster")
+MASKS_PLAN_WORDS_MAX, MASKS_BAND = 4958, 32
 
 
 class MetricsItem(C.Structure):
@@ -136,6 +139,26 @@ def photo_items(items):
         a.src_u8, a.dst_u8 = src or None, dst or None
         a.src_height, a.src_width, a.dst_height, a.dst_width = int(sh), int(sw), int(dh), int(dw)
     return arr
+
+
+class MasksRng(C.Structure):
+    """struct migan_masks_rng: RandomState.get_state() without its name"""
+    _fields_ = [("key", C.c_uint32 * 624), ("pos", C.c_int32), ("has_gauss", C.c_int32), ("gauss", C.c_double)]
+
+    @classmethod
+    def from_state(cls, state):
+        """('MT19937', key, pos, has_gauss, cached_gaussian) -> struct"""
+        import numpy as np
+        if state[0] != "MT19937":
+            raise TypeError(f"the generator must be numpy's legacy MT19937 RandomState, got {state[0]!r}")
+        s = cls()
+        C.memmove(s.key, np.ascontiguousarray(state[1], dtype=np.uint32).ctypes.data, 624 * 4)
+        s.pos, s.has_gauss, s.gauss = int(state[2]), int(state[3]), float(state[4])
+        return s
+
+    def to_state(self):
+        import numpy as np
+        return ("MT19937", np.frombuffer(bytes(self.key), dtype=np.uint32).copy(), int(self.pos), int(self.has_gauss), float(self.gauss))
 
 
 class PipelineItem(C.Structure):
@@ -217,7 +240,7 @@ class MiganLib:
             raise MiganError(f"cannot load {self.path}: {e}") from e
         L = self.lib
         for name in (EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + PIPELINE_PATCHES_EXPORTS + PIPELINE_REGIONS_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS
-                     + U8_EXPORTS + METRICS_EXPORTS + PHOTO_EXPORTS):
+                     + U8_EXPORTS + METRICS_EXPORTS + PHOTO_EXPORTS + MASKS_EXPORTS):
             if not hasattr(L, name):
                 raise MiganError(f"{self.path} does not export {name}")
         vp, ci = C.c_void_p, C.c_int
@@ -306,6 +329,8 @@ class MiganLib:
         L.migan_metrics_batch.restype = ci
         L.migan_photo_scratch_bytes.argtypes = [C.POINTER(PhotoItem), ci, ci, ci, C.POINTER(C.c_size_t)]
         L.migan_photo_resize_batch.argtypes = [C.POINTER(PhotoItem), ci, ci, ci, ci, vp, vp]
+        L.migan_masks_draw.argtypes = [C.POINTER(MasksRng), ci, C.c_double, ci, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(MasksRng)]
+        L.migan_masks_raster.argtypes = [vp, C.c_size_t, ci, ci, vp, vp, vp]
         L.migan_last_error.restype = C.c_char_p
         L.migan_last_kernel.restype = C.c_char_p
         L.migan_nan_policy.restype = C.c_char_p
@@ -491,6 +516,19 @@ class MiganLib:
     def photo_resize_batch(self, items, channels: int, filter: int, flags: int, scratch_ptr: int, stream: int = 0) -> None:
         self.check(self.lib.migan_photo_resize_batch(photo_items(items), 0 if items is None else len(items), int(channels), int(filter), int(flags),
                                                      C.c_void_p(scratch_ptr), C.c_void_p(stream)))
+
+    # the reference's RandomMask (include/migan_masks_hip.h).  masks_draw is host code: it needs no device
+    def masks_draw(self, rng: MasksRng, resolution: int, coef: float, count: int, plans_ptr: int = 0, capacity_words: int = 0, states=None) -> int:
+        """draws `count` candidates, advancing `rng` in place; -> the words written to the plan buffer (0 for a null buffer).
+        `states`: a (MasksRng * count)() array that receives the generator behind every candidate"""
+        used = C.c_size_t(0)
+        self.check(self.lib.migan_masks_draw(C.byref(rng) if rng is not None else None, int(resolution), C.c_double(coef), int(count),
+                                             C.c_void_p(plans_ptr or None), int(capacity_words), C.byref(used), states))
+        return int(used.value)
+
+    def masks_raster(self, plans_ptr: int, words: int, count: int, resolution: int, out_ptr: int, holes_ptr: int, stream: int = 0) -> None:
+        self.check(self.lib.migan_masks_raster(C.c_void_p(plans_ptr or None), int(words), int(count), int(resolution), C.c_void_p(out_ptr or None),
+                                               C.c_void_p(holes_ptr or None), C.c_void_p(stream)))
 
     def sepconv_forward(self, stream: int = 0, **kw) -> None:
         d = SepConvDesc()
