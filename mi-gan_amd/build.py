@@ -28,11 +28,13 @@ SOURCES = [os.path.join(CSRC, f) for f in ("migan_hip.hip", "migan_k_slice.hip",
                                             "comodgan_kernels.hpp", "comodgan_conv_body.inc", "comodgan_fir_body.inc", "comodgan_fromrgb_body.inc",
                                             "comodgan_torgb_body.inc", "comodgan_host.hpp", "comodgan_u8.hip", "migan_pipeline.hpp",
                                             "migan_pipeline_pool_body.inc", "migan_pipeline_samples_body.inc", "migan_pipeline_regions.inc",
+                                            "migan_pipeline_region_patches.inc",
                                             "migan_metrics.hpp", "migan_metrics.hip", "migan_photo.hpp", "migan_photo.hip",
                                             "migan_masks.hpp", "migan_masks_host.hpp", "migan_masks.hip")] + [
     os.path.join(ROOT, "include", "migan_hip.h"), os.path.join(ROOT, "include", "comodgan_hip.h"),
     os.path.join(ROOT, "include", "comodgan_samples_hip.h"), os.path.join(ROOT, "include", "migan_pipeline_samples_hip.h"),
     os.path.join(ROOT, "include", "migan_pipeline_patches_hip.h"), os.path.join(ROOT, "include", "migan_pipeline_regions_hip.h"),
+    os.path.join(ROOT, "include", "migan_pipeline_region_patches_hip.h"),
     os.path.join(ROOT, "include", "comodgan_fp16_hip.h"), os.path.join(ROOT, "include", "comodgan_fp16_storage_hip.h"),
     os.path.join(ROOT, "include", "comodgan_stages_hip.h"), os.path.join(ROOT, "include", "comodgan_u8_hip.h"),
     os.path.join(ROOT, "include", "migan_metrics_hip.h"), os.path.join(ROOT, "include", "migan_photo_hip.h"),

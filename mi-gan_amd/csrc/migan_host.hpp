@@ -22,6 +22,7 @@
 #include "../../include/migan_pipeline_samples_hip.h"
 #include "../../include/migan_pipeline_patches_hip.h"
 #include "../../include/migan_pipeline_regions_hip.h"
+#include "../../include/migan_pipeline_region_patches_hip.h"
 #include "../../include/migan_metrics_hip.h"
 #include "../../include/migan_photo_hip.h"
 #include "../../include/migan_masks_hip.h"
@@ -2341,6 +2342,101 @@ int migan_pipeline_regions_post(const migan_pipeline_region_row* rows, int m, in
                             return (unsigned long long)cdiv(it.box[1] - it.box[0], kPostTW) * (unsigned long long)cdiv(it.box[3] - it.box[2], kPostTH);
                           },
                           (size_t)kPostLdsBytes + 16, stream);
+  MIGAN_API_END
+}
+
+// ---- S completions per hole region as patches, and the paste back (include/migan_pipeline_region_patches_hip.h) ----
+// the crop's tiles of a row: the grid of pipe_post_rows_kernel, pipe_post_rows_patches_kernel and pipe_paste_rows_kernel
+static unsigned long long migan_pipeline_box_tiles(const int* box) {
+  return (unsigned long long)migan::cdiv(box[1] - box[0], migan::kPostTW) * (unsigned long long)migan::cdiv(box[3] - box[2], migan::kPostTH);
+}
+// _regions_post for `samples` generator outputs per row, out of place: row r and y rows r * samples ... -> outs[r] =
+// [samples][3][ch][cw].  The box is host data, so a destination that is too small is refused here, before anything is launched
+int migan_pipeline_regions_post_patches(const migan_pipeline_region_row* rows, int m, int samples, int resolution, const void* y_nchw,
+                                        const float* gauss25, void* const* outs, const size_t* out_bytes, void* stream) {
+  MIGAN_API_BEGIN
+  using namespace migan;
+  MIGAN_CHECK(y_nchw, MIGAN_EINVAL, "null tensor");
+  MIGAN_CHECK(samples >= 1, MIGAN_EINVAL, "samples must be at least 1");
+  MIGAN_CHECK(outs != nullptr, MIGAN_EINVAL, "null outs");
+  MIGAN_CHECK(out_bytes != nullptr, MIGAN_EINVAL, "null out_bytes");
+  std::vector<PipeRowItem> its;
+  migan_pipeline_rows_plan(rows, m, resolution, &its);
+  for (int i = 0; i < m; ++i) {
+    MIGAN_CHECK(outs[i] != nullptr, MIGAN_EINVAL, "null destination of row " + std::to_string(i));
+    // ch * cw < 2^30 and samples < 2^31: no overflow in 64 bits
+    const unsigned long long need = (unsigned long long)samples * 3ull * (unsigned long long)(its[i].box[3] - its[i].box[2]) *
+                                    (unsigned long long)(its[i].box[1] - its[i].box[0]);
+    MIGAN_CHECK((unsigned long long)out_bytes[i] >= need, MIGAN_EINVAL,
+                "row " + std::to_string(i) + ": its patches take " + std::to_string(need) + " bytes, the destination has " +
+                    std::to_string((unsigned long long)out_bytes[i]));
+  }
+  PipeRowPatchesArgs proto{};
+  proto.y = (const float*)y_nchw; proto.R = resolution; proto.S = samples;
+  migan_pipeline_gauss(gauss25, proto.gauss);
+  const size_t plane = (size_t)resolution * resolution;
+  for (size_t i0 = 0; i0 < its.size();) {
+    PipeRowPatchesArgs a = proto;
+    unsigned long long total = 0;
+    int k = 0;
+    for (; k < kPipeRowPatchesMax && i0 + k < its.size(); ++k) {
+      const PipeRowItem& it = its[i0 + k];
+      const unsigned long long t = migan_pipeline_box_tiles(it.box);
+      if (k > 0 && total + t > 0x7fffffffull) break;
+      PipeRowPatchesItem& b = a.item[k];
+      b.image = it.image; b.mask = it.mask; b.labels = it.labels; b.out = (unsigned char*)outs[i0 + k];
+      b.H = it.H; b.W = it.W; b.label = it.label;
+      for (int j = 0; j < 4; ++j) b.box[j] = it.box[j];
+      a.first[k] = (int)total;
+      total += t;
+    }
+    a.first[k] = (int)total;
+    a.n = k;
+    a.y += i0 * (size_t)samples * 3 * plane;
+    if (total)
+      rt_check(rt::launch(pipe_post_rows_patches_kernel, a, (unsigned)total, kThreads, (size_t)kPostLdsBytes + 16, (rt::stream_t)stream),
+               "migan::pipe_post_rows_patches_kernel");
+    i0 += (size_t)k;
+  }
+  MIGAN_API_END
+}
+// one sample's patch of every listed row -> its image, where labels == label: a copy
+int migan_pipeline_regions_paste(const migan_pipeline_region_paste_row* rows, int m, void* stream) {
+  MIGAN_API_BEGIN
+  using namespace migan;
+  MIGAN_CHECK(rows != nullptr && m >= 1, MIGAN_EINVAL, "the call needs at least one row");
+  std::vector<PipePasteItem> its((size_t)m);
+  for (int i = 0; i < m; ++i) {
+    const migan_pipeline_region_paste_row& r = rows[i];
+    const std::string who = "row " + std::to_string(i);
+    MIGAN_CHECK(r.image_chw_u8 && r.patch_chw_u8, MIGAN_EINVAL, "null image or patch in " + who);
+    MIGAN_CHECK(r.height >= 3 && r.width >= 3 && (unsigned long long)r.height * r.width < (1ull << 30), MIGAN_EINVAL,
+                who + ": image must be at least 3x3 and below 2^30 pixels");
+    MIGAN_CHECK(r.label >= 0 && r.label <= kRegionsCap, MIGAN_EINVAL, who + ": label must be in 0 ... 64");
+    MIGAN_CHECK(r.label == 0 || r.labels_u8, MIGAN_EINVAL, who + ": a label above 0 needs the label map");
+    MIGAN_CHECK(r.box[0] >= 0 && r.box[1] <= r.width && r.box[2] >= 0 && r.box[3] <= r.height && r.box[1] - r.box[0] >= 3 &&
+                r.box[3] - r.box[2] >= 3, MIGAN_EINVAL, who + ": box = {x_min, x_max, y_min, y_max} must lie inside the image and be at least 3x3");
+    PipePasteItem& b = its[(size_t)i];
+    b.image = (unsigned char*)r.image_chw_u8; b.labels = (const unsigned char*)r.labels_u8; b.patch = (const unsigned char*)r.patch_chw_u8;
+    b.H = r.height; b.W = r.width; b.label = r.label;
+    for (int j = 0; j < 4; ++j) b.box[j] = r.box[j];
+  }
+  for (size_t i0 = 0; i0 < its.size();) {
+    PipePasteArgs a{};
+    unsigned long long total = 0;
+    int k = 0;
+    for (; k < kPipePasteMax && i0 + k < its.size(); ++k) {
+      const unsigned long long t = migan_pipeline_box_tiles(its[i0 + k].box);
+      if (k > 0 && total + t > 0x7fffffffull) break;
+      a.item[k] = its[i0 + k];
+      a.first[k] = (int)total;
+      total += t;
+    }
+    a.first[k] = (int)total;
+    a.n = k;
+    if (total) rt_check(rt::launch(pipe_paste_rows_kernel, a, (unsigned)total, kThreads, 0, (rt::stream_t)stream), "migan::pipe_paste_rows_kernel");
+    i0 += (size_t)k;
+  }
   MIGAN_API_END
 }
 

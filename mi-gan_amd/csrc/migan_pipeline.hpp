@@ -15,7 +15,8 @@
 // _post): 1-D grids, workgroup -> (item, tile) through the prefix table in the argument, no host synchronisation in between.
 // The batch form's post step also exists out of place, for S generator outputs per image: as whole images (PipeSamplesArgs;
 // migan_pipeline_batch_post_samples) and as box-sized patches (PipePatchesArgs; migan_pipeline_batch_post_patches).
-// A fourth form gives every hole region of an image a box of its own (migan_pipeline_regions.inc; migan_pipeline_regions_*).
+// A fourth form gives every hole region of an image a box of its own (migan_pipeline_regions.inc; migan_pipeline_regions_*), in
+// place, or out of place as S box-sized patches per region with a paste step back (migan_pipeline_region_patches.inc).
 #pragma once
 
 #ifndef MIGAN_HOST_DEVICE          // (the CPU emulator build is host code throughout)
@@ -515,6 +516,8 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_post_patches_kernel(const Pip
 
 // ---- one crop per hole region: labelling, a box per region, pre / post over a row table (include/migan_pipeline_regions_hip.h) -----
 #include "migan_pipeline_regions.inc"
+// ---- S completions per hole region as patches, and the paste back (include/migan_pipeline_region_patches_hip.h) ----------------------
+#include "migan_pipeline_region_patches.inc"
 #endif  // MIGAN_TEMPLATE_KERNELS_ONLY
 
 }  // namespace migan

@@ -86,6 +86,8 @@ PIPELINE_PATCHES_EXPORTS = ("migan_pipeline_batch_post_patches",)
 # include/migan_pipeline_regions_hip.h
 PIPELINE_REGIONS_EXPORTS = ("migan_pipeline_regions_scratch_bytes", "migan_pipeline_regions_find", "migan_pipeline_regions_pre",
                             "migan_pipeline_regions_post")
+# include/migan_pipeline_region_patches_hip.h
+PIPELINE_REGION_PATCHES_EXPORTS = ("migan_pipeline_regions_post_patches", "migan_pipeline_regions_paste")
 # include/comodgan_fp16_hip.h
 FP16_EXPORTS = ("comodgan_set_fp16_blocks", "comodgan_get_fp16_blocks")
 # include/comodgan_fp16_storage_hip.h
@@ -195,6 +197,25 @@ def pipeline_region_rows(rows):
     return arr
 
 
+class PipelineRegionPasteRow(C.Structure):
+    """struct migan_pipeline_region_paste_row"""
+    _fields_ = [("image_chw_u8", C.c_void_p), ("labels_u8", C.c_void_p), ("patch_chw_u8", C.c_void_p), ("height", C.c_int), ("width", C.c_int),
+                ("label", C.c_int), ("box", C.c_int * 4)]
+
+
+def pipeline_region_paste_rows(rows):
+    """[(image_ptr, labels_ptr or None, patch_ptr, height, width, label, (x_min, x_max, y_min, y_max)), ...] -> a
+    migan_pipeline_region_paste_row array (None passes a null table through)"""
+    if rows is None:
+        return None
+    arr = (PipelineRegionPasteRow * max(1, len(rows)))()
+    for a, (img, lab, patch, h, w, label, box) in zip(arr, rows):
+        a.image_chw_u8, a.labels_u8, a.patch_chw_u8 = img or None, lab or None, patch or None
+        a.height, a.width, a.label = int(h), int(w), int(label)
+        a.box[:] = [int(v) for v in box]
+    return arr
+
+
 class CoModGANConfig(C.Structure):
     """struct comodgan_config"""
     _fields_ = [(n, C.c_int) for n in ("resolution", "ch_base", "ch_max", "z_dim", "w_dim", "w0_dim", "map_layers", "num_ws")]
@@ -239,7 +260,7 @@ class MiganLib:
         except OSError as e:  # pragma: no cover - depends on the machine
             raise MiganError(f"cannot load {self.path}: {e}") from e
         L = self.lib
-        for name in (EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + PIPELINE_PATCHES_EXPORTS + PIPELINE_REGIONS_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS
+        for name in (EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + PIPELINE_PATCHES_EXPORTS + PIPELINE_REGIONS_EXPORTS + PIPELINE_REGION_PATCHES_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS
                      + U8_EXPORTS + METRICS_EXPORTS + PHOTO_EXPORTS + MASKS_EXPORTS):
             if not hasattr(L, name):
                 raise MiganError(f"{self.path} does not export {name}")
@@ -270,6 +291,9 @@ class MiganLib:
         L.migan_pipeline_regions_find.argtypes = [C.POINTER(PipelineItem), ci, ci, ci, ci, ci, C.POINTER(vp), vp, vp, vp, vp]
         L.migan_pipeline_regions_pre.argtypes = [C.POINTER(PipelineRegionRow), ci, ci, vp, vp]
         L.migan_pipeline_regions_post.argtypes = [C.POINTER(PipelineRegionRow), ci, ci, vp, C.POINTER(C.c_float), vp]
+        L.migan_pipeline_regions_post_patches.argtypes = [C.POINTER(PipelineRegionRow), ci, ci, ci, vp, C.POINTER(C.c_float), C.POINTER(vp),
+                                                          C.POINTER(C.c_size_t), vp]
+        L.migan_pipeline_regions_paste.argtypes = [C.POINTER(PipelineRegionPasteRow), ci, vp]
         L.migan_num_weights.argtypes = [vp, C.POINTER(ci)]
         L.migan_weight_info.argtypes = [vp, ci, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(ci), C.POINTER(ci)]
         L.migan_set_weight.argtypes = [vp, C.c_char_p, vp, C.POINTER(C.c_int64), ci]
@@ -341,7 +365,7 @@ class MiganLib:
         if not allow_test_backend and L.migan_backend().decode() != PRODUCT_BACKEND:
             raise MiganError(f"{self.path} reports backend {L.migan_backend().decode()!r}, not {PRODUCT_BACKEND!r}: only the gfx950 HIP "
                              f"library is a product backend (the CPU emulator build is test infrastructure)")
-        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + PIPELINE_PATCHES_EXPORTS + PIPELINE_REGIONS_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS + U8_EXPORTS:
+        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + PIPELINE_PATCHES_EXPORTS + PIPELINE_REGIONS_EXPORTS + PIPELINE_REGION_PATCHES_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS + U8_EXPORTS:
             if name not in ("migan_last_error", "migan_last_kernel", "migan_nan_policy", "migan_backend", "migan_gemm_variant", "migan_tuning_key"):
                 getattr(L, name).restype = ci
 
@@ -492,6 +516,29 @@ class MiganLib:
         g = None if gauss25 is None else (C.c_float * 25)(*[float(v) for v in gauss25])
         self.check(self.lib.migan_pipeline_regions_post(pipeline_region_rows(rows), 0 if rows is None else len(rows), int(resolution),
                                                         C.c_void_p(y_ptr), g, C.c_void_p(stream)))
+
+    # S completions per hole region as patches, and the paste back (include/migan_pipeline_region_patches_hip.h)
+    def pipeline_regions_post_patches(self, rows, samples: int, resolution: int, y_ptr: int, out_ptrs, out_bytes, gauss25=None,
+                                      stream: int = 0) -> None:
+        """rows as for pipeline_regions_post (the images are only read); y [len(rows) * samples, 3, R, R], row r * samples + s = sample s
+        of rows[r] -> out_ptrs[r] = [samples, 3, ch_r, cw_r] uint8, the box of row r: the blended bytes where labels == label, the
+        image's elsewhere; out_bytes[r] = the capacity of out_ptrs[r] in bytes (too small: ValueError, nothing launched).  One entry
+        of each per row (None passes a null table through)"""
+        g = None if gauss25 is None else (C.c_float * 25)(*[float(v) for v in gauss25])
+        n = 0 if rows is None else len(rows)
+        outs = None if out_ptrs is None else (C.c_void_p * max(1, len(out_ptrs)))(*[p or None for p in out_ptrs])
+        caps = None if out_bytes is None else (C.c_size_t * max(1, len(out_bytes)))(*[int(b) for b in out_bytes])
+        for what, table in (("destination", out_ptrs), ("capacity", out_bytes)):
+            if table is not None and len(table) != n:
+                raise ValueError(f"expected one {what} per row, got {len(table)} for {n} rows")
+        self.check(self.lib.migan_pipeline_regions_post_patches(pipeline_region_rows(rows), n, int(samples), int(resolution),
+                                                                C.c_void_p(y_ptr), g, outs, caps, C.c_void_p(stream)))
+
+    def pipeline_regions_paste(self, rows, stream: int = 0) -> None:
+        """rows = [(image_ptr, labels_ptr or None, patch_ptr, height, width, label, box), ...]: patch_ptr -> ONE sample [3, ch, cw] of the
+        row's patches; it is copied into the image where labels == label (label 0: the whole box)"""
+        self.check(self.lib.migan_pipeline_regions_paste(pipeline_region_paste_rows(rows), 0 if rows is None else len(rows),
+                                                         C.c_void_p(stream)))
 
     # PSNR / SSIM of completions against the photo (include/migan_metrics_hip.h): `items` = [(gt_ptr, pred_ptr, mask_ptr or None, H, W), ...]
     def metrics_scratch_bytes(self, items, samples: int) -> int:

@@ -4,6 +4,7 @@ C ABI (``migan_pack_input`` / ``migan_compose_output``).  Like the generator the
 from __future__ import annotations
 
 import math
+import numbers
 
 import torch
 
@@ -67,7 +68,11 @@ class MIGAN_Pipeline(torch.nn.Module):
     (``migan_pipeline_batch_post_patches``): the pixels outside a box are the photo's in every completion.
 
     ``forward_regions(images, masks)`` is ``forward_batch`` with one crop per hole region instead of one per image: a photo with
-    several marked objects far apart gets each of them completed at its own scale (``migan_pipeline_regions_find / _pre / _post``)."""
+    several marked objects far apart gets each of them completed at its own scale (``migan_pipeline_regions_find / _pre / _post``).
+
+    ``forward_region_patches(images, masks, z)`` joins the two: S completions per hole region, returned as box-sized patches, with the
+    photos left as they are; ``paste_patches`` writes the chosen completion of every region into its photo
+    (``migan_pipeline_regions_post_patches / _paste``)."""
 
     def __init__(self, model_path, resolution: int, padding: int = 128, device="cuda"):
         super().__init__()
@@ -388,43 +393,13 @@ class MIGAN_Pipeline(torch.nn.Module):
             raise RuntimeError(f"expected as many masks as images and at least one, got {len(images)} images and {len(masks)} masks")
         if int(max_batch) < 1:
             raise RuntimeError(f"max_batch must be at least 1, got {max_batch}")
-        gap = max(2, self.padding // 4) if gap is None else int(gap)
-        max_regions, max_batch = int(max_regions), int(max_batch)
-        if not 2 <= gap <= 64:
-            raise ValueError(f"gap must be in 2 ... 64, got {gap}")
-        if not 1 <= max_regions <= 64:
-            raise ValueError(f"max_regions must be in 1 ... 64, got {max_regions}")
+        gap, max_regions, max_batch = *self._regions_args(gap, max_regions), int(max_batch)
         items, device = self._batch_items(images, masks)
         lib = load_library()
-        n, cap, res = len(items), max_regions + 1, self.res
+        res = self.res
         with torch.cuda.device(device):                          # the handle-free entry points launch on the CURRENT device
             stream = int(torch.cuda.current_stream(device).cuda_stream)
-            table = [it[:6] for it in items]
-            scratch = self._scratch_bytes(lib.pipeline_regions_scratch_bytes(table, gap, max_regions), device)
-            labels = [torch.empty((it[2], it[3]), dtype=torch.uint8, device=device) for it in items]
-            found = torch.empty(n + n * cap * 4, dtype=torch.int32, device=device)       # the counts, then the boxes: one copy
-            count, boxes = found[:n], found[n:]
-            lib.pipeline_regions_find(table, res, self.padding, gap, max_regions, [t.data_ptr() for t in labels], count.data_ptr(),
-                                      boxes.data_ptr(), scratch.data_ptr(), stream)
-            host = found.cpu()                                   # (waits for the labelling: the synchronisation of this mode)
-            counts, host_boxes = host[:n].tolist(), host[n:].view(n, cap, 4)
-            full, rows, used = [], [], []
-            for i, it in enumerate(items):
-                mask = it[6]
-                if (it[4], it[5]) != (it[2], it[3]):             # the rows take the mask at the image's size (:256)
-                    mask = torch.empty((it[2], it[3]), dtype=torch.uint8, device=device)
-                    lib.pipeline_mask_resize(it[1], it[4], it[5], mask.data_ptr(), it[2], it[3], stream)
-                full.append(mask)
-                k, box = counts[i], host_boxes[i]
-                single = box[0].tolist()
-                if k == 0:
-                    mine = []
-                elif k < 2 or k > max_regions or (single[1] - single[0] <= res and single[3] - single[2] <= res):
-                    mine = [(0, single)]
-                else:
-                    mine = [(r, box[r].tolist()) for r in range(1, k + 1)]
-                rows += [(it[0], mask.data_ptr(), labels[i].data_ptr(), it[2], it[3], label, b) for label, b in mine]
-                used.append(torch.tensor([b for _, b in mine], dtype=torch.int32).view(len(mine), 4))
+            rows, _, used, labels, full = self._regions_rows(lib, items, device, stream, gap, max_regions)      # (`full` keeps the rows' masks alive)
             if rows:
                 # forward_batch's rule for a lone last chunk: it runs at batch 2 (its x twice), so no row sees a batch-1 forward
                 lone = len(rows) % max_batch == 1 and len(rows) > 1 and max_batch > 1
@@ -437,3 +412,178 @@ class MIGAN_Pipeline(torch.nn.Module):
                     y = self.model(x[r0:r0 + len(chunk) + (1 if lone and len(chunk) == 1 else 0)]).contiguous()
                     lib.pipeline_regions_post(chunk, res, y.data_ptr(), gauss25=self._gauss, stream=stream)
         return (images, used, labels) if return_regions else images
+
+    def _regions_args(self, gap, max_regions):
+        """the checks of ``gap`` and ``max_regions`` forward_regions and forward_region_patches share -> gap, max_regions"""
+        gap = max(2, self.padding // 4) if gap is None else int(gap)
+        max_regions = int(max_regions)
+        if not 2 <= gap <= 64:
+            raise ValueError(f"gap must be in 2 ... 64, got {gap}")
+        if not 1 <= max_regions <= 64:
+            raise ValueError(f"max_regions must be in 1 ... 64, got {max_regions}")
+        return gap, max_regions
+
+    def _regions_rows(self, lib, items, device, stream, gap, max_regions):
+        """What forward_regions and forward_region_patches share, on the current device: ``migan_pipeline_regions_find`` for all images ->
+        ONE copy of the counts and boxes to the host (the host synchronisation) -> the "when not to split" rule.  Returns the rows of
+        all images in one list, (image ptr, mask ptr, labels ptr, H, W, label, box), the image every row belongs to, per image the
+        int32 CPU tensor [rows_i, 4] of its boxes, the label maps, and the masks at the images' sizes (the rows hold their addresses:
+        they must stay alive until the kernels that read them are queued)."""
+        n, cap, res = len(items), max_regions + 1, self.res
+        table = [it[:6] for it in items]
+        scratch = self._scratch_bytes(lib.pipeline_regions_scratch_bytes(table, gap, max_regions), device)
+        labels = [torch.empty((it[2], it[3]), dtype=torch.uint8, device=device) for it in items]
+        found = torch.empty(n + n * cap * 4, dtype=torch.int32, device=device)       # the counts, then the boxes: one copy
+        count, boxes = found[:n], found[n:]
+        lib.pipeline_regions_find(table, res, self.padding, gap, max_regions, [t.data_ptr() for t in labels], count.data_ptr(),
+                                  boxes.data_ptr(), scratch.data_ptr(), stream)
+        host = found.cpu()                                   # (waits for the labelling: the synchronisation of this mode)
+        counts, host_boxes = host[:n].tolist(), host[n:].view(n, cap, 4)
+        full, rows, owner, used = [], [], [], []
+        for i, it in enumerate(items):
+            mask = it[6]
+            if (it[4], it[5]) != (it[2], it[3]):             # the rows take the mask at the image's size (:256)
+                mask = torch.empty((it[2], it[3]), dtype=torch.uint8, device=device)
+                lib.pipeline_mask_resize(it[1], it[4], it[5], mask.data_ptr(), it[2], it[3], stream)
+            full.append(mask)
+            k, box = counts[i], host_boxes[i]
+            single = box[0].tolist()
+            if k == 0:
+                mine = []
+            elif k < 2 or k > max_regions or (single[1] - single[0] <= res and single[3] - single[2] <= res):
+                mine = [(0, single)]
+            else:
+                mine = [(r, box[r].tolist()) for r in range(1, k + 1)]
+            rows += [(it[0], mask.data_ptr(), labels[i].data_ptr(), it[2], it[3], label, b) for label, b in mine]
+            owner += [i] * len(mine)
+            used.append(torch.tensor([b for _, b in mine], dtype=torch.int32).view(len(mine), 4))
+        return rows, owner, used, labels, full
+
+    @torch.no_grad()
+    def forward_region_patches(self, images, masks, z=None, samples=None, *, gap=None, max_regions: int = 8, max_rows: int = 32,
+                               **model_kwargs):
+        """S completions PER HOLE REGION, as box-sized patches: ``forward_regions``' crops (one per region) with ``forward_patches``'
+        sample axis, written out of place -> ``(patches, boxes, labels)``.  An object-removal front end offers the S candidates of
+        every object and lets the user pick one per object; ``paste_patches`` then writes the picks into the photo.
+
+          patches[i]  a list with one uint8 [S, 3, ch, cw] device tensor per row of image i (views of one allocation per chunk);
+                      empty for an image without a hole pixel
+          boxes[i]    the int32 CPU tensor [rows_i, 4] of {x_min, x_max, y_min, y_max} rows ``forward_regions(return_regions=True)``
+                      gives
+          labels[i]   the uint8 [H_i, W_i] label map on the device (unspecified for an image with more than ``max_regions`` regions)
+
+        The label of row j of image i is ``j + 1`` when the image has two or more rows (it was split: row j is region j + 1 of the
+        label map) and 0 when it has one (a single-box row: no label test).  Inside its box, sample s of a row holds, where the label
+        map equals the row's label, the bytes ``forward_regions`` would store there for that generator output, and the photo's bytes
+        everywhere else -- also where the box covers a part of ANOTHER region: every patch is an opaque crop of the photo with one
+        region completed.  Images and masks are only read.
+
+        ``z``, ``samples``, ``max_rows`` and ``model_kwargs`` are ``forward_patches``' (checks and error types included), ``gap`` and
+        ``max_regions`` ``forward_regions``'; region finding, the "when not to split" rule and the row list are ``forward_regions``'.
+        Row j of image i uses the latents z[i] ([N, S, z_dim]): sample s of every region of a photo shares the photo's latent s.
+
+        Per call: ``migan_pipeline_regions_find`` -> ONE HOST SYNCHRONISATION (counts and boxes) -> the rows.  A model with
+        ``forward_samples`` then runs chunks of ``max_rows // S`` rows: ``migan_pipeline_regions_pre`` of the chunk ->
+        ``model.forward_samples(x_rows, z_rows, **model_kwargs)`` -> ``migan_pipeline_regions_post_patches``.  Any other model (the
+        MI-GAN generator, S = 1) runs ``self.model(x)`` on ``forward_regions``' chunks: ``max_rows`` rows, a lone last chunk at batch
+        2, so ``paste_patches(copies, patches, boxes, labels, 0)`` leaves ``forward_regions``' bytes.  The photos are not written, so
+        the network input is formed per chunk (``forward_regions`` holds the input of all rows at once)."""
+        images, masks = list(images), list(masks)
+        items, device, sampler, s, per_chunk, z = self._samples_plan(images, masks, z, samples, max_rows, model_kwargs)
+        gap, max_regions = self._regions_args(gap, max_regions)
+        lib = load_library()
+        res = self.res
+        patches = [[] for _ in items]
+        with torch.cuda.device(device):                          # the handle-free entry points launch on the CURRENT device
+            stream = int(torch.cuda.current_stream(device).cuda_stream)
+            rows, owner, used, labels, full = self._regions_rows(lib, items, device, stream, gap, max_regions)
+            # (without a sampler: forward_regions' rule for a lone last chunk, so that the bytes are forward_regions')
+            lone = sampler is None and len(rows) % per_chunk == 1 and len(rows) > 1 and per_chunk > 1
+            for r0 in range(0, len(rows), per_chunk):
+                chunk = rows[r0:r0 + per_chunk]
+                pad = 1 if lone and len(chunk) == 1 else 0
+                x = torch.empty((len(chunk) + pad, 4, res, res), dtype=torch.float32, device=device)
+                lib.pipeline_regions_pre(chunk, res, x.data_ptr(), stream)
+                if pad:
+                    x[1].copy_(x[0])
+                z_rows = None if z is None else z[torch.tensor(owner[r0:r0 + len(chunk)], device=device)]
+                y = self._samples_generate(x, len(chunk), sampler, z_rows, s, model_kwargs)
+                shapes = [(row[6][3] - row[6][2], row[6][1] - row[6][0]) for row in chunk]
+                sizes = [s * 3 * h * w for h, w in shapes]
+                flat = torch.empty(sum(sizes), dtype=torch.uint8, device=device)   # exactly the chunk's patches; the lists hold views
+                at = 0
+                outs = []
+                for (h, w), size in zip(shapes, sizes):
+                    outs.append(flat[at:at + size].view(s, 3, h, w))
+                    at += size
+                lib.pipeline_regions_post_patches(chunk, s, res, y.data_ptr(), [o.data_ptr() for o in outs], sizes, gauss25=self._gauss,
+                                                  stream=stream)
+                for i, o in zip(owner[r0:r0 + len(chunk)], outs):
+                    patches[i].append(o)
+            del full                                             # (the resized masks lived until their readers were queued)
+        return patches, used, labels
+
+    @torch.no_grad()
+    def paste_patches(self, images, patches, boxes, labels, choice):
+        """The inverse step of ``forward_region_patches``: writes the chosen sample of every region into its photo, IN PLACE, and returns
+        ``images``.  ``patches``, ``boxes``, ``labels`` are what ``forward_region_patches`` returned for these photos (or copies of
+        them).  ``choice`` is one int for all rows, or per image a sequence with one entry per row (or one int for the image);
+        ``None`` or -1 leaves that region untouched.
+
+        Only the pixels of the row's own label are written (``migan_pipeline_regions_paste``; the whole box for the single row of an
+        image that was not split), so the overlapping boxes of neighbouring regions do not disturb each other and the rows may be
+        pasted in any order, or in several calls.  ``ValueError``: a patch whose shape is not [S, 3, ch, cw] of its box, a choice
+        outside -1 ... S - 1, lists of the wrong length."""
+        images, patches, boxes, labels = list(images), list(patches), list(boxes), list(labels)
+        n = len(images)
+        if not images or not (len(patches) == len(boxes) == len(labels) == n):
+            raise ValueError(f"expected patches, boxes and labels for each of the {n} images and at least one image, got "
+                             f"{len(patches)}, {len(boxes)} and {len(labels)}")
+        if choice is None or isinstance(choice, numbers.Integral):
+            choice = [choice] * n
+        choice = list(choice)
+        if len(choice) != n:
+            raise ValueError(f"expected one choice, or one entry of choices per image ({n}), got {len(choice)}")
+        rows, device = [], None
+        for i, (image, mine, box, lab) in enumerate(zip(images, patches, boxes, labels)):
+            if not (image.is_cuda and lab.is_cuda):
+                raise RuntimeError("mi-gan_amd.pipeline needs tensors on an MI355X (HIP) device; there is no CPU path")
+            if image.dtype != torch.uint8 or lab.dtype != torch.uint8:
+                raise RuntimeError("image and label map must be uint8")
+            if not ((image.dim() == 4 and image.shape[0] == 1 and image.shape[1] == 3) or (image.dim() == 3 and image.shape[0] == 3)) \
+                    or not image.is_contiguous():
+                raise RuntimeError(f"expected a contiguous image (1, 3, H, W), got {list(image.shape)}")
+            device = image.device if device is None else device
+            if image.device != device or lab.device != device:
+                raise RuntimeError("images, patches and label maps must be on the same device")
+            h, w = int(image.shape[-2]), int(image.shape[-1])
+            mine = list(mine)
+            box = torch.as_tensor(box).reshape(-1, 4).tolist()
+            if len(mine) != len(box):
+                raise ValueError(f"image {i}: {len(mine)} patches for {len(box)} boxes")
+            if tuple(lab.shape) != (h, w) or not lab.is_contiguous():
+                raise ValueError(f"image {i}: expected a contiguous label map [{h}, {w}], got {list(lab.shape)}")
+            picks = choice[i]
+            if picks is None or isinstance(picks, numbers.Integral):
+                picks = [picks] * len(mine)
+            picks = list(picks)
+            if len(picks) != len(mine):
+                raise ValueError(f"image {i}: {len(picks)} choices for {len(mine)} rows")
+            for j, (patch, (x0, x1, y0, y1), pick) in enumerate(zip(mine, box, picks)):
+                if patch.dim() != 4 or tuple(patch.shape[1:]) != (3, y1 - y0, x1 - x0) or patch.shape[0] < 1:
+                    raise ValueError(f"image {i} row {j}: expected patches [S, 3, {y1 - y0}, {x1 - x0}] for box {[x0, x1, y0, y1]}, got {list(patch.shape)}")
+                if patch.dtype != torch.uint8 or not patch.is_contiguous():
+                    raise ValueError(f"image {i} row {j}: patches must be contiguous uint8")
+                if not patch.is_cuda or patch.device != device:
+                    raise RuntimeError("images, patches and label maps must be on the same device")
+                pick = -1 if pick is None else int(pick)
+                if not -1 <= pick < patch.shape[0]:
+                    raise ValueError(f"image {i} row {j}: choice {pick} is outside -1 ... {patch.shape[0] - 1}")
+                if pick < 0:
+                    continue
+                rows.append((image.data_ptr(), lab.data_ptr(), patch.data_ptr() + pick * 3 * (y1 - y0) * (x1 - x0), h, w,
+                             j + 1 if len(mine) >= 2 else 0, (x0, x1, y0, y1)))
+        if rows:
+            with torch.cuda.device(device):                      # the handle-free entry points launch on the CURRENT device
+                load_library().pipeline_regions_paste(rows, int(torch.cuda.current_stream(device).cuda_stream))
+        return images
