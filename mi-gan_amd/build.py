@@ -38,7 +38,7 @@ SOURCES = [os.path.join(CSRC, f) for f in ("migan_hip.hip", "migan_k_slice.hip",
     os.path.join(ROOT, "include", "comodgan_fp16_hip.h"), os.path.join(ROOT, "include", "comodgan_fp16_storage_hip.h"),
     os.path.join(ROOT, "include", "comodgan_stages_hip.h"), os.path.join(ROOT, "include", "comodgan_u8_hip.h"),
     os.path.join(ROOT, "include", "migan_metrics_hip.h"), os.path.join(ROOT, "include", "migan_photo_hip.h"),
-    os.path.join(ROOT, "include", "migan_masks_hip.h")]
+    os.path.join(ROOT, "include", "migan_masks_hip.h"), os.path.join(ROOT, "include", "migan_noise_samples_hip.h")]
 ARCH = "gfx950"
 # (GEMM variant, activation storage format) slices of the sepconv_kernel table; 16-bit storage is built for the fp16 GEMM variants (f16x2 = 2, f16 = 3)
 SLICES: Sequence[Tuple[int, int]] = ((0, 0), (1, 0), (2, 0), (2, 1), (2, 2), (3, 1), (3, 2))
@@ -58,9 +58,12 @@ def hipcc() -> str:
 def units(extra: Sequence[str] = ()) -> List[Tuple[str, List[str]]]:
     """(object file, command) per translation unit"""
     cc = hipcc()
+    # (the persistent kernels twice: the forms migan_forward launches, and their per-row forms in units of their own -- migan_pipe_table.inc)
     out = [(os.path.join(OBJ, "migan_hip.o"), [cc, *FLAGS, *extra, "-c", os.path.join(CSRC, "migan_hip.hip")]),
-           (os.path.join(OBJ, "migan_pipe.o"), [cc, *FLAGS, *extra, "-c", os.path.join(CSRC, "migan_pipe.hip")]),
-           (os.path.join(OBJ, "migan_wide2.o"), [cc, *FLAGS, *extra, "-c", os.path.join(CSRC, "migan_wide2.hip")]),
+           (os.path.join(OBJ, "migan_pipe.o"), [cc, *FLAGS, *extra, "-DMIGAN_ROWS_UNIT=0", "-c", os.path.join(CSRC, "migan_pipe.hip")]),
+           (os.path.join(OBJ, "migan_pipe_rows.o"), [cc, *FLAGS, *extra, "-DMIGAN_ROWS_UNIT=1", "-c", os.path.join(CSRC, "migan_pipe.hip")]),
+           (os.path.join(OBJ, "migan_wide2.o"), [cc, *FLAGS, *extra, "-DMIGAN_ROWS_UNIT=0", "-c", os.path.join(CSRC, "migan_wide2.hip")]),
+           (os.path.join(OBJ, "migan_wide2_rows.o"), [cc, *FLAGS, *extra, "-DMIGAN_ROWS_UNIT=1", "-c", os.path.join(CSRC, "migan_wide2.hip")]),
            (os.path.join(OBJ, "comodgan_u8.o"), [cc, *FLAGS, *extra, "-c", os.path.join(CSRC, "comodgan_u8.hip")]),
            (os.path.join(OBJ, "migan_metrics.o"), [cc, *FLAGS, *extra, "-c", os.path.join(CSRC, "migan_metrics.hip")]),
            (os.path.join(OBJ, "migan_photo.o"), [cc, *FLAGS, *extra, "-c", os.path.join(CSRC, "migan_photo.hip")]),

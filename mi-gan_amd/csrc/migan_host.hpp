@@ -26,6 +26,7 @@
 #include "../../include/migan_metrics_hip.h"
 #include "../../include/migan_photo_hip.h"
 #include "../../include/migan_masks_hip.h"
+#include "../../include/migan_noise_samples_hip.h"
 #include "migan_table.hpp"
 #include "migan_metrics.hpp"
 #include "migan_photo.hpp"
@@ -363,10 +364,11 @@ constexpr size_t kLds96 = 96 * 1024, kLds160 = 160 * 1024;
 // sepconv_wide_kernel<TORGB, STV, X1, BALL, DMA, UP>: x1 = GEMM variant "f16" (one fp16 piece per operand; 16-bit storage only: its fp32-storage
 // rows are never picked); ball = waves 4-7 run all the MFMAs (tuning().wide >= 2); dma = LDS-DMA staging (tuning().wide == 3, fp32 storage);
 // up = the FIR-up layer on the same tile
-struct WideEntry { bool torgb; int stv; bool x1, ball, dma, up; SepKernelFn fn; const char* name; size_t max_lds; };
+struct WideEntry { bool torgb; int stv; bool x1, ball, dma, up; SepKernelFn fn; const char* name; size_t max_lds; SepRowKernelFn rows_fn; const char* rows_name; };
 #define MIGAN_W(T, S, X, B, D, U)                                                                                                 \
   {T, S, X, B, D, U, sepconv_wide_kernel<T, S, X, B, D, U>, "migan::sepconv_wide_kernel<" #T ", " #S ", " #X ", " #B ", " #D ", " #U ">", \
-   (X && S == 0) ? 0 : kLds160}
+   (X && S == 0) ? 0 : kLds160, (X && S == 0) ? nullptr : sepconv_wide_rows_kernel<T, S, X, B, D, U>,                              \
+   "migan::sepconv_wide_rows_kernel<" #T ", " #S ", " #X ", " #B ", " #D ", " #U ">"}
 #define MIGAN_W3(T, X, B) MIGAN_W(T, 0, X, B, false, false), MIGAN_W(T, 1, X, B, false, false), MIGAN_W(T, 2, X, B, false, false)
 inline const std::vector<WideEntry>& wide_table() {
   static const std::vector<WideEntry> t = {
@@ -442,8 +444,9 @@ inline const DownEntry* pick_pipedown(int cin, int cout, int h_in, int w_in, int
 // Its pointwise form (variant 3) serves the second half of a down=2 layer that is not fused (Cout = 512: encoder.b128 / b64 .conv2 of migan-512):
 // the 128-column pointwise tiles re-read their A operand per column chunk (measured traffic 1.70x algorithmic), this one reads it once per 256.
 SepKernelFn wide2_fn(int variant);
-struct Wide2Entry { int variant; SepKernelFn fn; const char* name; size_t max_lds; };
-#define MIGAN_W2(V) {V, wide2_fn(V), "migan::sepconv_wide2_kernel<" #V ">", kLds160}
+SepRowKernelFn wide2_rows_fn(int variant);      // (null: the pointwise form)
+struct Wide2Entry { int variant; SepKernelFn fn; const char* name; size_t max_lds; SepRowKernelFn rows_fn; const char* rows_name; };
+#define MIGAN_W2(V) {V, wide2_fn(V), "migan::sepconv_wide2_kernel<" #V ">", kLds160, wide2_rows_fn(V), "migan::sepconv_wide2_rows_kernel<" #V ">"}
 inline const std::vector<Wide2Entry>& wide2_table() {
   static const std::vector<Wide2Entry> t = {MIGAN_W2(0), MIGAN_W2(1), MIGAN_W2(3)};
   return t;
@@ -564,13 +567,26 @@ inline void prepare_kernels() {
   const auto raise = [](const void* fn, size_t bytes) {
     if (bytes) rt_check(rt::allow_dynamic_lds(fn, bytes), "hipFuncSetAttribute");
   };
-  for (const auto& e : kernel_table()) raise((const void*)e.fn, kLds96);
+  // (the per-row form of a row, where it has one, takes the same LDS)
+  for (const auto& e : kernel_table()) {
+    raise((const void*)e.fn, kLds96);
+    if (e.rows_fn) raise((const void*)e.rows_fn, kLds96);
+  }
   const PipeSlice ps = pipe_slice();
-  for (int i = 0; i < ps.n; ++i) raise((const void*)ps.entries[i].fn, kLds160);
+  for (int i = 0; i < ps.n; ++i) {
+    raise((const void*)ps.entries[i].fn, kLds160);
+    if (ps.entries[i].rows_fn) raise((const void*)ps.entries[i].rows_fn, kLds160);
+  }
   const DownSlice ds = pipedown_slice();
   for (int i = 0; i < ds.n; ++i) raise((const void*)ds.entries[i].fn, kLds160);
-  for (const auto& e : wide_table()) raise((const void*)e.fn, e.max_lds);
-  for (const auto& e : wide2_table()) raise((const void*)e.fn, e.max_lds);
+  for (const auto& e : wide_table()) {
+    raise((const void*)e.fn, e.max_lds);
+    if (e.rows_fn) raise((const void*)e.rows_fn, e.max_lds);
+  }
+  for (const auto& e : wide2_table()) {
+    raise((const void*)e.fn, e.max_lds);
+    if (e.rows_fn) raise((const void*)e.rows_fn, e.max_lds);
+  }
   for (const auto& e : dwfir_table()) raise((const void*)e.fn, e.max_lds);
   for (const auto& e : torgb_table()) raise((const void*)e.fn, e.max_lds);
   for (const auto& e : narrow_table()) raise((const void*)e.fn, e.max_lds);
@@ -624,7 +640,14 @@ struct LayerPtrs {
   const float *frgb_w = nullptr, *frgb_b = nullptr, *trgb_w = nullptr, *trgb_b = nullptr, *img_prev = nullptr;
   float* img_out = nullptr;
   const migan_io_u8 *u8_in = nullptr, *u8_out = nullptr;      // migan_forward_u8, where x is the network's input / img_out its output
+  int samples = 0;      // > 0: the per-row form of the kernel (SepRowArgs): row b's noise plane at noise + b * noise_stride, skip = [batch / samples]...
+  unsigned noise_stride = 0;
 };
+// The limits the per-row kernels state, refused by the host beyond them.  rows_image_of is exact for row counts below 2^20: its argument is at
+// most samples - 1 plus the rows of a tile (8 at the most).  A multi-image tile forms (row in tile) * noise_stride + pixel in 32 bits, signed
+// where it is kept in a register across the K loop: 8 * 2^27 + a plane stays below 2^31.
+constexpr int kMaxRowSamples = (1 << 20) - 64;
+constexpr size_t kMaxRowNoiseStride = (size_t)1 << 27;
 
 inline unsigned tiles_of(const Geo& g, int batch) {
   return (unsigned)(g.tiles_x * g.tiles_y * cdiv(batch, 1 << g.lgIMGS) * g.nchunks);
@@ -666,14 +689,22 @@ struct Resolved {
   LaunchKind kind = K_NONE;
   union { SepKernelFn sep; DwFirKernelFn dw; RgbKernelFn rgb; } fn{};
   const char* name = "";
+  SepRowKernelFn rows_fn = nullptr; const char* rows_name = "";      // K_SEP: the per-row form of fn (LayerPtrs::samples), null where the family has none
   unsigned grid = 0, threads = 0; size_t lds_bytes = 0;
   bool whole_down = false;           // sepconv_pipedown_kernel: the whole down=2 layer, reading the LAYER's input (no dwfir scratch)
   bool drop_y = false;               // the fused ToRGB tail runs without writing the feature map: y = nullptr
   union { SepArgs sep; DwFirArgs dw; RgbArgs rgb; } args{};      // shape and geometry; every pointer null
 };
 inline Resolved sep_launch(SepKernelFn fn, const char* name, unsigned grid, unsigned threads, size_t lds_bytes, const SepArgs& a) {
-  Resolved r;
+  Resolved r;      // (a family without a per-row form: the narrow layers, the fused down=2 layer)
   r.kind = K_SEP; r.fn.sep = fn; r.name = name; r.grid = grid; r.threads = threads; r.lds_bytes = lds_bytes; r.args.sep = a;
+  return r;
+}
+template <class Entry>      // a row of a kernel family's table: fn, name, rows_fn, rows_name
+inline Resolved sep_launch(const Entry& e, unsigned grid, unsigned threads, size_t lds_bytes, const SepArgs& a) {
+  Resolved r;
+  r.kind = K_SEP; r.fn.sep = e.fn; r.name = e.name; r.rows_fn = e.rows_fn; r.rows_name = e.rows_name;
+  r.grid = grid; r.threads = threads; r.lds_bytes = lds_bytes; r.args.sep = a;
   return r;
 }
 
@@ -686,14 +717,14 @@ inline Resolved sep_launch(SepKernelFn fn, const char* name, unsigned grid, unsi
 inline Resolved resolve_sepconv(Geo g, const SepArgs& a, const LayerDesc& d, bool fused_rgb, int nd) {
   const unsigned pipe_grid = (unsigned)tuning().pipe_grid;
   if (const PipeEntry* pe = pick_pipe(g, a.CI, a.CO, nd, fused_rgb, d.skip)) {
-    Resolved l = sep_launch(pe->fn, pe->name, 0, (unsigned)pipe_threads(pe->na), pe->lds_bytes, a);
+    Resolved l = sep_launch(*pe, 0, (unsigned)pipe_threads(pe->na), pe->lds_bytes, a);
     l.args.sep.nchunks = a.CO / pe->NT;                  // (FIR-up: 64-column chunks, see pick_pipe)
     l.drop_y = d.out_dead && pe->torgb;                  // sepconv_pipe_kernel<MODE_NORMAL, ..., TORGB = true, ...>: finish_block tests p.y
     l.grid = std::min((unsigned)(g.tiles_x * g.tiles_y * l.args.sep.nchunks * a.B), pipe_grid);
     return l;
   }
   if (const Wide2Entry* we = pick_wide2(g, a, nd, fused_rgb, d.skip)) {
-    Resolved l = sep_launch(we->fn, we->name, 0, (unsigned)kW2Threads, (size_t)W2Lds::TOTAL, a);
+    Resolved l = sep_launch(*we, 0, (unsigned)kW2Threads, (size_t)W2Lds::TOTAL, a);
     SepArgs& aw = l.args.sep;
     aw.tiles_x = a.W / 16; aw.tiles_y = a.H / 16; aw.nchunks = a.CO / 256;
     aw.sy = 16; aw.sx = 16; aw.off = 0;
@@ -706,10 +737,10 @@ inline Resolved resolve_sepconv(Geo g, const SepArgs& a, const LayerDesc& d, boo
               "ToRGB can only be fused into a plain layer whose output channels fit one column tile");
   if (g.wide) {
     const WideEntry& e = wide_entry(g);
-    return sep_launch(e.fn, e.name, tiles_of(g, a.B), (unsigned)kWideThreads, g.lds_bytes, a);
+    return sep_launch(e, tiles_of(g, a.B), (unsigned)kWideThreads, g.lds_bytes, a);
   }
   const KernelEntry& k = pick_kernel(g);
-  return sep_launch(k.fn, k.name, grid_of(g, a.B, fused_rgb), (unsigned)kThreads, g.lds_bytes, a);
+  return sep_launch(k, grid_of(g, a.B, fused_rgb), (unsigned)kThreads, g.lds_bytes, a);
 }
 
 // The launches layer d becomes for n images (kernel forms chosen for nd: resolve_sepconv), in order, into out[]; returns how many.  A tiled
@@ -797,6 +828,14 @@ inline void launch(const Resolved& r, const LayerPtrs& q, rt::stream_t stream) {
     a.prof = prof_buffer();
     if (q.u8_in) set_u8(a, *q.u8_in, false);                     // the FromRGB head builds x from the uint8 image and mask
     if (q.u8_out && a.trgb_w) set_u8(a, *q.u8_out, true);         // the fused ToRGB tail composes and writes uint8
+    if (q.samples > 0) {
+      // (callers check rows_fn of every launch before the first one; a missing per-row form is an error, never the plain form)
+      MIGAN_CHECK(r.rows_fn != nullptr, MIGAN_EUNSUPPORTED, std::string("no per-row noise form of ") + r.name);
+      SepRowArgs ra{a, q.samples, q.noise_stride};
+      rt_check(rt::launch(r.rows_fn, ra, r.grid, r.threads, r.lds_bytes, stream), r.rows_name);
+      last_kernel_ref() = r.rows_name;
+      return;
+    }
     rt_check(rt::launch(r.fn.sep, a, r.grid, r.threads, r.lds_bytes, stream), r.name);
     last_kernel_ref() = r.name;
   } else if (r.kind == K_DWFIR) {
@@ -1037,8 +1076,69 @@ struct migan_handle {
     return total;
   }
   void ensure_aux();
+  // rows (forward_samples): run the launches [lo, hi) only.  samples > 0: at n = rows of a sub-batch through the per-row kernels -- the skip
+  // tensors are those of the once-per-image sub-workspace enc_ws (laid out for enc_n images; img0: the sub-batch's first image), every other
+  // buffer lies in sub_ws as rows_offset says, and row b's plane of launch li is noise + b * F + noise_off[li]
+  struct Rows {
+    size_t lo = 0, hi = 0;
+    int samples = 0;
+    const float* noise = nullptr;
+    size_t F = 0;
+    const size_t* noise_off = nullptr;
+    char* enc_ws = nullptr;
+    int enc_n = 0, img0 = 0;
+  };
   void run_range(const migan::Plan& P, const float* x, float* y, int n, char* sub_ws, char* shared, rt::stream_t stream,
-                 bool timed, int mid_after, int part, const migan_io_u8* u8, int nd);
+                 bool timed, int mid_after, int part, const migan_io_u8* u8, int nd, const Rows* rows = nullptr);
+  void write_planes(const migan::Plan& P, void* ws, rt::stream_t stream);
+  // ---- S completions per image from per-row noise (include/migan_noise_samples_hip.h) ----
+  // the first launch with noise (synthesis.b8.conv1): what lies before it -- the encoder and synthesis.b4 -- runs once per image
+  static size_t first_rows_launch(const migan::Plan& P) {
+    size_t i = 0;
+    while (i < P.launches.size() && P.launches[i].w_noise < 0) ++i;
+    return i;
+  }
+  static size_t noise_floats(const migan::Plan& P) {
+    size_t f = 0;
+    for (const migan::Launch& L : P.launches)
+      if (L.w_noise >= 0) f += (size_t)L.hout * L.wout;
+    return f;
+  }
+  // the row workspace holds the ping-pong buffers only (activations, RGB images): the feature maps stay where the encoder wrote them
+  static bool rows_buffer(const migan::Buf& b) { return b.name.compare(0, 3, "act") == 0 || b.name.compare(0, 3, "img") == 0; }
+  static size_t rows_offset(const migan::Plan& P, int id, int rows) {
+    size_t off = 0;
+    for (int i = 0; i < id; ++i)
+      if (rows_buffer(P.bufs[i])) off += migan::align256(P.bufs[i].bytes_per_image * (size_t)rows);
+    return off;
+  }
+  // sub-batches of the n * samples rows, in IMAGES (a row's skip tensor is its image's): as split() sizes them, on image boundaries
+  int split_images(int n, int samples, int imgs[kMaxStreams]) const {
+    int parts = 1;
+    if (streams >= 2) parts = std::min(std::min(streams, (int)kMaxStreams), std::min(n, (int)((long long)n * samples / 8)));
+    if (parts < 2) { imgs[0] = n; return 1; }
+    const int each = (n + parts - 1) / parts;
+    int left = n, k = 0;
+    while (left > 0 && k < parts) {
+      imgs[k] = (k == parts - 1) ? left : std::min(each, left);
+      left -= imgs[k];
+      ++k;
+    }
+    return k;
+  }
+  // The batch a sub-batch of `imgs` images of a call of n picks its kernel forms for.  A forward of those n images runs every one of them on
+  // the single-image forms (the K-split tiles, which sum K in another order: resolve_layer) if n == 1 and on none of them otherwise, in
+  // whatever sub-batches; so must every row, also where the split leaves one image to a sub-batch (n = 2, S = 8: 1 + 1).
+  static int rows_forms_batch(int n, int imgs) { return n == 1 ? 1 : std::max(imgs, 2); }
+  size_t workspace_bytes_samples(const migan::Plan& P, int n, int samples) const {
+    int imgs[kMaxStreams];
+    const int parts = split_images(n, samples, imgs);
+    size_t total = migan::align256(P.shared_bytes) + sub_bytes(P, n);
+    for (int k = 0; k < parts; ++k) total += rows_offset(P, (int)P.bufs.size(), imgs[k] * samples);
+    return total;
+  }
+  void forward_samples(migan::Plan& P, const float* x, const float* noise, float* y, int n, int samples, void* ws, size_t ws_bytes,
+                       rt::stream_t stream);
   // parts (migan_forward_parts): sub-batch k writes its images to parts->y[k] and, for k >= 1, runs on the CALLER's stream parts->streams[k - 1]
   // instead of the handle's own; the streams are not joined (the caller orders whatever follows behind each of them)
   struct Parts {
@@ -1333,10 +1433,11 @@ inline void migan_handle::ensure_aux() {
 // launches of one sub-batch of n images on `stream`.  nd: the batch the kernel forms are chosen for -- the per-launch timing run covers the whole
 // batch in one launch but must time the forms the production forward launches for its sub-batches
 inline void migan_handle::run_range(const migan::Plan& P, const float* x, float* y, int n, char* sub_ws, char* shared,
-                                    rt::stream_t stream, bool timed, int mid_after, int part, const migan_io_u8* u8, int nd) {
+                                    rt::stream_t stream, bool timed, int mid_after, int part, const migan_io_u8* u8, int nd, const Rows* rows) {
   using namespace migan;
+  const bool per_row = rows && rows->samples > 0;
   std::vector<size_t> offs(P.bufs.size());
-  for (size_t i = 0; i < P.bufs.size(); ++i) offs[i] = sub_offset(P, (int)i, n);
+  for (size_t i = 0; i < P.bufs.size(); ++i) offs[i] = per_row ? rows_offset(P, (int)i, n) : sub_offset(P, (int)i, n);
   auto bptr = [&](int id) -> void* {
     if (id == BUF_NONE) return nullptr;
     if (id == BUF_X) return const_cast<float*>(x);
@@ -1347,7 +1448,8 @@ inline void migan_handle::run_range(const migan::Plan& P, const float* x, float*
   unsigned short* wsplit = reinterpret_cast<unsigned short*>(shared);
   const std::vector<Resolved> R = P.resolve(n, nd);
   prepare_kernels();
-  for (size_t li = 0; li < P.launches.size(); ++li) {
+  const size_t lo = rows ? rows->lo : 0, hi = rows ? rows->hi : P.launches.size();
+  for (size_t li = lo; li < hi; ++li) {
     const Launch& L = P.launches[li];
     MIGAN_CHECK(!L.narrow || u8 == nullptr || (L.in_buf != BUF_X && L.imgout_buf != BUF_Y), MIGAN_EUNSUPPORTED,
                 "the uint8-in / uint8-out forward is not available at resolutions above 512");
@@ -1362,6 +1464,13 @@ inline void migan_handle::run_range(const migan::Plan& P, const float* x, float*
     q.img_prev = (const float*)bptr(L.imgprev_buf); q.img_out = (float*)bptr(L.imgout_buf);
     if (L.in_buf == BUF_X) q.u8_in = u8;
     if (L.imgout_buf == BUF_Y) q.u8_out = u8;
+    if (per_row) {
+      if (L.skip_buf >= 0)
+        q.skip = rows->enc_ws + sub_offset(P, L.skip_buf, rows->enc_n) + (size_t)rows->img0 * P.bufs[L.skip_buf].bytes_per_image;
+      // the caller's plane where it lies in the blobs (never the tiled / cropped copy of an arbitrary-size plan, which is not made)
+      q.noise = L.w_noise >= 0 ? rows->noise + rows->noise_off[li] : nullptr;
+      q.samples = rows->samples; q.noise_stride = (unsigned)rows->F;
+    }
     launch(R[li], q, stream);
     if (timed) rt_check(rt::event_record(events[2 * li + 1], stream), "hipEventRecord");
     if (!timed && (int)li == mid_after) rt_check(rt::event_record(ev_mid[part], stream), "hipEventRecord");
@@ -1372,9 +1481,25 @@ inline void migan_handle::run_range(const migan::Plan& P, const float* x, float*
     }
 #endif
   }
-  if (&P == &plan) {
-    launched.resize(R.size());
-    for (size_t li = 0; li < R.size(); ++li) launched[li] = R[li].name;
+  if (&P == &plan) {      // (a samples call: its once-per-image range first, then the per-row range of every sub-batch, the last one's names staying)
+    if (launched.size() != R.size()) {
+      launched.resize(R.size());
+      for (size_t li = 0; li < R.size(); ++li) launched[li] = R[li].name;
+    }
+    for (size_t li = lo; li < hi; ++li) launched[li] = per_row && R[li].kind == K_SEP ? R[li].rows_name : R[li].name;
+  }
+}
+
+// the 16-bit operand planes of every conv2.weight, at the start of the workspace, unless they are known to be there (see forward)
+inline void migan_handle::write_planes(const migan::Plan& P, void* ws, rt::stream_t stream) {
+  using namespace migan;
+  const bool planes_valid = static_weights && prepared_ws == ws && prepared_epoch == weight_epoch && prepared_stream == stream;
+  if (gemm && !planes_valid) {
+    SplitArgs sa = split_args(reinterpret_cast<unsigned short*>(ws), gemm);
+    for (const Launch& L : P.launches)
+      if (!L.is_rgb && !L.is_dwfir && !L.narrow) add_split(sa, slots[L.w_pw].ptr, L.wsplit_off, L.cin, L.cout);      // (narrow layers read conv2.weight in fp32)
+    launch_split(sa, stream);
+    prepared_ws = ws; prepared_epoch = weight_epoch; prepared_stream = stream;     // only reached when every launch succeeded
   }
 }
 
@@ -1400,14 +1525,7 @@ inline void migan_handle::forward(migan::Plan& P, const float* x, float* y, int 
   // conv2.weight of every layer -> 16-bit operand planes.  Re-done every forward (the weights are read in place, so
   // in-place parameter updates are always picked up) unless the caller asserted static weights and these planes were
   // written, in this workspace and stream order, since the last (re)binding of a weight.
-  const bool planes_valid = static_weights && prepared_ws == ws && prepared_epoch == weight_epoch && prepared_stream == stream;
-  if (gemm && !planes_valid) {
-    SplitArgs sa = split_args(reinterpret_cast<unsigned short*>(shared), gemm);
-    for (const Launch& L : P.launches)
-      if (!L.is_rgb && !L.is_dwfir && !L.narrow) add_split(sa, slots[L.w_pw].ptr, L.wsplit_off, L.cin, L.cout);      // (narrow layers read conv2.weight in fp32)
-    launch_split(sa, stream);
-    prepared_ws = ws; prepared_epoch = weight_epoch; prepared_stream = stream;     // only reached when every launch succeeded
-  }
+  write_planes(P, ws, stream);
   // arbitrary-size plans: crop / tile every noise_const to its layer's plane
   for (const Launch& L : P.launches) {
     if (L.noise_plane_off < 0) continue;
@@ -1462,6 +1580,83 @@ inline void migan_handle::forward(migan::Plan& P, const float* x, float* y, int 
     for (size_t li = 0; li < P.launches.size(); ++li)
       rt_check(rt::event_elapsed(&ms[li], events[2 * li], events[2 * li + 1]), "hipEventElapsedTime");
   }
+}
+
+// S completions per image (include/migan_noise_samples_hip.h): the launches before the first noisy one once per image on `stream`, synthesis.b4's
+// 4 x 4 output and image copied to every row, then the rest of the plan at samples rows per image through the per-row kernels, in sub-batches of
+// whole images on the handle's streams.  Every refusal comes before the first launch.
+inline void migan_handle::forward_samples(migan::Plan& P, const float* x, const float* noise, float* y, int n, int samples, void* ws,
+                                          size_t ws_bytes, rt::stream_t stream) {
+  using namespace migan;
+  MIGAN_CHECK(committed, MIGAN_ESTATE, "migan_forward_samples_hw before migan_commit");
+  MIGAN_CHECK(x && noise && y && n > 0 && samples > 0, MIGAN_EINVAL, "null tensor, empty batch or samples < 1");
+  MIGAN_CHECK(ws != nullptr, MIGAN_EINVAL, "null workspace");
+  MIGAN_CHECK(samples <= kMaxRowSamples && (long long)n * samples < (1ll << 24), MIGAN_EINVAL, "too many samples or rows");
+  MIGAN_CHECK(!debug, MIGAN_EUNSUPPORTED, "per-row noise is not available in keep-intermediates mode");
+  for (const Launch& L : P.launches)
+    MIGAN_CHECK(!L.narrow, MIGAN_EUNSUPPORTED, "per-row noise is not available at resolutions above 512 (layers with fewer than 64 channels)");
+  MIGAN_CHECK(ws_bytes >= workspace_bytes_samples(P, n, samples), MIGAN_EINVAL, "workspace too small for this batch and sample count");
+  const size_t first = first_rows_launch(P), nl = P.launches.size();
+  MIGAN_CHECK(first > 0 && first < nl, MIGAN_EINVAL, "internal: plan without a noisy layer");
+  int imgs[kMaxStreams];
+  const int parts = split_images(n, samples, imgs);
+  // what the first per-row launches read by row although it was computed per image: the input of launch `first` and the first previous image
+  const Launch& L0 = P.launches[first];
+  size_t li_img = first;
+  while (li_img < nl && P.launches[li_img].imgprev_buf == BUF_NONE) ++li_img;
+  MIGAN_CHECK(L0.in_buf >= 0 && li_img < nl && P.launches[li_img].imgprev_buf >= 0 && rows_buffer(P.bufs[L0.in_buf]) &&
+              rows_buffer(P.bufs[P.launches[li_img].imgprev_buf]), MIGAN_EINVAL, "internal: unexpected buffers around the first noisy layer");
+  const Launch& LI = P.launches[li_img];
+  std::vector<size_t> noise_off(nl, 0);
+  size_t F = 0;
+  for (size_t li = 0; li < nl; ++li)
+    if (P.launches[li].w_noise >= 0) { noise_off[li] = F; F += (size_t)P.launches[li].hout * P.launches[li].wout; }
+  MIGAN_CHECK(F < kMaxRowNoiseStride, MIGAN_EINVAL, "image too large: a row's noise blob would exceed the 32-bit offsets of the kernels");
+  for (int k = 0; k < parts; ++k) {      // a missing per-row form is an error before anything runs, never the plain kernel
+    const std::vector<Resolved> R = P.resolve(imgs[k] * samples, rows_forms_batch(n, imgs[k]));
+    for (size_t li = first; li < nl; ++li)
+      MIGAN_CHECK(R[li].kind != K_SEP || R[li].rows_fn != nullptr, MIGAN_EUNSUPPORTED, std::string("no per-row noise form of ") + R[li].name);
+  }
+  DeviceGuard guard(device);
+  char* shared = static_cast<char*>(ws);
+  char* enc = shared + align256(P.shared_bytes);
+  write_planes(P, ws, stream);
+  Rows once;
+  once.lo = 0; once.hi = first;
+  // (one launch for all n images, forms for n: a forward of 16 or more images runs them in sub-batches of 8 or more, on forms that give the
+  // same bits -- only a single image's differ)
+  run_range(P, x, nullptr, n, enc, shared, stream, false, -1, 0, nullptr, n, &once);
+  if (parts > 1) ensure_aux();
+  const size_t in_words = (size_t)L0.hin * L0.win * L0.cin * (stv == 0 ? 4 : 2) / 4, img_words = (size_t)3 * (LI.hout / 2) * (LI.wout / 2);
+  const size_t out_img = (size_t)3 * P.H * P.W;
+  char* sub = enc + sub_bytes(P, n);
+  int done = 0;
+  for (int k = 0; k < parts; ++k) {
+    const int rows_k = imgs[k] * samples;
+    rt::stream_t sk = k == 0 ? stream : aux_stream[k - 1];
+    // (sub-batch 0 runs behind the once-per-image launches on the caller's stream; each later one starts when the one before it is
+    // `stagger` launches in, as in forward, and is thereby ordered behind them too)
+    if (k > 0) rt_check(rt::stream_wait_event(sk, ev_mid[k - 1]), "hipStreamWaitEvent");
+    for (int t = 0; t < 2; ++t) {
+      const int id = t == 0 ? L0.in_buf : LI.imgprev_buf;
+      RowsCopyArgs ca{};
+      ca.words = (int)(t == 0 ? in_words : img_words); ca.samples = samples; ca.B = rows_k;
+      ca.src = reinterpret_cast<const unsigned*>(enc + sub_offset(P, id, n)) + (size_t)done * ca.words;
+      ca.dst = reinterpret_cast<unsigned*>(sub + rows_offset(P, id, rows_k));
+      rt_check(rt::launch(rows_copy_kernel, ca, (unsigned)rows_k, kThreads, 0, sk), "migan::rows_copy_kernel");
+    }
+    Rows rw;
+    rw.lo = first; rw.hi = nl; rw.samples = samples; rw.noise = noise + (size_t)done * samples * F; rw.F = F; rw.noise_off = noise_off.data();
+    rw.enc_ws = enc; rw.enc_n = n; rw.img0 = done;
+    const int mid = k + 1 < parts ? (int)std::min(nl - 1, first + (size_t)P.stagger) : -1;
+    // kernel forms as a forward of the call's n images picks them for these images (rows_forms_batch; grids are sized for the rows): with
+    // the model's own planes as every row's blob, a row then holds the bits of that forward, however the rows are split
+    run_range(P, nullptr, y + (size_t)done * samples * out_img, rows_k, sub, shared, sk, false, mid, k, nullptr, rows_forms_batch(n, imgs[k]), &rw);
+    if (k > 0) rt_check(rt::event_record(ev_join[k - 1], sk), "hipEventRecord");
+    sub += rows_offset(P, (int)P.bufs.size(), rows_k);
+    done += imgs[k];
+  }
+  for (int k = 1; k < parts; ++k) rt_check(rt::stream_wait_event(stream, ev_join[k - 1]), "hipStreamWaitEvent");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1697,6 +1892,32 @@ int migan_forward_hw(migan_handle* h, const void* x, void* y, int batch, int hei
   MIGAN_API_END
 }
 
+// S completions per image from per-row noise (include/migan_noise_samples_hip.h)
+int migan_noise_floats_hw(migan_handle* h, int height, int width, size_t* floats) {
+  MIGAN_API_BEGIN
+  MIGAN_CHECK(h && floats, MIGAN_EINVAL, "bad argument");
+  migan_check_hw(h, height, width);
+  *floats = migan_handle::noise_floats(h->plan_for(height, width));
+  MIGAN_API_END
+}
+int migan_workspace_bytes_samples_hw(migan_handle* h, int n, int samples, int height, int width, size_t* bytes) {
+  MIGAN_API_BEGIN
+  MIGAN_CHECK(h && bytes && n > 0 && samples > 0 && (long long)n * samples < (1ll << 24), MIGAN_EINVAL, "bad argument");
+  migan_check_hw(h, height, width);
+  *bytes = h->workspace_bytes_samples(h->plan_for(height, width), n, samples);
+  MIGAN_API_END
+}
+int migan_forward_samples_hw(migan_handle* h, const void* x, const void* noise, void* y, int n, int samples, int height, int width, void* ws,
+                             size_t ws_bytes, void* stream) {
+  MIGAN_API_BEGIN
+  MIGAN_CHECK(h, MIGAN_EINVAL, "null handle");
+  MIGAN_CHECK(x && noise && y && n > 0 && samples > 0, MIGAN_EINVAL, "null tensor, empty batch or samples < 1");
+  migan_check_hw(h, height, width);
+  h->forward_samples(h->plan_for(height, width), static_cast<const float*>(x), static_cast<const float*>(noise), static_cast<float*>(y), n,
+                     samples, ws, ws_bytes, (rt::stream_t)stream);
+  MIGAN_API_END
+}
+
 // uint8 in, uint8 out: demo.py's preprocess() fused into the first layer's tile builder, its postprocess + compose fused
 // into the last ToRGB epilogue
 int migan_forward_u8(migan_handle* h, const void* img_hwc_u8, const void* mask_u8, void* out_hwc_u8, int batch, void* ws, size_t ws_bytes,
@@ -1778,10 +1999,14 @@ int migan_debug_tensor_hw(migan_handle* h, int batch, int height, int width, con
   MIGAN_API_END
 }
 
-int migan_sepconv_forward(const migan_sepconv_desc* d, void* stream) {
+// samples == 0: migan_sepconv_forward; > 0: migan_sepconv_forward_samples (noise_const one plane per row, skip one tensor per image)
+static int migan_sepconv_run(const migan_sepconv_desc* d, int samples, void* stream) {
   MIGAN_API_BEGIN
   using namespace migan;
   MIGAN_CHECK(d != nullptr, MIGAN_EINVAL, "null descriptor");
+  if (samples > 0)
+    MIGAN_CHECK(samples <= migan::kMaxRowSamples && d->down == 1 && d->fromrgb_weight == nullptr && !is_narrow(d->cin, d->cout) && d->batch > 0 && d->batch % samples == 0, MIGAN_EINVAL,
+                "per-row noise: a plain or FIR-up layer of at least 64 channels without FromRGB, batch a multiple of samples");
   MIGAN_CHECK(d->x && d->y && d->conv1_weight && d->conv1_bias && d->conv2_weight, MIGAN_EINVAL, "null tensor");
   MIGAN_CHECK((d->down == 1 || d->down == 2) && (d->up == 1 || d->up == 2) && !(d->down == 2 && d->up == 2), MIGAN_EINVAL,
               "down/up must be 1 or 2 and not both 2");
@@ -1837,6 +2062,12 @@ int migan_sepconv_forward(const migan_sepconv_desc* d, void* stream) {
   }
   Resolved R[kMaxLayerLaunches];
   const int k = resolve_layer(ld, d->batch, d->batch, R);
+  if (samples > 0) {
+    MIGAN_CHECK((size_t)h_out * w_out < kMaxRowNoiseStride, MIGAN_EINVAL, "per-row noise: plane too large for the 32-bit offsets of the kernels");
+    p.samples = samples; p.noise_stride = (unsigned)(h_out * w_out);
+    for (int i = 0; i < k; ++i)
+      MIGAN_CHECK(R[i].kind != K_SEP || R[i].rows_fn != nullptr, MIGAN_EUNSUPPORTED, std::string("no per-row noise form of ") + R[i].name);
+  }
   if (R[0].kind == K_DWFIR)
     MIGAN_CHECK(d->scratch != nullptr && d->scratch_bytes >= (size_t)d->batch * h_out * w_out * d->cin * sizeof(float), MIGAN_EINVAL,
                 "down=2 needs scratch of batch*(res_in/2)^2*cin floats");
@@ -1857,6 +2088,14 @@ int migan_sepconv_forward(const migan_sepconv_desc* d, void* stream) {
     launch(R[i], q, (rt::stream_t)stream);
   }
   MIGAN_API_END
+}
+int migan_sepconv_forward(const migan_sepconv_desc* d, void* stream) { return migan_sepconv_run(d, 0, stream); }
+int migan_sepconv_forward_samples(const migan_sepconv_desc* d, int samples, void* stream) {
+  if (samples < 1) {
+    ::migan::last_error_ref() = "samples < 1";
+    return MIGAN_EINVAL;
+  }
+  return migan_sepconv_run(d, samples, stream);
 }
 
 static int migan_prepost_launch(bool pack, const void* y, const void* img, const void* mask, void* x, void* out, int batch,

@@ -27,7 +27,12 @@
 // compiler against tests/emu/hip_emu.h (a fiber-per-lane SIMT emulator used only by the CPU test
 // suite to check indexing/LDS/MFMA-fragment logic without a GPU).  The emulator is test
 // infrastructure; nothing in the product loads it.
-#pragma once
+#if !defined(MIGAN_KERNELS_HPP_) || defined(MIGAN_BODY_ROWS)
+// The kernel text between the "#endif  // !MIGAN_BODY_ROWS" lines of this file is compiled twice: this file includes itself once, with
+// MIGAN_BODY_ROWS defined as 1, and then emits only that text, as the per-row form (SepRowArgs, migan_kernels.hpp) of the same kernel.  The
+// plain kernel so keeps the parameter and the text it always had; ROWS / MIGAN_BODY_ROWS mark the only places where the two differ.
+#ifndef MIGAN_BODY_ROWS
+#define MIGAN_KERNELS_HPP_
 
 namespace migan {
 
@@ -80,6 +85,22 @@ struct SepArgs {
   int b_stride;                    // floats between the two 1x1-weight buffers (0 = single buffered)
   int a_stride;                    // MODE_PW: floats between the two A-operand buffers
 };
+
+// Per-row noise (migan_forward_samples_hw; reference training generator lib/model_zoo/migan.py:130-138, noise_mode='random' with the draw
+// given): the B rows of the launch are `samples` completions of each of B / samples images.  The *_rows_kernel form of a kernel family takes
+// this struct; it differs from the plain form in two addresses only, both formed once per tile from wave-uniform values:
+//   a.noise  row b reads the [HO][WO] plane at a.noise + b * noise_stride (the plain form reads one plane for every row).  noise_stride = HO * WO:
+//            a [B][HO][WO] tensor (migan_sepconv_forward_samples); = F: the layer's plane inside the caller's [B][F] blobs, used where it lies
+//   a.skip   [B / samples][HO][WO][CO]: row b adds the feature map of image b / samples (the encoder's maps are not replicated)
+struct SepRowArgs {
+  SepArgs a;
+  int samples;
+  unsigned noise_stride;      // floats between the planes of consecutive rows
+};
+// image of row r0 + i of a tile whose first row r0 has the remainder rem = r0 % samples, relative to the image of r0: (rem + i) / samples by a
+// multiplication with the tile's (wave-uniform) rcp = 1 / samples.  (k + 0.5) / samples is at least 0.5 / samples away from an integer and the
+// product is off by less than k / samples * 2^-22: exact for k < 2^20
+MIGAN_DEVICE MIGAN_INLINE int rows_image_of(int rem, int i, float rcp) { return (int)(((float)(rem + i) + 0.5f) * rcp); }
 
 struct RgbArgs {
   const void* x;         // NHWC [B][H][W][C], stored as Io<STV>
@@ -445,10 +466,25 @@ MIGAN_DEVICE MIGAN_INLINE void compose_pixel_bytes(u4v b, unsigned char* out, si
 //
 // Waves are laid out 2x2 over the MT x NT tile; each wave owns (MT/2)x(NT/2) as 32x32 MFMA tiles.
 //   STV    : activation storage format (Io<STV>): 0 fp32, 1 bf16, 2 fp16
+//   ROWS   : per-row noise planes, skip from image row / samples (SepRowArgs): sepconv_rows_kernel, this text compiled a second time (top of the file)
 #define BF_OF(G) ((G) >= 1)
+#endif  // !MIGAN_BODY_ROWS
 template <int MODE, int MT, int NT, int KC, bool FROMRGB, int NI, int MINW, bool MAING, bool PERSIST, int GEMMV, bool TORGB, int STV = 0>
+#if MIGAN_BODY_ROWS
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, MINW) sepconv_rows_kernel(const SepRowArgs ra) {
+  constexpr bool ROWS = true;
+  const SepArgs& p = ra.a;
+  const int samples = ra.samples;
+  const unsigned noise_stride = ra.noise_stride;
+#else
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, MINW) sepconv_kernel(const SepArgs p) {
+  constexpr bool ROWS = false;
+  constexpr int samples = 1;
+  constexpr unsigned noise_stride = 0u;
+#endif
+  (void)samples; (void)noise_stride;
   static_assert(MODE != MODE_DOWN, "FIR-down layers run as dwfir_kernel + a MODE_PW pointwise GEMM");
+  static_assert(!ROWS || (!FROMRGB && MODE != MODE_PW), "per-row noise: synthesis layers (plain and FIR-up)");
   MIGAN_DYN_SMEM(smem);
 
   constexpr int QC = KC / 4;                       // float4 groups per pixel in a K chunk
@@ -992,7 +1028,15 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, MINW) sepconv_kernel(const SepArgs p)
   const int gxt = m0 & (GW - 1), gyt = (m0 >> lgGW) & (GH - 1);
   const size_t img_elems = (size_t)p.HO * p.WO * p.CO;
   char* __restrict__ yb = gy_ + (size_t)b0 * img_elems * IoOut::ESZ;
-  const char* __restrict__ sb = gskip ? gskip + (size_t)b0 * img_elems * IoOut::ESZ : nullptr;
+  // ROWS: the tile's first row b0 reads noise plane b0 and the skip tensor of image b0 / samples; row b0 + i of a multi-image tile reads
+  // plane b0 + i and image b0 / samples + rows_image_of(b0 % samples, i, 1 / samples) (one division per tile, on wave-uniform values)
+  const int skip_b0 = ROWS ? b0 / samples : b0;
+  const int rows_rem = ROWS ? b0 - skip_b0 * samples : 0;
+  const float rows_rcp = ROWS ? 1.0f / (float)samples : 0.0f;
+  const unsigned nplane = ROWS ? noise_stride : 0u;
+  const float* __restrict__ gnz = ROWS ? gnoise + (size_t)b0 * nplane : gnoise;
+  (void)rows_rem; (void)rows_rcp;
+  const char* __restrict__ sb = gskip ? gskip + (size_t)skip_b0 * img_elems * IoOut::ESZ : nullptr;
   constexpr unsigned OE = IoOut::ESZ;
 
   if constexpr (MODE != MODE_UP) {
@@ -1029,6 +1073,9 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, MINW) sepconv_kernel(const SepArgs p)
       typename IoOut::raw4 sk[UB];
       float nz[UB];
       unsigned loff[UB];     // lane part of the offset, in BYTES
+#if MIGAN_BODY_ROWS
+      unsigned soff[UB];     // several images per tile: the same into the skip tensor (its image is not the row)
+#endif
       int upix[UB];          // uniform part, in pixels
       bool ok[UB];
 #pragma unroll
@@ -1039,17 +1086,30 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, MINW) sepconv_kernel(const SepArgs p)
         if constexpr (MAINGEO) {
           upix[u] = (dm >> lgGW) * p.WO + (dm & (GW - 1));
           loff[u] = off_t * OE;
+#if MIGAN_BODY_ROWS
+          soff[u] = loff[u];
+#endif
           ok[u] = true;
-          if constexpr (HN) nz[u] = *at_bytes(gnoise + upix[u], pix_t * 4u);
+          if constexpr (HN) nz[u] = *at_bytes(gnz + upix[u], pix_t * 4u);
         } else {
           const int gx = m & (GW - 1), gy = (m >> lgGW) & (GH - 1), img = m >> (lgGW + lgGH);
           ok[u] = (b0 + img) < p.B && (gy0 + gy) < p.HO && (gx0 + gx) < p.WO;       // ragged batch / ragged image edge
           const unsigned pix = ok[u] ? (unsigned)((gy0 + gy) * p.WO + gx0 + gx) : 0u;
           upix[u] = 0;
           loff[u] = ((unsigned)(ok[u] ? img : 0) * (unsigned)img_elems + pix * (unsigned)p.CO + (unsigned)(n0 + c4 * 4)) * OE;
+#if MIGAN_BODY_ROWS
+          const unsigned simg = ok[u] ? (unsigned)rows_image_of(rows_rem, img, rows_rcp) : 0u;
+          soff[u] = (simg * (unsigned)img_elems + pix * (unsigned)p.CO + (unsigned)(n0 + c4 * 4)) * OE;
+          if constexpr (HN) nz[u] = gnz[(unsigned)(ok[u] ? img : 0) * nplane + pix];
+#else
           if constexpr (HN) nz[u] = gnoise[pix];
+#endif
         }
+#if MIGAN_BODY_ROWS
+        if constexpr (HS) sk[u] = IoOut::ld_once(sb + (size_t)upix[u] * p.CO * OE, soff[u]);
+#else
         if constexpr (HS) sk[u] = IoOut::ld_once(sb + (size_t)upix[u] * p.CO * OE, loff[u]);
+#endif
       }
 #pragma unroll
       for (int u = 0; u < UB; ++u) {
@@ -1131,14 +1191,22 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, MINW) sepconv_kernel(const SepArgs p)
       if (gx < 1 || gx > GW - 2 || ly >= p.H || lx >= p.W || b >= p.B) continue;     // halo columns, ragged edge
       // uniform part (pixels) and lane part (elements) of the four output addresses
       int upix, loff, lpix;
+      int soff, npix;                  // ROWS, several images per tile: the offsets into the skip tensor and the noise planes
       if constexpr (MAINGEO) {
         upix = 2 * (dm >> lgGW) * p.WO + 2 * (dm & (GW - 1));
         loff = ooff_t;
         lpix = opix_t;
+        soff = loff; npix = lpix;
       } else {
         upix = 0;
         lpix = (2 * ly) * p.WO + 2 * lx;
         loff = img * (int)img_elems + lpix * p.CO + n0 + c4 * 4;
+        if constexpr (ROWS) {
+          soff = rows_image_of(rows_rem, img, rows_rcp) * (int)img_elems + lpix * p.CO + n0 + c4 * 4;
+          npix = img * (int)nplane + lpix;
+        } else {
+          soff = loff; npix = lpix;
+        }
       }
       typename IoOut::raw4 sk[2][2];
       float nz[2][2];
@@ -1147,8 +1215,8 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, MINW) sepconv_kernel(const SepArgs p)
 #pragma unroll
         for (int bb = 0; bb < 2; ++bb) {
           const int dp = upix + a * p.WO + bb;                      // uniform
-          if constexpr (HN) nz[a][bb] = gnoise[(unsigned)(lpix + dp)];
-          if constexpr (HS) sk[a][bb] = IoOut::ld_once(sb, (unsigned)(loff + dp * p.CO) * OE);
+          if constexpr (HN) nz[a][bb] = gnz[(unsigned)(npix + dp)];
+          if constexpr (HS) sk[a][bb] = IoOut::ld_once(sb, (unsigned)(soff + dp * p.CO) * OE);
         }
       f4 e[3], o[3];
 #pragma unroll
@@ -1195,6 +1263,7 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, MINW) sepconv_kernel(const SepArgs p)
   }  // tile loop
   PROF_END();
 }
+#ifndef MIGAN_BODY_ROWS
 
 // ------------------------------------------------------------------------------------------------
 // Wide plain layers (Cout % 256 == 0, output >= 16x16, f16x2 GEMM): one workgroup of 8 waves owns
@@ -1223,8 +1292,22 @@ constexpr int kWideThreads = 512;
 // pixels overlaps its neighbours by one pixel (tile pitch 6x14, as sepconv_kernel<MODE_UP>), the epilogue turns every interior pixel of
 // the result tile into its 2x2 output pixels (polyphase 1/4, 3/4 taps, reference Upsample2d :79-104) + noise + activation + skip.  One
 // workgroup per 256 columns instead of one per 128: the depthwise stage and the input tile are read half as often.
+// ROWS: per-row noise planes, skip from image row / samples (SepRowArgs): sepconv_wide_rows_kernel, this text compiled a second time (top of the file)
+#endif  // !MIGAN_BODY_ROWS
 template <bool TORGB, int STV = 0, bool X1 = false, bool BALL = false, bool DMA = false, bool UP = false>
+#if MIGAN_BODY_ROWS
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(kWideThreads, 2) sepconv_wide_rows_kernel(const SepRowArgs ra) {
+  constexpr bool ROWS = true;
+  const SepArgs& p = ra.a;
+  const int samples = ra.samples;
+  const unsigned noise_stride = ra.noise_stride;
+#else
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(kWideThreads, 2) sepconv_wide_kernel(const SepArgs p) {
+  constexpr bool ROWS = false;
+  constexpr int samples = 1;
+  constexpr unsigned noise_stride = 0u;
+#endif
+  (void)samples; (void)noise_stride;
   static_assert(!DMA || (STV == 0 && BALL), "the LDS-DMA staging is built for fp32 storage on the dedicated-MFMA-wave form");
   static_assert(!UP || (DMA && !TORGB), "the FIR-up epilogue is built on the LDS-DMA form");
   typedef Io<STV> IoT;
@@ -1632,7 +1715,10 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(kWideThreads, 2) sepconv_wide_kernel(const
   const int gxt = m0 & (GW - 1), gyt = m0 >> lgGW;
   const size_t img_elems = (size_t)p.HO * p.WO * p.CO;
   char* __restrict__ yb = gy_ + (size_t)b0 * img_elems * OE;
-  const char* __restrict__ sb = gskip ? gskip + (size_t)b0 * img_elems * OE : nullptr;
+  // ROWS: row b0 reads noise plane b0 and the skip tensor of image b0 / samples (one tile = one row: a division per workgroup)
+  const int skip_b0 = ROWS ? b0 / samples : b0;
+  const float* __restrict__ gnz = ROWS ? gnoise + (size_t)b0 * noise_stride : gnoise;
+  const char* __restrict__ sb = gskip ? gskip + (size_t)skip_b0 * img_elems * OE : nullptr;
   f4 tw0 = {0.f, 0.f, 0.f, 0.f}, tw1 = tw0, tw2 = tw0;
   int rgb_oy = 0, rgb_ox = 0;
   bool rgb_ok = false;
@@ -1674,7 +1760,7 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(kWideThreads, 2) sepconv_wide_kernel(const
 #pragma unroll
           for (int bb = 0; bb < 2; ++bb) {
             const int dp = upix + a * p.WO + bb;
-            if constexpr (HN) nz[a][bb] = gnoise[(unsigned)(opix_t + dp)];
+            if constexpr (HN) nz[a][bb] = gnz[(unsigned)(opix_t + dp)];
             if constexpr (HS) sk[a][bb] = IoT::ld_once(sb, (unsigned)(ooff_t + dp * p.CO) * OE);
           }
         f4 e[3], o[3];
@@ -1725,7 +1811,7 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(kWideThreads, 2) sepconv_wide_kernel(const
         const int dm = (it0 + u) * STEP;
         val[u] = ld4(g_s + (m0 + dm) * GS + c4 * 4);
         upix[u] = (dm >> lgGW) * p.WO + (dm & (GW - 1));
-        if constexpr (HN) nz[u] = *at_bytes(gnoise + upix[u], pix_t * 4u);
+        if constexpr (HN) nz[u] = *at_bytes(gnz + upix[u], pix_t * 4u);
         if constexpr (HS) sk[u] = IoT::ld_once(sb + (size_t)upix[u] * p.CO * OE, off_t);
       }
 #pragma unroll
@@ -1775,6 +1861,27 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(kWideThreads, 2) sepconv_wide_kernel(const
     }
   }
 }
+#ifndef MIGAN_BODY_ROWS
+#define MIGAN_BODY_ROWS 1
+#include "migan_kernels.hpp"
+#undef MIGAN_BODY_ROWS
+
+// Once per forward of S completions per image: the 4 x 4 tensors the first per-row layers read by row (synthesis.b4's output and image, computed
+// once per image) are copied to every row of their image -- `words` 32-bit words per image, dst row r = src image r / samples.
+struct RowsCopyArgs {
+  const unsigned* src;      // [B / samples][words]
+  unsigned* dst;            // [B][words]
+  int words, samples, B;
+};
+#ifndef MIGAN_TEMPLATE_KERNELS_ONLY
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) rows_copy_kernel(const RowsCopyArgs p) {
+  const int row = (int)blockIdx.x;                       // (one row per workgroup: the division is on wave-uniform values)
+  if (row >= p.B) return;
+  const unsigned* s = p.src + (size_t)(row / p.samples) * p.words;
+  unsigned* d = p.dst + (size_t)row * p.words;
+  for (int i = (int)threadIdx.x; i < p.words; i += kThreads) d[i] = s[i];
+}
+#endif
 
 // ------------------------------------------------------------------------------------------------
 // First half of a down=2 SeparableConv2d (reference :155-160): depthwise 3x3 + bias, lrelu_agc, then
@@ -2298,3 +2405,5 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) compose_output_kernel(const PrePos
 }  // namespace migan
 
 #include "migan_pipeline.hpp"
+#endif  // !MIGAN_BODY_ROWS
+#endif  // MIGAN_KERNELS_HPP_

@@ -22,7 +22,12 @@
 // trip is > 100); the first form of this kernel (4 + 4 waves) was bound by the lone epilogue wave per SIMD
 // (profiles/r04_pipe_phase_profile.txt), so the stages are spread over three to four waves per SIMD.
 // fp32 activation storage, f16x2 GEMM (the default of that storage format); everything else keeps sepconv_kernel.
-#pragma once
+#if !defined(MIGAN_PIPE_HPP_) || defined(MIGAN_BODY_ROWS)
+// The kernel text between the "#endif  // !MIGAN_BODY_ROWS" lines of this file is compiled twice: this file includes itself once, with
+// MIGAN_BODY_ROWS defined as 1, and then emits only that text, as the per-row form (SepRowArgs, migan_kernels.hpp) of the same kernel.  The
+// plain kernel so keeps the parameter and the text it always had; ROWS / MIGAN_BODY_ROWS mark the only places where the two differ.
+#ifndef MIGAN_BODY_ROWS
+#define MIGAN_PIPE_HPP_
 
 namespace migan {
 
@@ -107,8 +112,23 @@ struct PipeLds {
 #define PPROF_END(AT_) do {} while (0)
 #endif
 
+// ROWS: per-row noise planes, skip from image row / samples (SepRowArgs, migan_kernels.hpp): sepconv_pipe_rows_kernel, this text compiled a second time (top of the file)
+#endif  // !MIGAN_BODY_ROWS
 template <int MODE, int NT, int CIN, bool FROMRGB, bool TORGB, int R, int NA>
+#if MIGAN_BODY_ROWS
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(pipe_threads(NA), (NA + kPipeBWaves) / 4) sepconv_pipe_rows_kernel(const SepRowArgs ra) {
+  constexpr bool ROWS = true;
+  const SepArgs& p = ra.a;
+  const int samples = ra.samples;
+  const unsigned noise_stride = ra.noise_stride;
+#else
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(pipe_threads(NA), (NA + kPipeBWaves) / 4) sepconv_pipe_kernel(const SepArgs p) {
+  constexpr bool ROWS = false;
+  constexpr int samples = 1;
+  constexpr unsigned noise_stride = 0u;
+#endif
+  (void)samples; (void)noise_stride;
+  static_assert(!ROWS || !FROMRGB, "per-row noise: synthesis layers");
   static_assert(MODE == MODE_NORMAL || MODE == MODE_UP, "plain and FIR-up layers");
   static_assert(!FROMRGB || MODE == MODE_NORMAL, "FromRGB is fused into the first plain layer");
   static_assert(!TORGB || MODE == MODE_NORMAL, "ToRGB is fused into plain layers");
@@ -628,13 +648,25 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(pipe_threads(NA), (NA + kPipeBWaves) / 4) 
   // coordinates of the tile whose accumulators are in `accp` (pn0 etc.) and of the tile being accumulated (cn0 etc.)
   int ck = 0, cn0 = 0, cb0 = 0, cgy0 = 0, cgx0 = 0, pn0 = 0, pb0 = 0, pgy0 = 0, pgx0 = 0;
   int ppar = 0;                                                   // parity of the tile being finished = its previous-image window buffer
+  // ROWS: the image whose skip tensor the rows cb0 / pb0 add (row / samples: one division per tile, on the tile cursor's wave-uniform values)
+#if MIGAN_BODY_ROWS
+  int cskb = 0, pskb = 0;
+#endif
   TileCur ctc = tile0;
   tile_coords(ctc, cn0, cb0, cgy0, cgx0);
+#if MIGAN_BODY_ROWS
+  cskb = cb0 / samples;
+#endif
   auto hand_over = [&]() {
 #pragma unroll
     for (int j = (MODE == MODE_NORMAL ? 1 : 0); j < NTIW; ++j) accp[j] = acc[j];      // (plain layers stage block 0 straight from `acc`)
     pn0 = cn0; pb0 = cb0; pgy0 = cgy0; pgx0 = cgx0; ppar = ck & 1;
+#if MIGAN_BODY_ROWS
+    pskb = cskb;
+    if (++ck < T) { tile_next(ctc); tile_coords(ctc, cn0, cb0, cgy0, cgx0); cskb = cb0 / samples; }
+#else
     if (++ck < T) { tile_next(ctc); tile_coords(ctc, cn0, cb0, cgy0, cgx0); }
+#endif
   };
 
   BuildCursor bcur;
@@ -694,8 +726,14 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(pipe_threads(NA), (NA + kPipeBWaves) / 4) 
     auto request_next = [&]() {
       if (has_noise) {
         const unsigned px = (unsigned)((cgy0 + 2 * rb) * p.WO + cgx0 + prow) * 4u;
+#if MIGAN_BODY_ROWS
+        const float* nzp = p.noise + (size_t)cb0 * noise_stride;      // plane of row cb0: a uniform base, like the plane itself
+#pragma unroll
+        for (int q = 0; q < 4; ++q) nzn[q] = *at_bytes(nzp + ((q >> 1) * p.WO + (q & 1) * 8), px);
+#else
 #pragma unroll
         for (int q = 0; q < 4; ++q) nzn[q] = *at_bytes(p.noise + ((q >> 1) * p.WO + (q & 1) * 8), px);
+#endif
       }
       if constexpr (TORGB) {
         if (p.u8_out && cbk == 0 && q4 < 4)
@@ -916,13 +954,22 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(pipe_threads(NA), (NA + kPipeBWaves) / 4) 
       int m;
       unsigned lpix, loff;
       if (!item_geo(k, h, m, lpix, loff)) return;
+#if MIGAN_BODY_ROWS
+      const char* sb = p.skip ? reinterpret_cast<const char*>(p.skip) + (size_t)pskb * img_out_bytes : nullptr;      // image of row pb0
+      const float* nzp = p.noise + (size_t)pb0 * noise_stride;                                                         // plane of row pb0
+#else
       const char* sb = p.skip ? reinterpret_cast<const char*>(p.skip) + (size_t)pb0 * img_out_bytes : nullptr;
+#endif
 #pragma unroll
       for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int bb = 0; bb < 2; ++bb) {
           const unsigned dp = (unsigned)(a * p.WO + bb);
+#if MIGAN_BODY_ROWS
+          io.nzv[a][bb] = has_noise ? nzp[lpix + dp] : 0.0f;
+#else
           io.nzv[a][bb] = has_noise ? p.noise[lpix + dp] : 0.0f;
+#endif
           io.sk[a][bb] = sb ? Io<0>::ld_once(sb, loff + dp * (unsigned)p.CO * 4u) : f4{0.f, 0.f, 0.f, 0.f};
         }
     };
@@ -1011,6 +1058,10 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(pipe_threads(NA), (NA + kPipeBWaves) / 4) 
   PPROF_MARK(5);
   PPROF_END(AT);
 }
+#ifndef MIGAN_BODY_ROWS
+#define MIGAN_BODY_ROWS 1
+#include "migan_pipe.hpp"
+#undef MIGAN_BODY_ROWS
 
 // ------------------------------------------------------------------------------------------------------------------------------------
 // down=2 SeparableConv2d as ONE pipelined kernel (reference :154-163: depthwise 3x3 + bias -> lrelu_agc -> Downsample2d (4x4 FIR,
@@ -1448,3 +1499,5 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS((NA + NB) * 64, (NA + NB) / 4) sepconv_pip
 }
 
 }  // namespace migan
+#endif  // !MIGAN_BODY_ROWS
+#endif  // MIGAN_PIPE_HPP_

@@ -6,6 +6,7 @@
 namespace migan {
 
 typedef void (*SepKernelFn)(const SepArgs);
+typedef void (*SepRowKernelFn)(const SepRowArgs);      // the per-row form of a family (migan_kernels.hpp, SepRowArgs); null in a table: no samples plan reaches that row
 
 struct KernelEntry {
   int mode, MT, NT, KC;
@@ -17,12 +18,23 @@ struct KernelEntry {
   int stv;
   SepKernelFn fn;
   const char* name;     // the symbol as rocprofv3 prints it
+  SepRowKernelFn rows_fn;
+  const char* rows_name;
 };
+
+// per-row noise is a property of synthesis layers: plain and FIR-up tiles without FromRGB (the pointwise GEMM is the encoder's down=2 layer)
+template <int MODE, int MT, int NT, int KC, bool RGB, int NI, int MINW, bool MAING, bool PERSIST, int GEMMV, bool TORGB, int STV>
+inline SepRowKernelFn sepconv_rows_fn() {
+  if constexpr (RGB || MODE == MODE_PW) return nullptr;
+  else return sepconv_rows_kernel<MODE, MT, NT, KC, RGB, NI, MINW, MAING, PERSIST, GEMMV, TORGB, STV>;
+}
 
 #define MIGAN_K(MODE, MT, NT, KC, RGB, NI, MINW, MAING, PERSIST, GEMMV, TORGB, STV)                                              \
   {MODE, MT, NT, KC, RGB, NI, MINW, MAING, PERSIST, GEMMV, TORGB, STV,                                                           \
    sepconv_kernel<MODE, MT, NT, KC, RGB, NI, MINW, MAING, PERSIST, GEMMV, TORGB, STV>,                                            \
-   "migan::sepconv_kernel<" #MODE ", " #MT ", " #NT ", " #KC ", " #RGB ", " #NI ", " #MINW ", " #MAING ", " #PERSIST ", " #GEMMV ", " #TORGB ", " #STV ">"}
+   "migan::sepconv_kernel<" #MODE ", " #MT ", " #NT ", " #KC ", " #RGB ", " #NI ", " #MINW ", " #MAING ", " #PERSIST ", " #GEMMV ", " #TORGB ", " #STV ">", \
+   sepconv_rows_fn<MODE, MT, NT, KC, RGB, NI, MINW, MAING, PERSIST, GEMMV, TORGB, STV>(),                                         \
+   "migan::sepconv_rows_kernel<" #MODE ", " #MT ", " #NT ", " #KC ", " #RGB ", " #NI ", " #MINW ", " #MAING ", " #PERSIST ", " #GEMMV ", " #TORGB ", " #STV ">"}
 
 // Every tile geometry the host plan can pick (choose_geo), for one GEMM variant G and one storage format S.
 //   MODE 0 plain / 2 FIR-up / 3 pointwise GEMM (second half of FIR-down layers); MT x NT GEMM tile; KC channels per K chunk;
@@ -94,6 +106,8 @@ struct PipeEntry {
   SepKernelFn fn;
   const char* name;     // the symbol as rocprofv3 prints it
   size_t lds_bytes;
+  SepRowKernelFn rows_fn;      // (null: the fused-FromRGB forms)
+  const char* rows_name;
 };
 struct PipeSlice {
   const PipeEntry* entries;

@@ -24,7 +24,12 @@
 // LDS: 3 x 20.25 KB input + 64 KB weight planes + 2 x 16 KB A planes + 3 x 640 B taps = 159.1 KB.  fp32 storage, f16x2 GEMM.
 // Measured: -22 .. -24 % per layer against the 128 x 256 tile; what bounds it now and the variants that were built, measured and dropped
 // (loader wave, DMAs on the MFMA waves, 16-byte stores, activation + split on the MFMA waves, lookahead 2, stagger): profiles/r05_wide2.md.
-#pragma once
+#if !defined(MIGAN_WIDE2_HPP_) || defined(MIGAN_BODY_ROWS)
+// The kernel text between the "#endif  // !MIGAN_BODY_ROWS" lines of this file is compiled twice: this file includes itself once, with
+// MIGAN_BODY_ROWS defined as 1, and then emits only that text, as the per-row form (SepRowArgs, migan_kernels.hpp) of the same kernel.  The
+// plain kernel so keeps the parameter and the text it always had; ROWS / MIGAN_BODY_ROWS mark the only places where the two differ.
+#ifndef MIGAN_BODY_ROWS
+#define MIGAN_WIDE2_HPP_
 
 namespace migan {
 
@@ -54,8 +59,24 @@ template <int N> struct W2Int { static constexpr int value = N; };
 // row = 64 bytes: a DMA of half rows touches 32 rows x 32 bytes = sixteen half-used cache lines per instruction and measured 195 cycles at
 // issue (profiles/r05_wide2.md), one of whole rows sixteen rows x 64 bytes = eight full lines.  (A template also so that translation units
 // that only need W2Lds do not emit the kernel.)
+// ROWS: per-row noise planes (SepRowArgs, migan_kernels.hpp; these layers have no skip tensor): sepconv_wide2_rows_kernel, this text compiled a
+// second time (top of the file)
+#endif  // !MIGAN_BODY_ROWS
 template <int V>
+#if MIGAN_BODY_ROWS
+MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(kW2Threads, 3) sepconv_wide2_rows_kernel(const SepRowArgs ra) {
+  constexpr bool ROWS = true;
+  const SepArgs& p = ra.a;
+  const int samples = ra.samples;
+  const unsigned noise_stride = ra.noise_stride;
+#else
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(kW2Threads, 3) sepconv_wide2_kernel(const SepArgs p) {
+  constexpr bool ROWS = false;
+  constexpr int samples = 1;
+  constexpr unsigned noise_stride = 0u;
+#endif
+  (void)samples; (void)noise_stride;
+  static_assert(!ROWS || !(V & 2), "per-row noise: synthesis layers");
   typedef W2Lds L;
   constexpr int KS = 16, GW = 16, IGW = 18, NPIX = 18 * 18, NITEMS = NPIX * 4;     // 1296 16-byte units per input slot
   constexpr int AT = kW2AWaves * 64;
@@ -367,7 +388,12 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(kW2Threads, 3) sepconv_wide2_kernel(const 
     if (has_noise) {
       int ln = lane;
       MIGAN_OPAQUE(ln);                                          // (recomputed per tile: hoisted out of the persistent loop these lane terms cost registers the MFMA steps need)
+#if MIGAN_BODY_ROWS
+      const float* nzp = p.noise + (size_t)ctc.b * noise_stride;      // plane of row ctc.b: a uniform base, like the plane itself
+      nzl = nzp[(unsigned)((ctc.y * 16 + wm * 4 + (ln >> 4)) * p.W + ctc.x * 16 + (ln & 15))];
+#else
       nzl = p.noise[(unsigned)((ctc.y * 16 + wm * 4 + (ln >> 4)) * p.W + ctc.x * 16 + (ln & 15))];
+#endif
     }
   };
   auto epilogue = [&](auto hn_) {
@@ -435,5 +461,11 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(kW2Threads, 3) sepconv_wide2_kernel(const 
   }
   PPROF_END(AT);
 }
+#ifndef MIGAN_BODY_ROWS
+#define MIGAN_BODY_ROWS 1
+#include "migan_wide2.hpp"
+#undef MIGAN_BODY_ROWS
 
 }  // namespace migan
+#endif  // !MIGAN_BODY_ROWS
+#endif  // MIGAN_WIDE2_HPP_

@@ -79,6 +79,8 @@ EXPORTS = (
 # include/comodgan_samples_hip.h
 SAMPLES_EXPORTS = ("comodgan_workspace_bytes_samples", "comodgan_forward_samples", "comodgan_forward_samples_timed",
                    "comodgan_debug_tensor_samples")
+# include/migan_noise_samples_hip.h
+NOISE_SAMPLES_EXPORTS = ("migan_noise_floats_hw", "migan_workspace_bytes_samples_hw", "migan_forward_samples_hw", "migan_sepconv_forward_samples")
 # include/migan_pipeline_samples_hip.h
 PIPELINE_SAMPLES_EXPORTS = ("migan_pipeline_batch_post_samples",)
 # include/migan_pipeline_patches_hip.h
@@ -260,7 +262,7 @@ class MiganLib:
         except OSError as e:  # pragma: no cover - depends on the machine
             raise MiganError(f"cannot load {self.path}: {e}") from e
         L = self.lib
-        for name in (EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + PIPELINE_PATCHES_EXPORTS + PIPELINE_REGIONS_EXPORTS + PIPELINE_REGION_PATCHES_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS
+        for name in (EXPORTS + SAMPLES_EXPORTS + NOISE_SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + PIPELINE_PATCHES_EXPORTS + PIPELINE_REGIONS_EXPORTS + PIPELINE_REGION_PATCHES_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS
                      + U8_EXPORTS + METRICS_EXPORTS + PHOTO_EXPORTS + MASKS_EXPORTS):
             if not hasattr(L, name):
                 raise MiganError(f"{self.path} does not export {name}")
@@ -274,6 +276,10 @@ class MiganLib:
         L.migan_workspace_bytes_hw.argtypes = [vp, ci, ci, ci, C.POINTER(C.c_size_t)]
         L.migan_forward_hw.argtypes = [vp, vp, vp, ci, ci, ci, vp, C.c_size_t, vp]
         L.migan_forward_u8.argtypes = [vp, vp, vp, vp, ci, vp, C.c_size_t, vp]
+        L.migan_noise_floats_hw.argtypes = [vp, ci, ci, C.POINTER(C.c_size_t)]
+        L.migan_workspace_bytes_samples_hw.argtypes = [vp, ci, ci, ci, ci, C.POINTER(C.c_size_t)]
+        L.migan_forward_samples_hw.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp, C.c_size_t, vp]
+        L.migan_sepconv_forward_samples.argtypes = [C.POINTER(SepConvDesc), ci, vp]
         L.migan_forward_split.argtypes = [vp, ci, C.POINTER(ci), C.POINTER(ci)]
         L.migan_forward_parts.argtypes = [vp, vp, C.POINTER(vp), ci, vp, C.c_size_t, vp, C.POINTER(vp), ci, C.POINTER(ci), C.POINTER(ci)]
         L.migan_pipeline_mask_resize.argtypes = [vp, ci, ci, vp, ci, ci, vp]
@@ -577,7 +583,8 @@ class MiganLib:
         self.check(self.lib.migan_masks_raster(C.c_void_p(plans_ptr or None), int(words), int(count), int(resolution), C.c_void_p(out_ptr or None),
                                                C.c_void_p(holes_ptr or None), C.c_void_p(stream)))
 
-    def sepconv_forward(self, stream: int = 0, **kw) -> None:
+    def sepconv_forward(self, stream: int = 0, samples: Optional[int] = None, **kw) -> None:
+        """samples: migan_sepconv_forward_samples -- noise_const is [batch][res_out][width_out] (one plane per row), skip [batch / samples]..."""
         d = SepConvDesc()
         for f, _ in SepConvDesc._fields_:
             setattr(d, f, kw.pop(f, None if f not in ("batch", "cin", "cout", "res_in", "down", "up", "scratch_bytes", "wsplit_bytes",
@@ -586,6 +593,9 @@ class MiganLib:
             raise TypeError(f"unknown sepconv fields: {sorted(kw)}")
         d.down = d.down or 1
         d.up = d.up or 1
+        if samples is not None:
+            self.check(self.lib.migan_sepconv_forward_samples(C.byref(d), int(samples), C.c_void_p(stream)))
+            return
         self.check(self.lib.migan_sepconv_forward(C.byref(d), C.c_void_p(stream)))
 
 
@@ -681,6 +691,22 @@ class MiganHandle:
     def forward_hw(self, x_ptr: int, y_ptr: int, batch: int, height: int, width: int, ws_ptr: int, ws_bytes: int, stream: int = 0) -> None:
         self.lib.check(self.lib.lib.migan_forward_hw(self._h, C.c_void_p(x_ptr), C.c_void_p(y_ptr), int(batch), int(height), int(width),
                                                      C.c_void_p(ws_ptr), C.c_size_t(ws_bytes), C.c_void_p(stream)))
+
+    def noise_floats_hw(self, height: int, width: int) -> int:
+        n = C.c_size_t()
+        self.lib.check(self.lib.lib.migan_noise_floats_hw(self._h, int(height), int(width), C.byref(n)))
+        return int(n.value)
+
+    def workspace_bytes_samples_hw(self, n_images: int, samples: int, height: int, width: int) -> int:
+        n = C.c_size_t()
+        self.lib.check(self.lib.lib.migan_workspace_bytes_samples_hw(self._h, int(n_images), int(samples), int(height), int(width), C.byref(n)))
+        return int(n.value)
+
+    def forward_samples_hw(self, x_ptr: int, noise_ptr: int, y_ptr: int, n_images: int, samples: int, height: int, width: int, ws_ptr: int,
+                           ws_bytes: int, stream: int = 0) -> None:
+        self.lib.check(self.lib.lib.migan_forward_samples_hw(self._h, C.c_void_p(x_ptr), C.c_void_p(noise_ptr), C.c_void_p(y_ptr), int(n_images),
+                                                             int(samples), int(height), int(width), C.c_void_p(ws_ptr), int(ws_bytes),
+                                                             C.c_void_p(stream)))
 
     def forward_u8(self, img_ptr: int, mask_ptr: int, out_ptr: int, batch: int, ws_ptr: int, ws_bytes: int, stream: int = 0) -> None:
         self.lib.check(self.lib.lib.migan_forward_u8(self._h, C.c_void_p(img_ptr), C.c_void_p(mask_ptr), C.c_void_p(out_ptr), int(batch),

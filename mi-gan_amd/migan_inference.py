@@ -453,6 +453,65 @@ class Generator(nn.Module):
         h.forward_hw(x.data_ptr(), y.data_ptr(), n, hh, ww, ws.data_ptr(), ws.numel(), self._stream(x))
         return y
 
+    # ------------------------------------------------------------------ S completions per image from per-sample noise
+    # The reference's TRAINING generator (lib/model_zoo/migan.py:130-138, noise_mode='random') adds torch.randn([N,1,H,W]) * noise_strength in
+    # every synthesis SeparableConv2d with use_noise -- a fresh noise image per batch row; the exported module froze that to noise_const.  The
+    # methods below take the draw as an input: one blob of noise_floats() values per output row = the planes of synthesis.b8.conv1, b8.conv2,
+    # b16.conv1, ... in that order, each [h,w] of its layer (include/migan_noise_samples_hip.h).
+    def _noise_layers(self, hw: Optional[Tuple[int, int]] = None) -> List[Tuple[str, int, int]]:
+        r = self.resolution
+        hh, ww = (r, r) if hw is None else (int(hw[0]), int(hw[1]))
+        if hh < r // 4 or ww < r // 4 or hh % (r // 4) or ww % (r // 4):
+            raise RuntimeError(f"height and width must be positive multiples of resolution / 4 = {r // 4}, got {hh} x {ww}")
+        out, res = [], 8
+        while res <= r:
+            for conv in ("conv1", "conv2"):
+                out.append((f"synthesis.b{res}.{conv}.noise_const", hh * res // r, ww * res // r))
+            res *= 2
+        return out
+
+    def noise_floats(self, hw: Optional[Tuple[int, int]] = None) -> int:
+        """F: floats of one row's noise blob for inputs of size hw = (H, W) (default: resolution x resolution)."""
+        return sum(h * w for _, h, w in self._noise_layers(hw))
+
+    def const_noise(self, hw: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+        """[F]: the model's own noise_const planes as a blob.  For H x W each plane is tiled periodically and cropped to its layer's size, as
+        forward_any_size does: forward_noise_samples with this blob for every row gives forward_any_size's bits."""
+        bufs = dict(self.named_buffers())
+        planes = []
+        for name, h, w in self._noise_layers(hw):
+            c = bufs[name]
+            r = c.shape[0]
+            planes.append(c.repeat((h + r - 1) // r, (w + r - 1) // r)[:h, :w].reshape(-1))
+        return torch.cat(planes).contiguous()
+
+    def forward_noise_samples(self, x: torch.Tensor, noise: Optional[torch.Tensor] = None, samples: Optional[int] = None) -> torch.Tensor:
+        """x [N,4,H,W] (H, W as forward_any_size) and noise [N,S,F] on x's device -> [N,S,3,H,W]: completion s of image i is the reference
+        module's forward of x[i] with every noisy layer's noise_const replaced by that row's plane (= the training generator's
+        noise_mode='random' with the draw given).  The encoder and synthesis.b4 have no noise and run once per image.  With samples=S and no
+        noise the blobs are drawn with torch.randn on x's device."""
+        x = self._check_input(x, any_size=True)
+        n, hh, ww = x.shape[0], int(x.shape[2]), int(x.shape[3])
+        f = self.noise_floats((hh, ww))
+        if noise is None:
+            if samples is None or int(samples) < 1:
+                raise RuntimeError("forward_noise_samples needs noise [N,S,F] or samples >= 1")
+            noise = torch.randn((n, int(samples), f), dtype=torch.float32, device=x.device)
+        if noise.dim() != 3 or noise.shape[0] != n or noise.shape[1] < 1 or noise.shape[2] != f or (samples is not None and int(samples) != noise.shape[1]):
+            raise RuntimeError(f"expected noise of shape [{n}, S, {f}]" + (f" with S = {samples}" if samples is not None else "") + f", got {list(noise.shape)}")
+        if noise.dtype != torch.float32 or noise.device != x.device:
+            raise RuntimeError(f"noise must be float32 on {x.device}, got {noise.dtype} on {noise.device}")
+        noise = noise.contiguous()
+        s = int(noise.shape[1])
+        h = self._engine(x)
+        need = h.workspace_bytes_samples_hw(n, s, hh, ww)
+        if self._ws is None or self._ws.device != x.device or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        y = torch.empty((n, s, 3, hh, ww), dtype=torch.float32, device=x.device)
+        h.forward_samples_hw(x.data_ptr(), noise.data_ptr(), y.data_ptr(), n, s, hh, ww, self._ws.data_ptr(), self._ws.numel(), self._stream(x))
+        return y
+
     def forward_uint8(self, img_u8: torch.Tensor, mask_u8: torch.Tensor) -> torch.Tensor:
         """scripts/demo.py:56-66 + forward + :135-140 in one call, at network resolution: uint8 image [N,R,R,3] (HWC) and
         uint8 mask [N,R,R] (255 = known pixel) -> composited uint8 image [N,R,R,3].  preprocess() runs inside the first
@@ -491,3 +550,34 @@ class Generator(nn.Module):
             self._lib = load_library(nan_policy=self._nan_policy)
         h = self._handle or MiganHandle(self._lib, self.resolution, 0, dtype=self._act_dtype)
         return h.launches()        # kernel names reflect the variants used by the last forward on this handle
+
+
+class NoiseSampler(nn.Module):
+    """An MI-GAN generator as a model with several completions per image: its "latent" is the noise blob of ``forward_noise_samples``.
+
+    ``MIGAN_Pipeline(NoiseSampler(G), R)`` serves ``forward_samples``, ``forward_patches``, ``forward_region_patches`` and ``paste_patches``
+    with S completions per image from one encoder pass (a plain ``Generator`` stays a one-completion model there).  ``z_dim`` is
+    ``noise_floats()`` -- 699,008 floats per row at resolution 512 -- and the pipeline draws a missing ``z`` on the CPU before moving it to the
+    device, so at 512 callers should pass ``z`` drawn on the device: ``torch.randn(N, S, sampler.z_dim, device=...)``."""
+
+    def __init__(self, generator: Generator):
+        super().__init__()
+        self.generator = generator
+
+    @property
+    def resolution(self) -> int:
+        return self.generator.resolution
+
+    @property
+    def z_dim(self) -> int:
+        return self.generator.noise_floats()
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """the one completion the exported module gives (noise_const)"""
+        return self.generator(x)
+
+    def forward_samples(self, x: torch.Tensor, z: Optional[torch.Tensor] = None, samples: Optional[int] = None) -> torch.Tensor:
+        """x [N,4,R,R], z [N,S,z_dim] (or samples=S to draw it on x's device) -> [N,S,3,R,R]"""
+        if z is not None and z.dtype != torch.float32:
+            z = z.float()
+        return self.generator.forward_noise_samples(x, z, samples)
