@@ -21,24 +21,16 @@ CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
 OUT = os.path.join(CSRC, "libmigan_hip.so")
 OBJ = os.path.join(CSRC, "_obj")
-SOURCES = [os.path.join(CSRC, f) for f in ("migan_hip.hip", "migan_k_slice.hip", "migan_k_slice.inc", "migan_table.hpp",
-                                            "migan_pipe.hip", "migan_pipe.hpp", "migan_pipe_table.inc",
-                                            "migan_wide2.hip", "migan_wide2.hpp", "migan_wide2_table.inc",
-                                            "migan_kernels.hpp", "migan_host.hpp", "migan_rt_hip.h",
-                                            "comodgan_kernels.hpp", "comodgan_conv_body.inc", "comodgan_fir_body.inc", "comodgan_fromrgb_body.inc",
-                                            "comodgan_torgb_body.inc", "comodgan_host.hpp", "comodgan_u8.hip", "migan_pipeline.hpp",
-                                            "migan_pipeline_pool_body.inc", "migan_pipeline_samples_body.inc", "migan_pipeline_regions.inc",
-                                            "migan_pipeline_region_patches.inc",
-                                            "migan_metrics.hpp", "migan_metrics.hip", "migan_photo.hpp", "migan_photo.hip",
-                                            "migan_masks.hpp", "migan_masks_host.hpp", "migan_masks.hip")] + [
-    os.path.join(ROOT, "include", "migan_hip.h"), os.path.join(ROOT, "include", "comodgan_hip.h"),
-    os.path.join(ROOT, "include", "comodgan_samples_hip.h"), os.path.join(ROOT, "include", "migan_pipeline_samples_hip.h"),
-    os.path.join(ROOT, "include", "migan_pipeline_patches_hip.h"), os.path.join(ROOT, "include", "migan_pipeline_regions_hip.h"),
-    os.path.join(ROOT, "include", "migan_pipeline_region_patches_hip.h"),
-    os.path.join(ROOT, "include", "comodgan_fp16_hip.h"), os.path.join(ROOT, "include", "comodgan_fp16_storage_hip.h"),
-    os.path.join(ROOT, "include", "comodgan_stages_hip.h"), os.path.join(ROOT, "include", "comodgan_u8_hip.h"),
-    os.path.join(ROOT, "include", "migan_metrics_hip.h"), os.path.join(ROOT, "include", "migan_photo_hip.h"),
-    os.path.join(ROOT, "include", "migan_masks_hip.h"), os.path.join(ROOT, "include", "migan_noise_samples_hip.h")]
+
+
+def sources() -> List[str]:
+    """what the library is built from, read from the directories so that a new file cannot be forgotten: every source under csrc/ and
+    the public headers"""
+    inc = os.path.join(ROOT, "include")
+    return (sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".hpp", ".inc", ".h")))
+            + sorted(os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h")))
+
+
 ARCH = "gfx950"
 # (GEMM variant, activation storage format) slices of the sepconv_kernel table; 16-bit storage is built for the fp16 GEMM variants (f16x2 = 2, f16 = 3)
 SLICES: Sequence[Tuple[int, int]] = ((0, 0), (1, 0), (2, 0), (2, 1), (2, 2), (3, 1), (3, 2))
@@ -87,7 +79,7 @@ def is_fresh(extra: Sequence[str] = ()) -> bool:
         return False
     if open(STAMP).read().strip() != flags_digest(extra):
         return False
-    return os.path.getmtime(OUT) >= max(os.path.getmtime(s) for s in SOURCES)
+    return os.path.getmtime(OUT) >= max(os.path.getmtime(s) for s in sources())
 
 
 def build(force: bool = False, verbose: bool = False, extra: Sequence[str] = (), jobs: int = 0, lint: bool = True) -> str:
@@ -156,7 +148,7 @@ def build_variant(name: str, extra: Sequence[str], force: bool = False, verbose:
     out = os.path.join(CSRC, f"libmigan_hip_{name}.so")
     stamp = out + ".flags"
     if (not force and os.path.exists(out) and os.path.exists(stamp) and open(stamp).read().strip() == flags_digest(extra)
-            and os.path.getmtime(out) >= max(os.path.getmtime(s) for s in SOURCES)):
+            and os.path.getmtime(out) >= max(os.path.getmtime(s) for s in sources())):
         return out
     obj = os.path.join(CSRC, f"_obj_{name}")
     os.makedirs(obj, exist_ok=True)

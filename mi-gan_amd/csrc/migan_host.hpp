@@ -16,6 +16,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/migan_hip.h"
@@ -1660,6 +1661,63 @@ inline void migan_handle::forward_samples(migan::Plan& P, const float* x, const 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Kernels that take a table of items by value (migan_pipeline.hpp, "the batch form"): the host half, once, for the deployed
+// pipeline's entry points, the metrics and the photo resize.  Such a kernel's argument holds item[N], first[N + 1] and n; item i of
+// a call has tiles(i) workgroups (0: it takes no part), and a call with more items or workgroups than one launch carries is
+// several launches on the stream, one after the other.
+namespace migan {
+struct TableLaunch {
+  int i0, k;                         // items [i0, i0 + k)
+  unsigned long long total;          // their workgroups
+};
+constexpr unsigned long long kTableGroupsMax = 0x7fffffffull;    // a 1-D grid
+template <class Args>
+constexpr int table_items = (int)std::extent<decltype(Args::item)>::value;
+
+// The split, no HIP call: a launch takes the next item while it holds fewer than max_items and the item's workgroups still fit
+// under max_groups.  An item that alone exceeds max_groups is refused, so the first item of a launch always fits.
+template <class Tiles>
+inline std::vector<TableLaunch> table_split(int n, Tiles tiles, int max_items, unsigned long long max_groups = kTableGroupsMax) {
+  std::vector<TableLaunch> out;
+  TableLaunch l{0, 0, 0};
+  for (int i = 0; i < n; ++i) {
+    const unsigned long long t = tiles(i);
+    MIGAN_CHECK(t <= max_groups, MIGAN_EINVAL, "item " + std::to_string(i) + ": image too large");
+    if (l.k == max_items || l.total + t > max_groups) {
+      out.push_back(l);
+      l = TableLaunch{i, 0, 0};
+    }
+    ++l.k;
+    l.total += t;
+  }
+  if (l.k) out.push_back(l);
+  return out;
+}
+// One launch: a copy of `proto` with fill(a, j, i) for item i in slot j, first[] and n, then advance(a, i0) for the base pointers
+// that move with the first item.  Nothing is launched for a chunk without workgroups.  Returns the argument (metrics_final_kernel
+// reads the same table).
+template <class Args, class Tiles, class Fill, class Advance>
+inline Args table_launch(void (*kernel)(const Args), const char* name, const Args& proto, const TableLaunch& l, Tiles tiles, Fill fill,
+                         Advance advance, unsigned threads, size_t lds, void* stream) {
+  static_assert(std::extent<decltype(Args::first)>::value == table_items<Args> + 1, "first[] is a prefix over item[]");
+  MIGAN_CHECK(l.k >= 1 && l.k <= table_items<Args>, MIGAN_ERUNTIME, "more items than the kernel's table holds");
+  Args a = proto;
+  unsigned long long total = 0;
+  for (int j = 0; j < l.k; ++j) {
+    fill(a, j, l.i0 + j);
+    a.first[j] = (int)total;
+    total += tiles(l.i0 + j);
+  }
+  a.first[l.k] = (int)total;
+  a.n = l.k;
+  advance(a, l.i0);
+  MIGAN_CHECK(total <= kTableGroupsMax, MIGAN_EINVAL, "too many workgroups in one launch");
+  if (total) rt_check(rt::launch(kernel, a, (unsigned)total, threads, lds, (rt::stream_t)stream), name);
+  return a;
+}
+}  // namespace migan
+
+// ------------------------------------------------------------------------------------------------
 // C ABI
 
 #define MIGAN_API_BEGIN try {
@@ -2128,10 +2186,40 @@ int migan_compose_output(const void* y_nchw, const void* img_hwc_u8, const void*
 }
 
 // ---- the deployed pipeline around the generator (reference scripts/create_onnx_pipeline.py::MIGAN_Pipeline :118-264) ----
+// The checks of one image, item or row, stated once.  (kind, index) is ("item", 3) or ("row", 3), or (nullptr, 0) for the
+// single-image calls; the text "item 3: " is put together only for a refusal.  2^30 pixels bound every 32-bit pixel index of the
+// kernels and keep an item's workgroups far below a grid's 2^31.
+static std::string migan_pipeline_who(const char* kind, int index) {
+  return kind ? std::string(kind) + " " + std::to_string(index) + ": " : std::string();
+}
+static void migan_pipeline_check_image(const char* kind, int index, int height, int width,
+                                       const char* why = " (reflect padding of the 5x5 blur)") {
+  MIGAN_CHECK(height >= 3 && width >= 3 && (unsigned long long)height * width < (1ull << 30), MIGAN_EINVAL,
+              migan_pipeline_who(kind, index) + "image must be at least 3x3" + why + " and below 2^30 pixels");
+}
+static void migan_pipeline_check_mask(const char* kind, int index, int mask_height, int mask_width) {
+  MIGAN_CHECK(mask_height > 0 && mask_width > 0 && (unsigned long long)mask_height * mask_width < (1ull << 30), MIGAN_EINVAL,
+              migan_pipeline_who(kind, index) + "bad mask size");
+}
+// a region of an image: its label, the label map that a label above 0 is looked up in, and its crop
+static void migan_pipeline_check_region(const char* kind, int index, int label, const void* labels_u8, const int box[4], int height,
+                                        int width) {
+  MIGAN_CHECK(label >= 0 && label <= migan::kRegionsCap, MIGAN_EINVAL, migan_pipeline_who(kind, index) + "label must be in 0 ... 64");
+  MIGAN_CHECK(label == 0 || labels_u8, MIGAN_EINVAL, migan_pipeline_who(kind, index) + "a label above 0 needs the label map");
+  MIGAN_CHECK(box[0] >= 0 && box[1] <= width && box[2] >= 0 && box[3] <= height && box[1] - box[0] >= 3 && box[3] - box[2] >= 3,
+              MIGAN_EINVAL, migan_pipeline_who(kind, index) + "box = {x_min, x_max, y_min, y_max} must lie inside the image and be at least 3x3");
+}
+// the crop's tiles: the grid of pipe_post_rows_kernel, pipe_post_rows_patches_kernel and pipe_paste_rows_kernel
+static unsigned long long migan_pipeline_box_tiles(const int* box) {
+  return (unsigned long long)migan::cdiv(box[1] - box[0], migan::kPostTW) * (unsigned long long)migan::cdiv(box[3] - box[2], migan::kPostTH);
+}
+// an image's tiles: the grid of pipe_post_batch_kernel, _samples_ and _patches_, whose crop is on the device
+static unsigned long long migan_pipeline_image_tiles(int height, int width) {
+  return (unsigned long long)migan::cdiv(width, migan::kPostTW) * (unsigned long long)migan::cdiv(height, migan::kPostTH);
+}
 static void migan_pipeline_check(const void* mask, int height, int width, int resolution) {
   MIGAN_CHECK(mask, MIGAN_EINVAL, "null mask");
-  MIGAN_CHECK(height >= 3 && width >= 3 && (unsigned long long)height * width < (1ull << 30), MIGAN_EINVAL,
-              "image must be at least 3x3 (reflect padding of the 5x5 blur) and below 2^30 pixels");
+  migan_pipeline_check_image(nullptr, 0, height, width);
   MIGAN_CHECK(resolution >= 8 && (resolution & (resolution - 1)) == 0, MIGAN_EINVAL, "resolution must be a power of two >= 8");
 }
 static void migan_pipeline_check_bbox(const int bbox[4], int height, int width) {
@@ -2232,10 +2320,8 @@ static size_t migan_pipeline_batch_plan(const migan_pipeline_item* items, int n,
   for (int i = 0; i < n; ++i) {
     const migan_pipeline_item& it = items[i];
     MIGAN_CHECK(!need_pointers || (it.image_chw_u8 && it.mask_u8), MIGAN_EINVAL, "null image or mask in item " + std::to_string(i));
-    MIGAN_CHECK(it.height >= 3 && it.width >= 3 && (unsigned long long)it.height * it.width < (1ull << 30), MIGAN_EINVAL,
-                "item " + std::to_string(i) + ": image must be at least 3x3 (reflect padding of the 5x5 blur) and below 2^30 pixels");
-    MIGAN_CHECK(it.mask_height > 0 && it.mask_width > 0 && (unsigned long long)it.mask_height * it.mask_width < (1ull << 30), MIGAN_EINVAL,
-                "item " + std::to_string(i) + ": bad mask size");
+    migan_pipeline_check_image("item", i, it.height, it.width);
+    migan_pipeline_check_mask("item", i, it.mask_height, it.mask_width);
     const bool resize = it.mask_height != it.height || it.mask_width != it.width;
     if (out) {
       PipeBatchItem& b = (*out)[(size_t)i];
@@ -2248,31 +2334,22 @@ static size_t migan_pipeline_batch_plan(const migan_pipeline_item* items, int n,
   }
   return bytes;
 }
-// one kernel over all items, kPipeBatchMax (and fewer than 2^31 workgroups) per launch: tiles(item) workgroups for each
+// one kernel over all items (table_split, table_launch): tiles(item) workgroups for each; x, y and the boxes of a launch begin at its
+// first item
 extern "C++" template <class Tiles>
-static void migan_pipeline_batch_run(void (*kernel)(const migan::PipeBatchArgs), const char* name, const migan::PipeBatchArgs& proto,
-                                     const std::vector<migan::PipeBatchItem>& items, Tiles tiles, size_t lds, void* stream) {
+static void migan_pipeline_batch_launch(void (*kernel)(const migan::PipeBatchArgs), const char* name, const migan::PipeBatchArgs& proto,
+                                        const std::vector<migan::PipeBatchItem>& items, Tiles tiles, size_t lds, void* stream) {
   using namespace migan;
   const size_t plane = (size_t)proto.R * proto.R;
-  for (size_t i0 = 0; i0 < items.size();) {
-    PipeBatchArgs a = proto;
-    unsigned long long total = 0;
-    int k = 0;
-    for (; k < kPipeBatchMax && i0 + k < items.size(); ++k) {
-      const unsigned long long t = tiles(items[i0 + k]);
-      if (k > 0 && total + t > 0x7fffffffull) break;
-      a.item[k] = items[i0 + k];
-      a.first[k] = (int)total;
-      total += t;
-    }
-    a.first[k] = (int)total;
-    a.n = k;
-    if (a.x) a.x += i0 * 4 * plane;
-    if (a.y) a.y += i0 * 3 * plane;
-    a.bbox += i0 * 4;
-    if (total) rt_check(rt::launch(kernel, a, (unsigned)total, kThreads, lds, (rt::stream_t)stream), name);
-    i0 += (size_t)k;
-  }
+  const auto t = [&](int i) { return (unsigned long long)tiles(items[(size_t)i]); };
+  for (const TableLaunch& l : table_split((int)items.size(), t, table_items<PipeBatchArgs>))
+    table_launch(kernel, name, proto, l, t, [&](PipeBatchArgs& a, int j, int i) { a.item[j] = items[(size_t)i]; },
+                 [&](PipeBatchArgs& a, int i0) {
+                   if (a.x) a.x += (size_t)i0 * 4 * plane;
+                   if (a.y) a.y += (size_t)i0 * 3 * plane;
+                   a.bbox += (size_t)i0 * 4;
+                 },
+                 kThreads, lds, stream);
 }
 static void migan_pipeline_batch_check(int resolution, const int* bbox_dev, const void* scratch) {
   MIGAN_CHECK(resolution >= 8 && (resolution & (resolution - 1)) == 0, MIGAN_EINVAL, "resolution must be a power of two >= 8");
@@ -2296,15 +2373,15 @@ int migan_pipeline_batch_pre(const migan_pipeline_item* items, int n, int resolu
   PipeBatchArgs a{};
   a.x = (float*)x_nchw; a.bbox = bbox_dev; a.R = resolution; a.padding = padding;
   auto pixels = [](const PipeBatchItem& it) { return (unsigned long long)cdiv(it.H * it.W, kThreads); };
-  migan_pipeline_batch_run(pipe_mask_resize_batch_kernel, "migan::pipe_mask_resize_batch_kernel", a, its,
-                           [&](const PipeBatchItem& it) { return it.mask_resized ? pixels(it) : 0ull; }, 0, stream);
-  migan_pipeline_batch_run(pipe_flags_clear_batch_kernel, "migan::pipe_flags_clear_batch_kernel", a, its,
-                           [](const PipeBatchItem& it) { return (unsigned long long)cdiv(it.H + it.W, kThreads); }, 0, stream);
-  migan_pipeline_batch_run(pipe_flags_batch_kernel, "migan::pipe_flags_batch_kernel", a, its, pixels, 0, stream);
-  migan_pipeline_batch_run(pipe_bbox_batch_kernel, "migan::pipe_bbox_batch_kernel", a, its, [](const PipeBatchItem&) { return 1ull; },
-                           4 * kThreads * sizeof(int), stream);
+  migan_pipeline_batch_launch(pipe_mask_resize_batch_kernel, "migan::pipe_mask_resize_batch_kernel", a, its,
+                              [&](const PipeBatchItem& it) { return it.mask_resized ? pixels(it) : 0ull; }, 0, stream);
+  migan_pipeline_batch_launch(pipe_flags_clear_batch_kernel, "migan::pipe_flags_clear_batch_kernel", a, its,
+                              [](const PipeBatchItem& it) { return (unsigned long long)cdiv(it.H + it.W, kThreads); }, 0, stream);
+  migan_pipeline_batch_launch(pipe_flags_batch_kernel, "migan::pipe_flags_batch_kernel", a, its, pixels, 0, stream);
+  migan_pipeline_batch_launch(pipe_bbox_batch_kernel, "migan::pipe_bbox_batch_kernel", a, its, [](const PipeBatchItem&) { return 1ull; },
+                              4 * kThreads * sizeof(int), stream);
   const unsigned long long per_item = (unsigned long long)cdiv(resolution * resolution, kThreads);
-  migan_pipeline_batch_run(pipe_pre_batch_kernel, "migan::pipe_pre_batch_kernel", a, its, [=](const PipeBatchItem&) { return per_item; }, 0, stream);
+  migan_pipeline_batch_launch(pipe_pre_batch_kernel, "migan::pipe_pre_batch_kernel", a, its, [=](const PipeBatchItem&) { return per_item; }, 0, stream);
   MIGAN_API_END
 }
 // postprocess (:241-250) and the paste back (:263) of every item, in place; the crop of item i is row i of bbox_dev
@@ -2320,9 +2397,8 @@ int migan_pipeline_batch_post(const migan_pipeline_item* items, int n, int resol
   a.y = (const float*)y_nchw; a.bbox = const_cast<int*>(bbox_dev); a.R = resolution;
   migan_pipeline_gauss(gauss25, a.gauss);
   // the crop is on the device: the grid covers each item's whole image, the workgroups past the crop's tiles leave at once
-  migan_pipeline_batch_run(pipe_post_batch_kernel, "migan::pipe_post_batch_kernel", a, its,
-                           [](const PipeBatchItem& it) { return (unsigned long long)cdiv(it.W, kPostTW) * (unsigned long long)cdiv(it.H, kPostTH); },
-                           (size_t)kPostLdsBytes, stream);
+  migan_pipeline_batch_launch(pipe_post_batch_kernel, "migan::pipe_post_batch_kernel", a, its,
+                              [](const PipeBatchItem& it) { return migan_pipeline_image_tiles(it.H, it.W); }, (size_t)kPostLdsBytes, stream);
   MIGAN_API_END
 }
 // the same for `samples` generator outputs per item, out of place: item i and y rows i * samples ... -> outs[i] = [samples][3][H][W].
@@ -2343,27 +2419,15 @@ int migan_pipeline_batch_post_samples(const migan_pipeline_item* items, int n, i
   proto.y = (const float*)y_nchw; proto.bbox = bbox_dev; proto.R = resolution; proto.S = samples;
   migan_pipeline_gauss(gauss25, proto.gauss);
   const size_t plane = (size_t)resolution * resolution;
-  for (size_t i0 = 0; i0 < its.size();) {
-    PipeSamplesArgs a = proto;
-    unsigned long long total = 0;
-    int k = 0;
-    for (; k < kPipeSamplesMax && i0 + k < its.size(); ++k) {
-      const PipeBatchItem& it = its[i0 + k];
-      const unsigned long long t = (unsigned long long)cdiv(it.W, kPostTW) * (unsigned long long)cdiv(it.H, kPostTH);
-      if (k > 0 && total + t > 0x7fffffffull) break;
-      a.item[k] = PipeSamplesItem{it.image, it.mask_resized ? it.mask_resized : it.mask_src, (unsigned char*)outs[i0 + k], it.H, it.W};
-      a.first[k] = (int)total;
-      total += t;
-    }
-    a.first[k] = (int)total;
-    a.n = k;
-    a.y += i0 * (size_t)samples * 3 * plane;
-    a.bbox += i0 * 4;
-    if (total)
-      rt_check(rt::launch(pipe_post_samples_kernel, a, (unsigned)total, kThreads, (size_t)kPostLdsBytes, (rt::stream_t)stream),
-               "migan::pipe_post_samples_kernel");
-    i0 += (size_t)k;
-  }
+  const auto tiles = [&](int i) { return migan_pipeline_image_tiles(its[(size_t)i].H, its[(size_t)i].W); };
+  for (const TableLaunch& l : table_split(n, tiles, table_items<PipeSamplesArgs>))
+    table_launch(pipe_post_samples_kernel, "migan::pipe_post_samples_kernel", proto, l, tiles,
+                 [&](PipeSamplesArgs& a, int j, int i) {
+                   const PipeBatchItem& it = its[(size_t)i];
+                   a.item[j] = PipeSamplesItem{it.image, it.mask_resized ? it.mask_resized : it.mask_src, (unsigned char*)outs[i], it.H, it.W};
+                 },
+                 [&](PipeSamplesArgs& a, int i0) { a.y += (size_t)i0 * samples * 3 * plane; a.bbox += (size_t)i0 * 4; },
+                 kThreads, (size_t)kPostLdsBytes, stream);
   MIGAN_API_END
 }
 // the same S outputs per item as box-sized patches: item i -> outs[i] = [samples][3][ch_i][cw_i], the crop alone.  The box is on the
@@ -2387,28 +2451,16 @@ int migan_pipeline_batch_post_patches(const migan_pipeline_item* items, int n, i
   proto.y = (const float*)y_nchw; proto.bbox = bbox_dev; proto.R = resolution; proto.S = samples;
   migan_pipeline_gauss(gauss25, proto.gauss);
   const size_t plane = (size_t)resolution * resolution;
-  for (size_t i0 = 0; i0 < its.size();) {
-    PipePatchesArgs a = proto;
-    unsigned long long total = 0;
-    int k = 0;
-    for (; k < kPipePatchesMax && i0 + k < its.size(); ++k) {
-      const PipeBatchItem& it = its[i0 + k];
-      const unsigned long long t = (unsigned long long)cdiv(it.W, kPostTW) * (unsigned long long)cdiv(it.H, kPostTH);
-      if (k > 0 && total + t > 0x7fffffffull) break;
-      a.item[k] = PipePatchesItem{it.image, it.mask_resized ? it.mask_resized : it.mask_src, (unsigned char*)outs[i0 + k],
-                                  (unsigned long long)out_bytes[i0 + k], it.H, it.W};
-      a.first[k] = (int)total;
-      total += t;
-    }
-    a.first[k] = (int)total;
-    a.n = k;
-    a.y += i0 * (size_t)samples * 3 * plane;
-    a.bbox += i0 * 4;
-    if (total)
-      rt_check(rt::launch(pipe_post_patches_kernel, a, (unsigned)total, kThreads, (size_t)kPostLdsBytes, (rt::stream_t)stream),
-               "migan::pipe_post_patches_kernel");
-    i0 += (size_t)k;
-  }
+  const auto tiles = [&](int i) { return migan_pipeline_image_tiles(its[(size_t)i].H, its[(size_t)i].W); };
+  for (const TableLaunch& l : table_split(n, tiles, table_items<PipePatchesArgs>))
+    table_launch(pipe_post_patches_kernel, "migan::pipe_post_patches_kernel", proto, l, tiles,
+                 [&](PipePatchesArgs& a, int j, int i) {
+                   const PipeBatchItem& it = its[(size_t)i];
+                   a.item[j] = PipePatchesItem{it.image, it.mask_resized ? it.mask_resized : it.mask_src, (unsigned char*)outs[i],
+                                               (unsigned long long)out_bytes[i], it.H, it.W};
+                 },
+                 [&](PipePatchesArgs& a, int i0) { a.y += (size_t)i0 * samples * 3 * plane; a.bbox += (size_t)i0 * 4; },
+                 kThreads, (size_t)kPostLdsBytes, stream);
   MIGAN_API_END
 }
 
@@ -2428,10 +2480,8 @@ static size_t migan_pipeline_regions_plan(const migan_pipeline_item* items, int 
   for (int i = 0; i < n; ++i) {
     const migan_pipeline_item& it = items[i];
     MIGAN_CHECK(!out || (it.mask_u8 && labels[i]), MIGAN_EINVAL, "null mask or label map of item " + std::to_string(i));
-    MIGAN_CHECK(it.height >= 3 && it.width >= 3 && (unsigned long long)it.height * it.width < (1ull << 30), MIGAN_EINVAL,
-                "item " + std::to_string(i) + ": image must be at least 3x3 (reflect padding of the 5x5 blur) and below 2^30 pixels");
-    MIGAN_CHECK(it.mask_height > 0 && it.mask_width > 0 && (unsigned long long)it.mask_height * it.mask_width < (1ull << 30), MIGAN_EINVAL,
-                "item " + std::to_string(i) + ": bad mask size");
+    migan_pipeline_check_image("item", i, it.height, it.width);
+    migan_pipeline_check_mask("item", i, it.mask_height, it.mask_width);
     const bool resize = it.mask_height != it.height || it.mask_width != it.width;
     const size_t plane = align256((size_t)it.height * it.width);
     if (out) {
@@ -2456,8 +2506,8 @@ int migan_pipeline_regions_scratch_bytes(const migan_pipeline_item* items, int n
   *bytes = migan_pipeline_regions_plan(items, n, gap, max_regions, nullptr, nullptr, nullptr);
   MIGAN_API_END
 }
-// the nine kernels of migan_pipeline_regions.inc, each over all items (kRegionsFindMax and fewer than 2^31 workgroups per launch),
-// all on `stream`, nothing read back
+// the nine kernels of migan_pipeline_regions.inc, each over all items (table_split, table_launch: kRegionsFindMax items per launch;
+// counts and boxes of a launch begin at its first item), all on `stream`, nothing read back
 int migan_pipeline_regions_find(const migan_pipeline_item* items, int n, int resolution, int padding, int gap, int max_regions,
                                 void* const* labels, int* count_dev, int* boxes_dev, void* scratch, void* stream) {
   MIGAN_API_BEGIN
@@ -2470,24 +2520,11 @@ int migan_pipeline_regions_find(const migan_pipeline_item* items, int n, int res
   proto.count = count_dev; proto.boxes = boxes_dev;
   proto.R = resolution; proto.padding = padding; proto.gap = gap; proto.max_regions = max_regions;
   auto run = [&](void (*kernel)(const PipeRegionsArgs), const char* name, auto tiles, size_t lds) {
-    for (size_t i0 = 0; i0 < its.size();) {
-      PipeRegionsArgs a = proto;
-      unsigned long long total = 0;
-      int k = 0;
-      for (; k < kRegionsFindMax && i0 + k < its.size(); ++k) {
-        const unsigned long long t = tiles(its[i0 + k]);
-        if (k > 0 && total + t > 0x7fffffffull) break;
-        a.item[k] = its[i0 + k];
-        a.first[k] = (int)total;
-        total += t;
-      }
-      a.first[k] = (int)total;
-      a.n = k;
-      a.count += i0;
-      a.boxes += i0 * (size_t)(max_regions + 1) * 4;
-      if (total) rt_check(rt::launch(kernel, a, (unsigned)total, kThreads, lds, (rt::stream_t)stream), name);
-      i0 += (size_t)k;
-    }
+    const auto t = [&](int i) { return (unsigned long long)tiles(its[(size_t)i]); };
+    for (const TableLaunch& l : table_split(n, t, table_items<PipeRegionsArgs>))
+      table_launch(kernel, name, proto, l, t, [&](PipeRegionsArgs& a, int j, int i) { a.item[j] = its[(size_t)i]; },
+                   [&](PipeRegionsArgs& a, int i0) { a.count += i0; a.boxes += (size_t)i0 * (size_t)(max_regions + 1) * 4; },
+                   kThreads, lds, stream);
   };
   auto pixels = [](const PipeRegionsItem& it) { return (unsigned long long)cdiv(it.H * it.W, kThreads); };
   auto tiles32 = [](const PipeRegionsItem& it) { return (unsigned long long)cdiv(it.W, kRegTile) * (unsigned long long)cdiv(it.H, kRegTile); };
@@ -2514,44 +2551,29 @@ static void migan_pipeline_rows_plan(const migan_pipeline_region_row* rows, int 
   out->resize((size_t)m);
   for (int i = 0; i < m; ++i) {
     const migan_pipeline_region_row& r = rows[i];
-    const std::string who = "row " + std::to_string(i);
-    MIGAN_CHECK(r.image_chw_u8 && r.mask_u8, MIGAN_EINVAL, "null image or mask in " + who);
-    MIGAN_CHECK(r.height >= 3 && r.width >= 3 && (unsigned long long)r.height * r.width < (1ull << 30), MIGAN_EINVAL,
-                who + ": image must be at least 3x3 (reflect padding of the 5x5 blur) and below 2^30 pixels");
-    MIGAN_CHECK(r.label >= 0 && r.label <= kRegionsCap, MIGAN_EINVAL, who + ": label must be in 0 ... 64");
-    MIGAN_CHECK(r.label == 0 || r.labels_u8, MIGAN_EINVAL, who + ": a label above 0 needs the label map");
-    MIGAN_CHECK(r.box[0] >= 0 && r.box[1] <= r.width && r.box[2] >= 0 && r.box[3] <= r.height && r.box[1] - r.box[0] >= 3 &&
-                r.box[3] - r.box[2] >= 3, MIGAN_EINVAL, who + ": box = {x_min, x_max, y_min, y_max} must lie inside the image and be at least 3x3");
+    MIGAN_CHECK(r.image_chw_u8 && r.mask_u8, MIGAN_EINVAL, "null image or mask in row " + std::to_string(i));
+    migan_pipeline_check_image("row", i, r.height, r.width);
+    migan_pipeline_check_region("row", i, r.label, r.labels_u8, r.box, r.height, r.width);
     PipeRowItem& b = (*out)[(size_t)i];
     b.image = (unsigned char*)r.image_chw_u8; b.mask = (const unsigned char*)r.mask_u8; b.labels = (const unsigned char*)r.labels_u8;
     b.H = r.height; b.W = r.width; b.label = r.label;
     for (int j = 0; j < 4; ++j) b.box[j] = r.box[j];
   }
 }
-// one kernel over all rows, kPipeRowsMax (and fewer than 2^31 workgroups) per launch: tiles(row) workgroups for each
+// one kernel over all rows (table_split, table_launch): tiles(row) workgroups for each; x and y of a launch begin at its first row
 extern "C++" template <class Tiles>
-static void migan_pipeline_rows_run(void (*kernel)(const migan::PipeRowsArgs), const char* name, const migan::PipeRowsArgs& proto,
-                                    const std::vector<migan::PipeRowItem>& rows, Tiles tiles, size_t lds, void* stream) {
+static void migan_pipeline_rows_launch(void (*kernel)(const migan::PipeRowsArgs), const char* name, const migan::PipeRowsArgs& proto,
+                                       const std::vector<migan::PipeRowItem>& rows, Tiles tiles, size_t lds, void* stream) {
   using namespace migan;
   const size_t plane = (size_t)proto.R * proto.R;
-  for (size_t i0 = 0; i0 < rows.size();) {
-    PipeRowsArgs a = proto;
-    unsigned long long total = 0;
-    int k = 0;
-    for (; k < kPipeRowsMax && i0 + k < rows.size(); ++k) {
-      const unsigned long long t = tiles(rows[i0 + k]);
-      if (k > 0 && total + t > 0x7fffffffull) break;
-      a.item[k] = rows[i0 + k];
-      a.first[k] = (int)total;
-      total += t;
-    }
-    a.first[k] = (int)total;
-    a.n = k;
-    if (a.x) a.x += i0 * 4 * plane;
-    if (a.y) a.y += i0 * 3 * plane;
-    if (total) rt_check(rt::launch(kernel, a, (unsigned)total, kThreads, lds, (rt::stream_t)stream), name);
-    i0 += (size_t)k;
-  }
+  const auto t = [&](int i) { return (unsigned long long)tiles(rows[(size_t)i]); };
+  for (const TableLaunch& l : table_split((int)rows.size(), t, table_items<PipeRowsArgs>))
+    table_launch(kernel, name, proto, l, t, [&](PipeRowsArgs& a, int j, int i) { a.item[j] = rows[(size_t)i]; },
+                 [&](PipeRowsArgs& a, int i0) {
+                   if (a.x) a.x += (size_t)i0 * 4 * plane;
+                   if (a.y) a.y += (size_t)i0 * 3 * plane;
+                 },
+                 kThreads, lds, stream);
 }
 int migan_pipeline_regions_pre(const migan_pipeline_region_row* rows, int m, int resolution, void* x_nchw, void* stream) {
   MIGAN_API_BEGIN
@@ -2562,7 +2584,7 @@ int migan_pipeline_regions_pre(const migan_pipeline_region_row* rows, int m, int
   PipeRowsArgs a{};
   a.x = (float*)x_nchw; a.R = resolution;
   const unsigned long long per_row = (unsigned long long)cdiv(resolution * resolution, kThreads);
-  migan_pipeline_rows_run(pipe_pre_rows_kernel, "migan::pipe_pre_rows_kernel", a, its, [=](const PipeRowItem&) { return per_row; }, 0, stream);
+  migan_pipeline_rows_launch(pipe_pre_rows_kernel, "migan::pipe_pre_rows_kernel", a, its, [=](const PipeRowItem&) { return per_row; }, 0, stream);
   MIGAN_API_END
 }
 // the box is host data: the grid has exactly the crop's tiles
@@ -2576,19 +2598,12 @@ int migan_pipeline_regions_post(const migan_pipeline_region_row* rows, int m, in
   PipeRowsArgs a{};
   a.y = (const float*)y_nchw; a.R = resolution;
   migan_pipeline_gauss(gauss25, a.gauss);
-  migan_pipeline_rows_run(pipe_post_rows_kernel, "migan::pipe_post_rows_kernel", a, its,
-                          [](const PipeRowItem& it) {
-                            return (unsigned long long)cdiv(it.box[1] - it.box[0], kPostTW) * (unsigned long long)cdiv(it.box[3] - it.box[2], kPostTH);
-                          },
-                          (size_t)kPostLdsBytes + 16, stream);
+  migan_pipeline_rows_launch(pipe_post_rows_kernel, "migan::pipe_post_rows_kernel", a, its,
+                             [](const PipeRowItem& it) { return migan_pipeline_box_tiles(it.box); }, (size_t)kPostLdsBytes + 16, stream);
   MIGAN_API_END
 }
 
 // ---- S completions per hole region as patches, and the paste back (include/migan_pipeline_region_patches_hip.h) ----
-// the crop's tiles of a row: the grid of pipe_post_rows_kernel, pipe_post_rows_patches_kernel and pipe_paste_rows_kernel
-static unsigned long long migan_pipeline_box_tiles(const int* box) {
-  return (unsigned long long)migan::cdiv(box[1] - box[0], migan::kPostTW) * (unsigned long long)migan::cdiv(box[3] - box[2], migan::kPostTH);
-}
 // _regions_post for `samples` generator outputs per row, out of place: row r and y rows r * samples ... -> outs[r] =
 // [samples][3][ch][cw].  The box is host data, so a destination that is too small is refused here, before anything is launched
 int migan_pipeline_regions_post_patches(const migan_pipeline_region_row* rows, int m, int samples, int resolution, const void* y_nchw,
@@ -2614,29 +2629,17 @@ int migan_pipeline_regions_post_patches(const migan_pipeline_region_row* rows, i
   proto.y = (const float*)y_nchw; proto.R = resolution; proto.S = samples;
   migan_pipeline_gauss(gauss25, proto.gauss);
   const size_t plane = (size_t)resolution * resolution;
-  for (size_t i0 = 0; i0 < its.size();) {
-    PipeRowPatchesArgs a = proto;
-    unsigned long long total = 0;
-    int k = 0;
-    for (; k < kPipeRowPatchesMax && i0 + k < its.size(); ++k) {
-      const PipeRowItem& it = its[i0 + k];
-      const unsigned long long t = migan_pipeline_box_tiles(it.box);
-      if (k > 0 && total + t > 0x7fffffffull) break;
-      PipeRowPatchesItem& b = a.item[k];
-      b.image = it.image; b.mask = it.mask; b.labels = it.labels; b.out = (unsigned char*)outs[i0 + k];
-      b.H = it.H; b.W = it.W; b.label = it.label;
-      for (int j = 0; j < 4; ++j) b.box[j] = it.box[j];
-      a.first[k] = (int)total;
-      total += t;
-    }
-    a.first[k] = (int)total;
-    a.n = k;
-    a.y += i0 * (size_t)samples * 3 * plane;
-    if (total)
-      rt_check(rt::launch(pipe_post_rows_patches_kernel, a, (unsigned)total, kThreads, (size_t)kPostLdsBytes + 16, (rt::stream_t)stream),
-               "migan::pipe_post_rows_patches_kernel");
-    i0 += (size_t)k;
-  }
+  const auto tiles = [&](int i) { return migan_pipeline_box_tiles(its[(size_t)i].box); };
+  for (const TableLaunch& l : table_split(m, tiles, table_items<PipeRowPatchesArgs>))
+    table_launch(pipe_post_rows_patches_kernel, "migan::pipe_post_rows_patches_kernel", proto, l, tiles,
+                 [&](PipeRowPatchesArgs& a, int j, int i) {
+                   const PipeRowItem& it = its[(size_t)i];
+                   PipeRowPatchesItem& b = a.item[j];
+                   b.image = it.image; b.mask = it.mask; b.labels = it.labels; b.out = (unsigned char*)outs[i];
+                   b.H = it.H; b.W = it.W; b.label = it.label;
+                   for (int c = 0; c < 4; ++c) b.box[c] = it.box[c];
+                 },
+                 [&](PipeRowPatchesArgs& a, int i0) { a.y += (size_t)i0 * samples * 3 * plane; }, kThreads, (size_t)kPostLdsBytes + 16, stream);
   MIGAN_API_END
 }
 // one sample's patch of every listed row -> its image, where labels == label: a copy
@@ -2644,38 +2647,23 @@ int migan_pipeline_regions_paste(const migan_pipeline_region_paste_row* rows, in
   MIGAN_API_BEGIN
   using namespace migan;
   MIGAN_CHECK(rows != nullptr && m >= 1, MIGAN_EINVAL, "the call needs at least one row");
-  std::vector<PipePasteItem> its((size_t)m);
   for (int i = 0; i < m; ++i) {
     const migan_pipeline_region_paste_row& r = rows[i];
-    const std::string who = "row " + std::to_string(i);
-    MIGAN_CHECK(r.image_chw_u8 && r.patch_chw_u8, MIGAN_EINVAL, "null image or patch in " + who);
-    MIGAN_CHECK(r.height >= 3 && r.width >= 3 && (unsigned long long)r.height * r.width < (1ull << 30), MIGAN_EINVAL,
-                who + ": image must be at least 3x3 and below 2^30 pixels");
-    MIGAN_CHECK(r.label >= 0 && r.label <= kRegionsCap, MIGAN_EINVAL, who + ": label must be in 0 ... 64");
-    MIGAN_CHECK(r.label == 0 || r.labels_u8, MIGAN_EINVAL, who + ": a label above 0 needs the label map");
-    MIGAN_CHECK(r.box[0] >= 0 && r.box[1] <= r.width && r.box[2] >= 0 && r.box[3] <= r.height && r.box[1] - r.box[0] >= 3 &&
-                r.box[3] - r.box[2] >= 3, MIGAN_EINVAL, who + ": box = {x_min, x_max, y_min, y_max} must lie inside the image and be at least 3x3");
-    PipePasteItem& b = its[(size_t)i];
-    b.image = (unsigned char*)r.image_chw_u8; b.labels = (const unsigned char*)r.labels_u8; b.patch = (const unsigned char*)r.patch_chw_u8;
-    b.H = r.height; b.W = r.width; b.label = r.label;
-    for (int j = 0; j < 4; ++j) b.box[j] = r.box[j];
+    MIGAN_CHECK(r.image_chw_u8 && r.patch_chw_u8, MIGAN_EINVAL, "null image or patch in row " + std::to_string(i));
+    migan_pipeline_check_image("row", i, r.height, r.width, "");      // (no blur here)
+    migan_pipeline_check_region("row", i, r.label, r.labels_u8, r.box, r.height, r.width);
   }
-  for (size_t i0 = 0; i0 < its.size();) {
-    PipePasteArgs a{};
-    unsigned long long total = 0;
-    int k = 0;
-    for (; k < kPipePasteMax && i0 + k < its.size(); ++k) {
-      const unsigned long long t = migan_pipeline_box_tiles(its[i0 + k].box);
-      if (k > 0 && total + t > 0x7fffffffull) break;
-      a.item[k] = its[i0 + k];
-      a.first[k] = (int)total;
-      total += t;
-    }
-    a.first[k] = (int)total;
-    a.n = k;
-    if (total) rt_check(rt::launch(pipe_paste_rows_kernel, a, (unsigned)total, kThreads, 0, (rt::stream_t)stream), "migan::pipe_paste_rows_kernel");
-    i0 += (size_t)k;
-  }
+  const auto tiles = [&](int i) { return migan_pipeline_box_tiles(rows[i].box); };
+  for (const TableLaunch& l : table_split(m, tiles, table_items<PipePasteArgs>))
+    table_launch(pipe_paste_rows_kernel, "migan::pipe_paste_rows_kernel", PipePasteArgs{}, l, tiles,
+                 [&](PipePasteArgs& a, int j, int i) {
+                   const migan_pipeline_region_paste_row& r = rows[i];
+                   PipePasteItem& b = a.item[j];
+                   b.image = (unsigned char*)r.image_chw_u8; b.labels = (const unsigned char*)r.labels_u8; b.patch = (const unsigned char*)r.patch_chw_u8;
+                   b.H = r.height; b.W = r.width; b.label = r.label;
+                   for (int c = 0; c < 4; ++c) b.box[c] = r.box[c];
+                 },
+                 [](PipePasteArgs&, int) {}, kThreads, 0, stream);
   MIGAN_API_END
 }
 
@@ -2735,32 +2723,23 @@ int migan_version(void) { return 2; }
 // ------------------------------------------------------------------------------------------------
 // include/migan_metrics_hip.h: PSNR / SSIM of completions against the photo (kernels: migan_metrics.hpp)
 namespace migan {
-struct MetLaunch {
-  int i0, k;                         // items [i0, i0 + k)
-  unsigned long long tiles;
-};
-// The launches of a batch (kMetItemsMax items and fewer than 2^31 workgroups each) and the scratch the largest of them needs: per
-// tile S * 3 partial pairs and one pair of counts.  Launches follow each other on one stream, so they share the scratch.  One
-// statement for _scratch_bytes and _batch; it also checks the sizes.
-static size_t metrics_plan(const migan_metrics_item* items, int n, int samples, std::vector<MetLaunch>* out) {
+inline unsigned long long metrics_tiles(const migan_metrics_item& it) {
+  return (unsigned long long)cdiv(it.W, kMetTW) * (unsigned long long)cdiv(it.H, kMetTH);
+}
+// The launches of a batch (table_split) and the scratch the largest of them needs: per tile S * 3 partial pairs and one pair of
+// counts.  Launches follow each other on one stream, so they share the scratch.  One statement for _scratch_bytes and _batch; it
+// also checks the sizes.
+static size_t metrics_plan(const migan_metrics_item* items, int n, int samples, std::vector<TableLaunch>* out) {
   MIGAN_CHECK(items != nullptr && n >= 1, MIGAN_EINVAL, "the batch needs at least one item");
   MIGAN_CHECK(samples >= 1 && samples <= (1 << 24), MIGAN_EINVAL, "samples must be at least 1 (and at most 2^24)");
+  const std::vector<TableLaunch> launches = table_split(n, [&](int i) {
+    MIGAN_CHECK(items[i].H >= 1 && items[i].W >= 1, MIGAN_EINVAL, "item " + std::to_string(i) + ": empty image");
+    return metrics_tiles(items[i]);
+  }, table_items<MetArgs>);
   size_t bytes = 0;
-  for (int i0 = 0; i0 < n;) {
-    unsigned long long total = 0;
-    int k = 0;
-    for (; k < kMetItemsMax && i0 + k < n; ++k) {
-      const migan_metrics_item& it = items[i0 + k];
-      MIGAN_CHECK(it.H >= 1 && it.W >= 1, MIGAN_EINVAL, "item " + std::to_string(i0 + k) + ": empty image");
-      const unsigned long long t = (unsigned long long)cdiv(it.W, kMetTW) * (unsigned long long)cdiv(it.H, kMetTH);
-      MIGAN_CHECK(t <= 0x7fffffffull, MIGAN_EINVAL, "item " + std::to_string(i0 + k) + ": image too large");
-      if (k > 0 && total + t > 0x7fffffffull) break;
-      total += t;
-    }
-    if (out) out->push_back(MetLaunch{i0, k, total});
-    bytes = std::max(bytes, align256((size_t)total * samples * 3 * sizeof(MetPart<true>)) + align256((size_t)total * 2 * sizeof(unsigned)));
-    i0 += k;
-  }
+  for (const TableLaunch& l : launches)
+    bytes = std::max(bytes, align256((size_t)l.total * samples * 3 * sizeof(MetPart<true>)) + align256((size_t)l.total * 2 * sizeof(unsigned)));
+  if (out) *out = launches;
   return bytes;
 }
 }  // namespace migan
@@ -2787,7 +2766,7 @@ int migan_metrics_batch(const migan_metrics_item* items, int n, int samples, int
   MIGAN_CHECK(std::isfinite(lo) && std::isfinite(hi) && std::isfinite(span) && hi != lo, MIGAN_EINVAL,
               "the value range needs two different finite ends");
   MIGAN_CHECK(scratch && out_mse && out_ssim, MIGAN_EINVAL, "null scratch or output");
-  std::vector<MetLaunch> launches;
+  std::vector<TableLaunch> launches;
   metrics_plan(items, n, samples, &launches);
   for (int i = 0; i < n; ++i) {
     const migan_metrics_item& it = items[i];
@@ -2799,23 +2778,18 @@ int migan_metrics_batch(const migan_metrics_item* items, int n, int samples, int
                     std::to_string(shave) + " from every side");
   }
   const MetForm form = metrics_form(dtype == MIGAN_METRICS_U8);
-  for (const MetLaunch& l : launches) {
-    MetArgs a{};
-    unsigned long long total = 0;
-    for (int k = 0; k < l.k; ++k) {
-      const migan_metrics_item& it = items[l.i0 + k];
-      a.item[k] = MetItem{it.gt, it.pred, it.mask, it.H, it.W};
-      a.first[k] = (int)total;
-      total += (unsigned long long)cdiv(it.W, kMetTW) * (unsigned long long)cdiv(it.H, kMetTH);
-    }
-    a.first[l.k] = (int)total;
-    a.part = scratch;
-    a.cnt = (unsigned*)((char*)scratch + align256((size_t)total * samples * 3 * sizeof(MetPart<true>)));
-    a.out_mse = out_mse + (size_t)l.i0 * samples;
-    a.out_ssim = out_ssim + (size_t)l.i0 * samples;
-    a.n = l.k; a.S = samples; a.shave = shave; a.hwc = layout == MIGAN_METRICS_HWC;
-    a.lo = lo; a.span = span;
-    rt_check(rt::launch(form.tile, a, (unsigned)total, kMetThreads, (size_t)kMetLdsBytes, (rt::stream_t)stream), form.tile_name);
+  MetArgs proto{};
+  proto.part = scratch; proto.S = samples; proto.shave = shave; proto.hwc = layout == MIGAN_METRICS_HWC;
+  proto.lo = lo; proto.span = span;
+  for (const TableLaunch& l : launches) {
+    const MetArgs a = table_launch(form.tile, form.tile_name, proto, l, [&](int i) { return metrics_tiles(items[i]); },
+                                   [&](MetArgs& d, int j, int i) { d.item[j] = MetItem{items[i].gt, items[i].pred, items[i].mask, items[i].H, items[i].W}; },
+                                   [&](MetArgs& d, int i0) {
+                                     d.cnt = (unsigned*)((char*)scratch + align256((size_t)l.total * samples * 3 * sizeof(MetPart<true>)));
+                                     d.out_mse = out_mse + (size_t)i0 * samples;
+                                     d.out_ssim = out_ssim + (size_t)i0 * samples;
+                                   },
+                                   kMetThreads, (size_t)kMetLdsBytes, stream);
     rt_check(rt::launch(form.final, a, (unsigned)(l.k * samples), kMetThreads, (size_t)kMetFinalLdsBytes, (rt::stream_t)stream), form.final_name);
   }
   MIGAN_API_END
@@ -2877,17 +2851,13 @@ static void photo_check_common(const migan_photo_item* items, int n, int channel
   MIGAN_CHECK(channels == 1 || channels == 3, MIGAN_EINVAL, "channels must be 1 or 3");
   MIGAN_CHECK(filter == MIGAN_PHOTO_NEAREST || filter == MIGAN_PHOTO_BICUBIC, MIGAN_EINVAL, "filter must be MIGAN_PHOTO_NEAREST or MIGAN_PHOTO_BICUBIC");
 }
-// one launch over the chunk's items: `tiles(item)` workgroups each (0: the item takes no part)
+// one launch over the chunk's items as `a` holds them (the chunks are fixed: their scratch is laid out per chunk and four kernels
+// share one): `tiles(item)` workgroups each (0: the item takes no part).  table_launch refuses more workgroups than a launch
+// carries (32 largest items stay far below).
 template <class Tiles>
-static void photo_launch(void (*kernel)(const PhArgs), const char* name, PhArgs& a, Tiles tiles, size_t lds, void* stream) {
-  long long total = 0;
-  for (int j = 0; j < a.n; ++j) {
-    a.first[j] = (int)total;
-    total += tiles(a.item[j]);
-  }
-  a.first[a.n] = (int)total;
-  MIGAN_CHECK(total <= 0x7fffffffll, MIGAN_EINVAL, "too many workgroups in one launch");      // (32 largest items stay far below)
-  if (total > 0) rt_check(rt::launch(kernel, a, (unsigned)total, kPhThreads, lds, (rt::stream_t)stream), name);
+static void photo_launch(void (*kernel)(const PhArgs), const char* name, const PhArgs& a, Tiles tiles, size_t lds, void* stream) {
+  table_launch(kernel, name, a, TableLaunch{0, a.n, 0}, [&](int j) { return (unsigned long long)tiles(a.item[j]); },
+               [](PhArgs&, int, int) {}, [](PhArgs&, int) {}, kPhThreads, lds, stream);
 }
 }  // namespace migan
 

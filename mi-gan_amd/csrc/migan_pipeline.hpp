@@ -233,6 +233,9 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_post_kernel(const PipeArgs p)
 // The item table travels BY VALUE in the kernel argument (48 bytes per item: about 1.8 KB of the 4 KB a launch may carry), so a
 // batch costs no table upload and no allocation.  Grids are 1-D: workgroup b works on item i with first[i] <= b < first[i + 1], as
 // tile b - first[i] of it; the host fills `first` per launch (each kernel has its own tile size).  No atomics, no host round trip.
+// Every later table of this file and of its .inc files (samples, patches, regions, rows, row patches, paste) has this form, and so
+// have the metrics' and the photo resize's.  The host half is stated once for all of them (migan_host.hpp: table_split, which items
+// go into which launch, and table_launch, which fills item[], first[] and n); the device half of the tables here is pipe_table_item.
 constexpr int kPipeBatchMax = 32;
 struct PipeBatchItem {
   unsigned char* image;              // [3][H][W] uint8, post: read and written in place
@@ -252,8 +255,10 @@ struct PipeBatchArgs {
 };
 static_assert(sizeof(PipeBatchArgs) <= 2048, "the batch argument must stay well under the 4 KB kernel-argument limit");
 
-// wave-uniform: a handful of scalar compares on the argument
-MIGAN_DEVICE MIGAN_INLINE int pipe_batch_item(const PipeBatchArgs& p, int b) {
+// the item of workgroup b, for any argument with item[], first[] and n.  Wave-uniform: a handful of scalar compares on the
+// argument; an item without a workgroup in this launch is stepped over
+template <class Args>
+MIGAN_DEVICE MIGAN_INLINE int pipe_table_item(const Args& p, int b) {
   int i = 0;
   while (i + 1 < p.n && b >= p.first[i + 1]) ++i;
   return i;
@@ -264,21 +269,21 @@ MIGAN_DEVICE MIGAN_INLINE const unsigned char* pipe_batch_mask(const PipeBatchIt
 
 // tiles of kThreads pixels of the items whose mask has another size than their image (the others have no tile)
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_mask_resize_batch_kernel(const PipeBatchArgs p) {
-  const int k = pipe_batch_item(p, (int)blockIdx.x);
+  const int k = pipe_table_item(p, (int)blockIdx.x);
   const PipeBatchItem& it = p.item[k];
   pipe_mask_resize_pixel(it.mask_src, it.mh, it.mw, it.mask_resized, it.H, it.W, ((int)blockIdx.x - p.first[k]) * kThreads + (int)threadIdx.x);
 }
 
 // tiles of kThreads of the H + W flags of each item
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_flags_clear_batch_kernel(const PipeBatchArgs p) {
-  const int k = pipe_batch_item(p, (int)blockIdx.x);
+  const int k = pipe_table_item(p, (int)blockIdx.x);
   const PipeBatchItem& it = p.item[k];
   const int i = ((int)blockIdx.x - p.first[k]) * kThreads + (int)threadIdx.x;
   if (i < it.H + it.W) it.flags[i] = 0;
 }
 // tiles of kThreads pixels of each item's mask
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_flags_batch_kernel(const PipeBatchArgs p) {
-  const int k = pipe_batch_item(p, (int)blockIdx.x);
+  const int k = pipe_table_item(p, (int)blockIdx.x);
   const PipeBatchItem& it = p.item[k];
   const int i = ((int)blockIdx.x - p.first[k]) * kThreads + (int)threadIdx.x;
   if (i >= it.H * it.W) return;
@@ -327,7 +332,7 @@ MIGAN_DEVICE MIGAN_INLINE bool pipe_box_valid(const int* box, int H, int W) {
 
 // cdiv(R * R, kThreads) tiles per item (first[i] = i * that), box read from device memory
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_pre_batch_kernel(const PipeBatchArgs p) {
-  const int k = pipe_batch_item(p, (int)blockIdx.x);
+  const int k = pipe_table_item(p, (int)blockIdx.x);
   const PipeBatchItem& it = p.item[k];
   const int* box = p.bbox + 4 * k;
   if (!pipe_box_valid(box, it.H, it.W)) return;
@@ -353,7 +358,7 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_post_batch_kernel(const PipeB
   MIGAN_DYN_SMEM(smem);
   unsigned char* win = reinterpret_cast<unsigned char*>(smem);       // [kPostWH][kPostWW]: crop rows ty0 - 3 ..., columns tx0 - 3 ...
   unsigned char* pool = win + kPostWinBytes;                         // [kPostPH][kPostPW]: crop rows ty0 - 2 ..., columns tx0 - 2 ...
-  const int k = pipe_batch_item(p, (int)blockIdx.x);
+  const int k = pipe_table_item(p, (int)blockIdx.x);
   const PipeBatchItem& it = p.item[k];
   const int* box = p.bbox + 4 * k;
   // the box came through device memory: one that does not fit the image is not touched (and nothing of the image is)
@@ -429,7 +434,7 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_post_samples_kernel(const Pip
   unsigned char* win = reinterpret_cast<unsigned char*>(smem);       // [kPostWH][kPostWW]: crop rows ty0 - 3 ..., columns tx0 - 3 ...
   unsigned char* pool = win + kPostWinBytes;                         // [kPostPH][kPostPW]: crop rows ty0 - 2 ..., columns tx0 - 2 ...
   int k = 0;
-  while (k + 1 < p.n && (int)blockIdx.x >= p.first[k + 1]) ++k;      // (wave-uniform, as pipe_batch_item)
+  while (k + 1 < p.n && (int)blockIdx.x >= p.first[k + 1]) ++k;      // (wave-uniform; pipe_table_item, spelled out: the call changes this kernel's code)
   const PipeSamplesItem& it = p.item[k];
   const int* box = p.bbox + 4 * k;
   // the box came through device memory: one that does not fit the image is an empty crop here, and every tile copies
@@ -492,7 +497,7 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_post_patches_kernel(const Pip
   unsigned char* win = reinterpret_cast<unsigned char*>(smem);       // [kPostWH][kPostWW]: crop rows ty0 - 3 ..., columns tx0 - 3 ...
   unsigned char* pool = win + kPostWinBytes;                         // [kPostPH][kPostPW]: crop rows ty0 - 2 ..., columns tx0 - 2 ...
   int k = 0;
-  while (k + 1 < p.n && (int)blockIdx.x >= p.first[k + 1]) ++k;      // (wave-uniform, as pipe_batch_item)
+  while (k + 1 < p.n && (int)blockIdx.x >= p.first[k + 1]) ++k;      // (wave-uniform; pipe_table_item, spelled out: the call changes this kernel's code)
   const PipePatchesItem& it = p.item[k];
   const int* box = p.bbox + 4 * k;
   // the box came through device memory: one that does not fit the image has no patch ...

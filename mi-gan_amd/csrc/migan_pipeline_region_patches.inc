@@ -38,7 +38,7 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_post_rows_patches_kernel(cons
   unsigned char* pool = win + kPostWinBytes;                         // [kPostPH][kPostPW]: crop rows ty0 - 2 ..., columns tx0 - 2 ...
   int* any = reinterpret_cast<int*>(win + kPostLdsBytes);            // the tile holds a pixel of the row's label
   int k = 0;
-  while (k + 1 < p.n && (int)blockIdx.x >= p.first[k + 1]) ++k;      // (wave-uniform, as pipe_batch_item)
+  while (k + 1 < p.n && (int)blockIdx.x >= p.first[k + 1]) ++k;      // (wave-uniform; pipe_table_item, spelled out: the call changes this kernel's code)
   const PipeRowPatchesItem& it = p.item[k];
   if (!pipe_box_valid(it.box, it.H, it.W)) return;                   // (the host checked it: never taken)
   const int x_min = it.box[0], y_min = it.box[2], cw = it.box[1] - it.box[0], ch = it.box[3] - it.box[2];
@@ -94,7 +94,7 @@ static_assert(sizeof(PipePasteArgs) <= 2048, "the paste argument must stay well 
 // tiles of the crop as above, one pixel per thread: the label test, then three byte copies.  No LDS, no barrier.
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_paste_rows_kernel(const PipePasteArgs p) {
   int k = 0;
-  while (k + 1 < p.n && (int)blockIdx.x >= p.first[k + 1]) ++k;      // (wave-uniform, as pipe_batch_item)
+  while (k + 1 < p.n && (int)blockIdx.x >= p.first[k + 1]) ++k;      // (wave-uniform; pipe_table_item, spelled out: the call changes this kernel's code)
   const PipePasteItem& it = p.item[k];
   if (!pipe_box_valid(it.box, it.H, it.W)) return;                   // (the host checked it: never taken)
   const int x_min = it.box[0], y_min = it.box[2], cw = it.box[1] - it.box[0], ch = it.box[3] - it.box[2];

@@ -52,11 +52,6 @@ struct PipeRegionsArgs {
 };
 static_assert(sizeof(PipeRegionsArgs) <= 2048, "the regions argument must stay well under the 4 KB kernel-argument limit");
 
-MIGAN_DEVICE MIGAN_INLINE int regions_item(const PipeRegionsArgs& p, int b) {      // (wave-uniform, as pipe_batch_item)
-  int i = 0;
-  while (i + 1 < p.n && b >= p.first[i + 1]) ++i;
-  return i;
-}
 MIGAN_DEVICE MIGAN_INLINE const unsigned char* regions_mask(const PipeRegionsItem& it) {
   return it.mask_resized ? it.mask_resized : it.mask_src;
 }
@@ -98,7 +93,7 @@ MIGAN_DEVICE MIGAN_INLINE void regions_union(int* parent, int a, int b) {
 
 // tiles of kThreads pixels of the items whose mask has another size than their image (the others have no tile)
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) regions_mask_resize_kernel(const PipeRegionsArgs p) {
-  const int k = regions_item(p, (int)blockIdx.x);
+  const int k = pipe_table_item(p, (int)blockIdx.x);
   const PipeRegionsItem& it = p.item[k];
   pipe_mask_resize_pixel(it.mask_src, it.mh, it.mw, it.mask_resized, it.H, it.W, ((int)blockIdx.x - p.first[k]) * kThreads + (int)threadIdx.x);
 }
@@ -110,7 +105,7 @@ constexpr int kRegRowBits = kThreads + 2 * kRegionsGapMax, kRegRowWords = kRegRo
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) regions_dilate_rows_kernel(const PipeRegionsArgs p) {
   MIGAN_DYN_SMEM(smem);
   unsigned* bits = reinterpret_cast<unsigned*>(smem);                // [kRegRowWords]: bit e = column x0 - kRegionsGapMax + e
-  const int k = regions_item(p, (int)blockIdx.x);
+  const int k = pipe_table_item(p, (int)blockIdx.x);
   const PipeRegionsItem& it = p.item[k];
   const int tile = (int)blockIdx.x - p.first[k], ntx = (it.W + kThreads - 1) / kThreads;
   const int y = tile / ntx, x0 = tile % ntx * kThreads;
@@ -138,7 +133,7 @@ constexpr int kRegColRows = 64, kRegColBits = kRegColRows + 2 * kRegionsGapMax, 
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) regions_dilate_cols_kernel(const PipeRegionsArgs p) {
   MIGAN_DYN_SMEM(smem);
   unsigned* cols = reinterpret_cast<unsigned*>(smem);                // [kRegTile][kRegColStride]: bit r = row y0 - kRegionsGapMax + r
-  const int k = regions_item(p, (int)blockIdx.x);
+  const int k = pipe_table_item(p, (int)blockIdx.x);
   const PipeRegionsItem& it = p.item[k];
   const int tile = (int)blockIdx.x - p.first[k], ntx = (it.W + kRegTile - 1) / kRegTile;
   const int y0 = tile / ntx * kRegColRows, x0 = tile % ntx * kRegTile;
@@ -168,7 +163,7 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) regions_dilate_cols_kernel(const P
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) regions_label_tile_kernel(const PipeRegionsArgs p) {
   MIGAN_DYN_SMEM(smem);
   int* lab = reinterpret_cast<int*>(smem);                           // [kRegTile * kRegTile], -1 outside D
-  const int k = regions_item(p, (int)blockIdx.x);
+  const int k = pipe_table_item(p, (int)blockIdx.x);
   const PipeRegionsItem& it = p.item[k];
   const int tile = (int)blockIdx.x - p.first[k], ntx = (it.W + kRegTile - 1) / kRegTile;
   const int y0 = tile / ntx * kRegTile, x0 = tile % ntx * kRegTile;
@@ -201,7 +196,7 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) regions_label_tile_kernel(const Pi
 // pixel lies in the top row, the left column or (NE) the right column of its tile: 3 kRegTile threads per tile look at those.  The
 // union is exact (a set keeps one root however many tiles it crosses and in whatever order the pairs arrive): one pass is enough.
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) regions_merge_kernel(const PipeRegionsArgs p) {
-  const int k = regions_item(p, (int)blockIdx.x);
+  const int k = pipe_table_item(p, (int)blockIdx.x);
   const PipeRegionsItem& it = p.item[k];
   const int tile = (int)blockIdx.x - p.first[k], ntx = (it.W + kRegTile - 1) / kRegTile;
   const int y0 = tile / ntx * kRegTile, x0 = tile % ntx * kRegTile;
@@ -224,7 +219,7 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) regions_merge_kernel(const PipeReg
 
 // tiles of kThreads pixels: a root appends itself; the list holds max_regions + 1 entries, the counter goes on counting
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) regions_roots_kernel(const PipeRegionsArgs p) {
-  const int k = regions_item(p, (int)blockIdx.x);
+  const int k = pipe_table_item(p, (int)blockIdx.x);
   const PipeRegionsItem& it = p.item[k];
   const int i = ((int)blockIdx.x - p.first[k]) * kThreads + (int)threadIdx.x;
   if (i >= it.H * it.W || it.parent[i] != i) return;
@@ -264,7 +259,7 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) regions_labels_kernel(const PipeRe
   MIGAN_DYN_SMEM(smem);
   int* list = reinterpret_cast<int*>(smem);                          // [kRegionsCap + 1] sorted roots
   int* ext = list + kRegionsCap + 1;                                 // [kRegionsCap + 1][4] = {x_min, x_max, y_min, y_max}
-  const int k = regions_item(p, (int)blockIdx.x);
+  const int k = pipe_table_item(p, (int)blockIdx.x);
   const PipeRegionsItem& it = p.item[k];
   const int t = (int)threadIdx.x;
   const int count = it.meta[0], nslots = 4 * (p.max_regions + 1);
@@ -340,7 +335,7 @@ static_assert(sizeof(PipeRowsArgs) <= 2304, "the rows argument must stay well un
 // cdiv(R * R, kThreads) tiles per row: pipe_pre_batch_kernel with the box in the argument
 MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_pre_rows_kernel(const PipeRowsArgs p) {
   int k = 0;
-  while (k + 1 < p.n && (int)blockIdx.x >= p.first[k + 1]) ++k;      // (wave-uniform, as pipe_batch_item)
+  while (k + 1 < p.n && (int)blockIdx.x >= p.first[k + 1]) ++k;      // (wave-uniform; pipe_table_item, spelled out: the call changes this kernel's code)
   const PipeRowItem& it = p.item[k];
   if (!pipe_box_valid(it.box, it.H, it.W)) return;
   pipe_pre_pixel(it.image, it.mask, p.x + (size_t)k * 4 * p.R * p.R, it.H, it.W, p.R, it.box[0], it.box[1], it.box[2], it.box[3],
@@ -356,7 +351,7 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_post_rows_kernel(const PipeRo
   unsigned char* pool = win + kPostWinBytes;                         // [kPostPH][kPostPW]: crop rows ty0 - 2 ..., columns tx0 - 2 ...
   int* any = reinterpret_cast<int*>(win + kPostLdsBytes);            // the tile holds a pixel of the row's label
   int k = 0;
-  while (k + 1 < p.n && (int)blockIdx.x >= p.first[k + 1]) ++k;      // (wave-uniform, as pipe_batch_item)
+  while (k + 1 < p.n && (int)blockIdx.x >= p.first[k + 1]) ++k;      // (wave-uniform; pipe_table_item, spelled out: the call changes this kernel's code)
   const PipeRowItem& it = p.item[k];
   if (!pipe_box_valid(it.box, it.H, it.W)) return;
   const int x_min = it.box[0], y_min = it.box[2], cw = it.box[1] - it.box[0], ch = it.box[3] - it.box[2];

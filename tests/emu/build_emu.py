@@ -8,27 +8,17 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 OUT_DIR = os.path.join(HERE, "_build")
 OUT = os.path.join(OUT_DIR, "libmigan_emu.so")
-SOURCES = [
-    os.path.join(HERE, "migan_emu.cpp"),
-    os.path.join(HERE, "hip_emu.h"),
-    os.path.join(ROOT, "mi-gan_amd", "csrc", "migan_kernels.hpp"),
-    os.path.join(ROOT, "mi-gan_amd", "csrc", "migan_host.hpp"),
-    os.path.join(ROOT, "mi-gan_amd", "csrc", "migan_table.hpp"),
-    os.path.join(ROOT, "mi-gan_amd", "csrc", "migan_pipeline.hpp"),
-    os.path.join(ROOT, "mi-gan_amd", "csrc", "migan_pipe.hpp"),
-    os.path.join(ROOT, "mi-gan_amd", "csrc", "migan_pipe_table.inc"),
-    os.path.join(ROOT, "mi-gan_amd", "csrc", "migan_wide2.hpp"),
-    os.path.join(ROOT, "mi-gan_amd", "csrc", "migan_wide2_table.inc"),
-    os.path.join(ROOT, "mi-gan_amd", "csrc", "migan_k_slice.inc"),
-    os.path.join(ROOT, "include", "migan_hip.h"),
-    os.path.join(ROOT, "mi-gan_amd", "csrc", "comodgan_kernels.hpp"),
-    os.path.join(ROOT, "mi-gan_amd", "csrc", "comodgan_conv_body.inc"),
-    os.path.join(ROOT, "mi-gan_amd", "csrc", "comodgan_fir_body.inc"),
-    os.path.join(ROOT, "mi-gan_amd", "csrc", "comodgan_fromrgb_body.inc"),
-    os.path.join(ROOT, "mi-gan_amd", "csrc", "comodgan_torgb_body.inc"),
-    os.path.join(ROOT, "mi-gan_amd", "csrc", "comodgan_host.hpp"),
-    os.path.join(ROOT, "include", "comodgan_hip.h"),
-]
+SRC = os.path.join(HERE, "migan_emu.cpp")
+
+
+def sources():
+    """what the library is built from, read from the directories so that a new header cannot be forgotten: the emulator's own two
+    files, every source under mi-gan_amd/csrc/ and the public headers"""
+    csrc = os.path.join(ROOT, "mi-gan_amd", "csrc")
+    inc = os.path.join(ROOT, "include")
+    return ([SRC, os.path.join(HERE, "hip_emu.h")]
+            + sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp", ".inc", ".h")))
+            + sorted(os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h")))
 
 
 def _compiler():
@@ -41,11 +31,11 @@ def _compiler():
 def build(force: bool = False) -> str:
     os.makedirs(OUT_DIR, exist_ok=True)
     if not force and os.path.exists(OUT):
-        newest = max(os.path.getmtime(s) for s in SOURCES)
+        newest = max(os.path.getmtime(s) for s in sources())
         if os.path.getmtime(OUT) >= newest:
             return OUT
     cmd = [_compiler(), "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-psabi",
-           SOURCES[0], "-o", OUT, "-lpthread"]
+           SRC, "-o", OUT, "-lpthread"]
     subprocess.run(cmd, check=True)
     return OUT
 

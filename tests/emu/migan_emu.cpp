@@ -248,3 +248,21 @@ extern "C" int hipemu_tile_walk(int tiles_x, int tiles_y, int nchunks, int B, in
   return T;
 }
 extern "C" int hipemu_xcd_remap(int bid, int nblk) { return migan::xcd_remap(bid, nblk); }
+
+// the split of a call's items into launches (mi-gan_amd/csrc/migan_host.hpp: table_split), for tests/test_emu_table_split.py.
+// max_groups = 0: the split's own default.  launches = up to `cap` rows {i0, k, total}; returns their number, or -1 for a refusal
+// (its text is migan_last_error's)
+extern "C" int hipemu_table_split(const unsigned long long* tiles, int n, int max_items, unsigned long long max_groups,
+                                  unsigned long long* launches, int cap) {
+  try {
+    const auto t = [&](int i) { return tiles[i]; };
+    const std::vector<migan::TableLaunch> ls = max_groups ? migan::table_split(n, t, max_items, max_groups) : migan::table_split(n, t, max_items);
+    for (int q = 0; q < (int)ls.size() && q < cap; ++q) {
+      launches[3 * q] = (unsigned long long)ls[q].i0; launches[3 * q + 1] = (unsigned long long)ls[q].k; launches[3 * q + 2] = ls[q].total;
+    }
+    return (int)ls.size();
+  } catch (const std::exception& e) {
+    migan::last_error_ref() = e.what();
+    return -1;
+  }
+}

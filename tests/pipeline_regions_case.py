@@ -257,6 +257,48 @@ def run_find(lib, bufs, case, images_dev, masks_dev):
     return [bufs.to_np(b) for b in labels], bufs.to_np(count), bufs.to_np(boxes), labels
 
 
+def seventeen_items():
+    """more items than one launch of regions_find carries (kRegionsFindMax = 16): 17 tiny images of different sizes between 8 x 8 and
+    14 x 14 with one or two holes each, two of them with a mask of another size, one all known, one all hole.  No oracle: the test
+    compares one call with 17 calls."""
+    rng = np.random.default_rng(111)
+    sizes = [(8 + i % 7, 8 + (2 * i + i // 7) % 7) for i in range(17)]
+    assert len(set(sizes)) == 17 and all(8 <= s <= 14 for hw in sizes for s in hw)
+    masks = []
+    for i, (h, w) in enumerate(sizes):
+        mh, mw = {3: (2 * h, 2 * w), 11: (h + 3, w - 2)}.get(i, (h, w))
+        m = _blank(mh, mw)
+        m[1:3, 1:3] = 0
+        if i % 2:
+            m[mh - 3:mh - 1, mw - 3:mw - 1] = 0
+        masks.append(m)
+    masks[5][...] = 255
+    masks[9][...] = 0
+    images = [rng.integers(0, 256, (3, h, w), dtype=np.uint8) for h, w in sizes]
+    return dict(name="seventeen_items", images=images, masks=masks, gap=2, max_regions=4, res=8, padding=2)
+
+
+def check_find_splits_like_single_calls(lib, bufs):
+    """labels, counts and boxes of ONE regions_find over 17 items (two launches of every kernel; counts and boxes of the second
+    begin at item 16) are, byte for byte, those of 17 calls with one item each"""
+    case = seventeen_items()
+
+    def find(sub):
+        images_dev = [bufs.to_dev(img) for img in sub["images"]]
+        masks_dev = [bufs.to_dev(m) for m in sub["masks"]]
+        return run_find(lib, bufs, sub, images_dev, masks_dev)[:3]
+
+    labels, count, boxes = find(case)
+    assert sorted(set(count.tolist())) == [0, 1, 2], "the case must hold images without a region, with one and with two"
+    assert count[5] == 0 and count[9] == 1 and not (labels[5] != 0).any() and (labels[9] == 1).all()
+    for i in range(17):
+        one = dict(case, images=case["images"][i:i + 1], masks=case["masks"][i:i + 1])
+        labels1, count1, boxes1 = find(one)
+        np.testing.assert_array_equal(labels[i], labels1[0], err_msg=f"item {i}")
+        assert count[i] == count1[0], f"item {i}"
+        np.testing.assert_array_equal(boxes[i], boxes1[0], err_msg=f"item {i}")
+
+
 def check_find(case, labels, count, boxes):
     """label map, counts and boxes against the oracle"""
     cap = case["max_regions"] + 1

@@ -17,14 +17,7 @@ BUFS = pc.Buffers(to_dev=lambda a: np.array(a, copy=True), ptr=ptr, to_np=lambda
 
 @pytest.fixture(scope="module")
 def lib():
-    """the emulator library WITH the region patches kernels: their files are not among the sources tests/emu/build_emu.py watches, so
-    a library older than them is rebuilt whatever build_emu thinks of it"""
-    from tests.emu import build_emu
-    watched = [os.path.join(ROOT, "mi-gan_amd", "csrc", f) for f in ("migan_pipeline_region_patches.inc", "migan_pipeline_regions.inc",
-                                                                      "migan_pipeline_pool_body.inc", "migan_pipeline_samples_body.inc")]
-    watched.append(os.path.join(ROOT, "include", "migan_pipeline_region_patches_hip.h"))
-    stale = not os.path.exists(build_emu.OUT) or os.path.getmtime(build_emu.OUT) < max(os.path.getmtime(f) for f in watched)
-    build_emu.build(force=stale)
+    """the emulator library WITH the region patches kernels (tests/emu/build_emu.py rebuilds a library older than any source)"""
     lib = emu_lib()
     assert hasattr(lib.lib, "migan_pipeline_regions_post_patches"), "the emulator library lacks the region patches entry points"
     return lib

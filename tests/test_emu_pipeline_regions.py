@@ -16,13 +16,7 @@ BUFS = rc.Buffers(to_dev=lambda a: np.array(a, copy=True), ptr=ptr, to_np=lambda
 
 @pytest.fixture(scope="module")
 def lib():
-    """the emulator library WITH the regions kernels: their file is not among the sources tests/emu/build_emu.py watches, so a
-    library older than it is rebuilt whatever build_emu thinks of it"""
-    from tests.emu import build_emu
-    inc = os.path.join(ROOT, "mi-gan_amd", "csrc", "migan_pipeline_regions.inc")
-    header = os.path.join(ROOT, "include", "migan_pipeline_regions_hip.h")
-    stale = not os.path.exists(build_emu.OUT) or os.path.getmtime(build_emu.OUT) < max(os.path.getmtime(inc), os.path.getmtime(header))
-    build_emu.build(force=stale)
+    """the emulator library WITH the regions kernels (tests/emu/build_emu.py rebuilds a library older than any source)"""
     lib = emu_lib()
     assert hasattr(lib.lib, "migan_pipeline_regions_find"), "the emulator library lacks the regions entry points"
     return lib
@@ -89,6 +83,11 @@ def test_rows_may_come_in_any_order_and_in_separate_calls(lib):
     lib.pipeline_regions_post([table[r] for r in order[7:]], case["res"], ptr(y[7:]), rc.GAUSS)
     for got, want in zip(images, first["images"]):
         np.testing.assert_array_equal(got, want)
+
+
+def test_more_items_than_one_launch_of_find_carries(lib):
+    """17 items, kRegionsFindMax = 16: one call gives the bytes of 17 calls with one item each"""
+    rc.check_find_splits_like_single_calls(lib, BUFS)
 
 
 def test_twice_the_same(lib):

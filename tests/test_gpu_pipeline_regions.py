@@ -57,6 +57,11 @@ def test_fallback_rows_give_the_batch_pipelines_bytes(pkg):
         np.testing.assert_array_equal(images[j].cpu().numpy(), out["images"][i])
 
 
+def test_more_items_than_one_launch_of_find_carries(pkg):
+    """17 items, kRegionsFindMax = 16: one call gives the bytes of 17 calls with one item each"""
+    rc.check_find_splits_like_single_calls(pkg.load_library(), _bufs())
+
+
 def test_twice_the_same(pkg):
     lib = pkg.load_library()
     case = rc.CASES["serpentine"]()
