@@ -109,7 +109,14 @@ int migan_forward(migan_handle* h, const void* x_nchw, void* y_nchw, int batch,
  * (height*res/resolution) x (width*res/resolution); the reference's two fixed-size constants are made "dynamic" the way
  * its README asks: filter_const (the zero-insertion mask of Upsample2d, :85) is implicit in the polyphase FIR, and each
  * noise_const [res,res] (:149) is tiled periodically and cropped to its layer's size (== the reference module run with
- * those buffers replaced by noise_const.repeat(...)[:h,:w]).  height = width = resolution is migan_forward. */
+ * those buffers replaced by noise_const.repeat(...)[:h,:w]).  height = width = resolution is migan_forward.
+ *
+ * THE EXTENT LIMIT of these entries and of migan_sepconv_forward / _samples (MIGAN_EINVAL "image too large" beyond it, before any
+ * launch): height * width * channels of every per-image tensor must not exceed 2^30 - 1024 elements: at 4 bytes per element the image
+ * ends at or before byte 2^32 - 4096, the 32-bit lane offset at which the kernels fetch padding pixels.  Channels count as at least 4;
+ * the count is the same in every storage format (a 16-bit tensor ends at 2^31 - 2048 bytes).  For the generator the largest tensor is
+ * height * width * channels at full resolution (64 for resolution 512); for the operator it is the larger of x, y (= skip) and, with
+ * down == 2, scratch.  The batch is not limited: image bases are 64-bit. */
 int migan_workspace_bytes_hw(migan_handle* h, int batch, int height, int width, size_t* bytes);
 int migan_forward_hw(migan_handle* h, const void* x_nchw, void* y_nchw, int batch, int height, int width,
                      void* workspace, size_t workspace_bytes, void* stream);
@@ -260,6 +267,7 @@ typedef struct migan_sepconv_desc {
   int dtype;                  /* MIGAN_DTYPE_*: storage format of x (unless fromrgb), y and skip; scratch stays fp32 */
   int width_in;               /* 0: square input (res_in x res_in); otherwise the input is res_in rows x width_in columns */
 } migan_sepconv_desc;
+/* Sizes beyond the extent limit stated at migan_forward_hw are MIGAN_EINVAL ("image too large"); nothing is launched or written. */
 int migan_sepconv_forward(const migan_sepconv_desc* d, void* stream);
 
 /* ---- either side of the forward ---------------------------------- */

@@ -650,6 +650,38 @@ struct LayerPtrs {
 constexpr int kMaxRowSamples = (1 << 20) - 64;
 constexpr size_t kMaxRowNoiseStride = (size_t)1 << 27;
 
+// THE extent limit of every SeparableConv2d kernel, stated once (migan_check_hw, build_plan and migan_sepconv_run apply it; include/migan_hip.h
+// and DESIGN.md quote it).  A kernel addresses a per-image tensor with an unsigned 32-bit lane BYTE offset added to a 64-bit image base, and
+// forms element indices as int: below 2^32 bytes and 2^31 elements.  The binding term is the out-of-range marker.  Lanes that must read
+// zeros are issued at the lane offset kPadMarker = 0xfffff000 and rely on the buffer descriptor's range check.
+//   The model relied on: the check compares the LANE offset (plus the access width) with num_records, the scalar offset at most reducing
+// what is left of the range (num_records less the scalar offset); the scalar offset is NOT added to the lane offset in 32 bits before the
+// check.  Evidence: the previous-image window of the pipelined ToRGB tail (migan_pipe.hpp, issue_prev_window) issues marker lanes with a
+// scalar offset of (image * 3 + colour) planes, far above 4096 bytes at 256 x 256 and up; in a 32-bit adder marker + offset would wrap into
+// the range and the top / left border would show the wrong colour plane.  Those borders are compared with the oracle in
+// tests/test_gpu_migan_layers.py (r256_b1) and, at the limit, in tests/test_gpu_large_extents.py (pipe64-torgb-prev).
+//   Scalar offsets that meet a marker lane: (a) border tiles, where the marker stands for the convolution's zero padding and MUST read
+// zeros: tile_soff is 0 and only the K chunk's offset is added, (CIN - KC) * 4 <= 1920 bytes, (CI - 16) * 4 <= 1984 in
+// sepconv_wide2_kernel; (b) the previous-image window above: up to the whole batch's planes; (c) interior tiles of the pipelined kernels
+// (sepconv_wide2_kernel issues no unit past its window): the units of an LDS slot past the window (1440..1535 of 1536 in sepconv_pipe_kernel) keep the marker and ride
+// on the whole window offset tile_soff, which approaches the image size at the limit.  Under the model all three are out of range.  (c) is
+// harmless under any model: those units are loads into the slot's tail, which the depthwise stage never reads (it indexes the window's
+// NITEMS units only).
+//   Hence the limit: the marker must not fall inside the descriptor's range, so the image must END AT OR BEFORE it.  A larger image (4095 x
+// 4097 x 64 fp32 is 2^32 - 256 bytes) makes the marker a real pixel, which every border tile would convolve into its zero padding.  The
+// widest load at the marker is 16 bytes; the 4096 bytes above it are more than that distance.  Bytes are counted at 4 per element in every
+// storage format (a 16-bit tensor of the same shape is half as long: there the element count binds, at 2^31 bytes).
+constexpr unsigned kPadMarker = 0xfffff000u;
+constexpr unsigned long long kMaxImageElems = kPadMarker / 4;      // 2^30 - 1024
+static_assert((unsigned long long)kPadMarker + 16 <= (1ull << 32), "the widest load issued at the marker ends below 2^32");
+#define MIGAN_IMAGE_LIMIT_TEXT \
+  "height * width * channels of every per-image tensor must not exceed 2^30 - 1024 elements: at 4 bytes per element the image ends at or " \
+  "before byte 2^32 - 4096, the 32-bit lane offset at which the kernels fetch padding pixels"
+// (h and w are ints: their product fits 64 bits; the division keeps an absurd channel count from wrapping the other product)
+inline bool image_fits(int h, int w, int c) {
+  return h >= 0 && w >= 0 && (unsigned long long)h * (unsigned long long)w <= kMaxImageElems / (unsigned long long)std::max(c, 4);
+}
+
 inline unsigned tiles_of(const Geo& g, int batch) {
   return (unsigned)(g.tiles_x * g.tiles_y * cdiv(batch, 1 << g.lgIMGS) * g.nchunks);
 }
@@ -1399,13 +1431,10 @@ inline void migan_handle::build_plan(migan::Plan& P, int H, int W) const {
   if (tuning().stagger >= 0) P.stagger = tuning().stagger;
   // always a launch that exists: the event recorded after it is what orders the next sub-batch behind the weight / noise planes
   P.stagger = std::min(std::max(0, (int)P.launches.size() - 1), std::max(0, P.stagger));
-  // the kernels address every per-image tensor with 32-bit lane BYTE offsets and int element indices
-  for (const Launch& L : P.launches) {
-    const unsigned long long ein = (unsigned long long)L.hin * L.win * (unsigned long long)std::max(L.cin, 4);
-    const unsigned long long eout = (unsigned long long)L.hout * L.wout * (unsigned long long)std::max(L.cout, 4);
-    MIGAN_CHECK(std::max(ein, eout) < (1ull << 31) && std::max(ein, eout) * 4ull < (1ull << 32), MIGAN_EINVAL,
-                "image too large: layer " + L.layer + " would exceed the 32-bit per-image offsets of the kernels");
-  }
+  // the kernels address every per-image tensor with 32-bit lane BYTE offsets and int element indices (kMaxImageElems)
+  for (const Launch& L : P.launches)
+    MIGAN_CHECK(image_fits(L.hin, L.win, L.cin) && image_fits(L.hout, L.wout, L.cout), MIGAN_EINVAL,
+                "image too large: layer " + L.layer + ": " MIGAN_IMAGE_LIMIT_TEXT);
 }
 
 inline migan::Plan& migan_handle::plan_for(int H, int W) {
@@ -1930,9 +1959,7 @@ static void migan_check_hw(const migan_handle* h, int height, int width) {
               "height and width must be positive multiples of resolution / 4 (the network halves its input log2(resolution) - 2 times)");
   // per-layer bound on the 32-bit per-image offsets of the kernels: the largest tensor of the plan at this size is
   // h * w * channels_at(resolution) elements at full resolution (build_plan re-checks every layer)
-  const unsigned long long top = (unsigned long long)height * width * (unsigned long long)migan::channels_at(h->resolution);
-  MIGAN_CHECK(top < (1ull << 31) && top * 4ull < (1ull << 32), MIGAN_EINVAL,
-              "image too large: height * width * channels must stay below 2^30 elements per image (32-bit offsets in the kernels)");
+  MIGAN_CHECK(migan::image_fits(height, width, migan::channels_at(h->resolution)), MIGAN_EINVAL, "image too large: " MIGAN_IMAGE_LIMIT_TEXT);
 }
 int migan_workspace_bytes_hw(migan_handle* h, int batch, int height, int width, size_t* bytes) {
   MIGAN_API_BEGIN
@@ -2072,6 +2099,8 @@ static int migan_sepconv_run(const migan_sepconv_desc* d, int samples, void* str
   MIGAN_CHECK(d->dtype >= 0 && d->dtype <= 2, MIGAN_EINVAL, "dtype must be a MIGAN_DTYPE_* value");
   const int stv = d->dtype;
   const int h_in = d->res_in, w_in = d->width_in > 0 ? d->width_in : d->res_in;
+  MIGAN_CHECK(h_in > 0 && w_in > 0 && h_in < (1 << 30) && w_in < (1 << 30) && d->cin > 0 && d->cout > 0, MIGAN_EINVAL,
+              "sizes and channel counts must be positive (sizes below 2^30: the output size of an up=2 layer is an int)");
   MIGAN_CHECK(d->down == 1 || (h_in % 2 == 0 && w_in % 2 == 0), MIGAN_EINVAL, "down=2 needs even sizes");
   const int h_out = d->down == 2 ? h_in / 2 : (d->up == 2 ? h_in * 2 : h_in);
   const int w_out = d->down == 2 ? w_in / 2 : (d->up == 2 ? w_in * 2 : w_in);
@@ -2090,6 +2119,10 @@ static int migan_sepconv_run(const migan_sepconv_desc* d, int samples, void* str
   ld.fromrgb = fromrgb; ld.torgb = torgb; ld.skip = d->skip != nullptr; ld.noise = d->noise_const != nullptr;
   Geo g; DwGeo dg; int gemmv = 0;
   // (every refusal before the first launch: a refused call leaves y, img_out and the scratch tensors untouched)
+  // the extent limit of the kernels, on both branches: input (NCHW [4] planes under FromRGB), output = skip, and the scratch tensor of a
+  // down=2 layer ([h_out][w_out][cin]); img_out and img_prev have 3 channels of at most the output's pixels
+  MIGAN_CHECK(image_fits(h_in, w_in, fromrgb ? 4 : d->cin) && image_fits(h_out, w_out, d->cout) && (d->down != 2 || image_fits(h_out, w_out, d->cin)),
+              MIGAN_EINVAL, "image too large: " MIGAN_IMAGE_LIMIT_TEXT);
   if (is_narrow(d->cin, d->cout) && d->cin <= 64 && d->cout <= 64 && d->cin % 4 == 0 && d->cout % 4 == 0) {
     // fewer than 64 channels on either side (the layers of resolutions above 512): the plain kernel, the whole layer in one launch
     MIGAN_CHECK(stv == 0, MIGAN_EUNSUPPORTED, "layers with fewer than 64 channels run with fp32 activation storage only");

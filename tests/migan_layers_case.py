@@ -39,6 +39,7 @@ oracle with the same storage_close arguments, so a seed whose reference alone le
 
 Guards: every unit is finite everywhere; in fp32 storage a unit's optional terms (skip, noise, previous image) each exceed 10 x its bound,
 so a launch that drops one fails; the unit count is 5 * (log2 R - 1).  Test infrastructure only."""
+import threading
 import time
 from concurrent.futures import ThreadPoolExecutor
 
@@ -158,6 +159,15 @@ class Taps:
             finally:
                 h.close()
 
+    # what a unit reads: whole tensors here; WindowTaps serves the rows under one strip of the unit's output instead
+    def read(self, name, role, cls):
+        """role "in": the unit's input (name None: the network input x); "out": a tensor of the unit's own size (skip, the feature map under
+        an image); "prev": the previous, half-size image"""
+        return self.x if name is None else self.t[name]
+
+    def noise(self, p):
+        return p
+
     def kernels_of(self, name):
         """the symbols launch_info gave for the unit: its SeparableConv2d entry and the dwfir entry in front of it; an image unit: the
         un-fused ToRGB entry, or the conv2 launch whose tail writes the image"""
@@ -183,24 +193,26 @@ def _sub(sd, prefix, dt):
 
 def units(T):
     """-> [(name, class, fn(dt) -> (value before the storage rounding, {term: max |term|}))] in launch order; dt the oracle's arithmetic"""
-    R, sd, t = T.res, T.sd, T.t
+    R, sd = T.res, T.sd
     gemm16 = T.storage != "f32" and T.gemm == "f16"
     out = []
 
     def sep(name, src, cls, head=False, skip=None):
         def fn(dt):
-            x = (T.x if head else t[src]).astype(dt)
+            x = T.read(None if head else src, "in", cls).astype(dt)
             if head:
                 x = orc.lrelu_agc(orc.pointwise(x, sd[f"encoder.b{R}.fromrgb.weight"].astype(dt), sd[f"encoder.b{R}.fromrgb.bias"].astype(dt)))
-            p = _sub(sd, name, dt)
+            p = T.noise(_sub(sd, name, dt))
             y = orc.separable_conv(x, p, "m", gemm16)
             terms = {}
             if "m.noise_const" in p:
                 terms["noise"] = float(np.abs(p["m.noise_const"] * p["m.noise_strength"]).max())
             if skip is not None:
-                y = y + t[skip].astype(dt)
-                terms["skip"] = float(np.abs(t[skip]).max())
+                sk = T.read(skip, "out", cls)
+                y = y + sk.astype(dt)
+                terms["skip"] = float(np.abs(sk).max())
             return y, terms
+        fn.src = None if head else src
         out.append((name, cls, fn))
 
     r, prev = R, None
@@ -217,13 +229,14 @@ def units(T):
         sep(b + ".conv2", b + ".conv1", "syn.conv2")
 
         def img(dt, b=b, r=r):
-            y = orc.pointwise(t[b + ".conv2"].astype(dt), sd[b + ".torgb.weight"].astype(dt), sd[b + ".torgb.bias"].astype(dt))
+            y = orc.pointwise(T.read(b + ".conv2", "out", "img").astype(dt), sd[b + ".torgb.weight"].astype(dt), sd[b + ".torgb.bias"].astype(dt))
             terms = {}
             if r > 4:
-                up = orc.upsample2d(t[f"synthesis.b{r // 2}.img"].astype(dt))
+                up = orc.upsample2d(T.read(f"synthesis.b{r // 2}.img", "prev", "img").astype(dt))
                 y = y + up
                 terms["prev"] = float(np.abs(up).max())
             return y, terms
+        img.src = b + ".conv2"
         out.append((b + ".img", "img", img))
         prev = b + ".conv2"
         r *= 2
@@ -308,6 +321,143 @@ def run_case(lib, pkg, mem, *, res, batch, storage="f32", gemm=None, knobs={}, h
     print(format_rows(rows))
     assert not failures, (tag, "units over their bound (layer, kernel symbols, what)", failures)
     return {k for _, k in T.launches}
+
+
+class WindowTaps(Taps):
+    """A debug-plan forward whose taps stay on the device (GPU only, fp32 storage, batch 1): at the extent limit of the kernels the workspace
+    is some 30 GiB.  x is drawn on the device; read() serves the rows of a tap under the current strip of the unit's output (self.strip =
+    (o0, o1), set by run_window_case), with the rows of the input that strip depends on (tests/large_extent_case.py: in_rows, MARGIN)."""
+
+    def __init__(self, lib, pkg, dev, *, res, hw, seed):
+        import torch
+        from tests.sepconv_case import CudaMem
+        self.torch, mem = torch, CudaMem(dev)
+        self.res, self.batch, self.storage = res, 1, "f32"
+        self.hh, self.ww = hh, ww = hw
+        self.sd = pkg.synth.make_state_dict(res, seed=seed)
+        g = torch.Generator(device=dev)
+        g.manual_seed(seed)
+        self.xd = torch.empty((1, 4, hh, ww), device=dev).normal_(generator=g).mul_(0.7)
+        h = pkg.hipbind.MiganHandle(lib, res, dtype="f32")
+        try:
+            h.set_streams(1)
+            h.set_debug(True)
+            self.gemm = h.gemm()
+            keep = {k: mem.put(np.ascontiguousarray(v.reshape(1) if v.ndim == 0 else v)) for k, v in self.sd.items()}
+            for name, shape, _ in h.weights():
+                h.set_weight(name, mem.ptr(keep[name]), shape)
+            h.commit(mem.stream)
+            self.need = h.workspace_bytes_hw(1, hh, ww)
+            print(f"workspace_bytes_hw(1, {hh}, {ww}) of the debug plan: {self.need} bytes ({self.need / 2 ** 30:.2f} GiB)")
+            self.yd = torch.empty((1, 3, hh, ww), device=dev)
+            self.yd.view(torch.uint8).fill_(NAN_BYTE)
+            self.ws = torch.empty(self.need, dtype=torch.uint8, device=dev).fill_(NAN_BYTE)
+            assert self.ws.data_ptr() % 256 == 0
+            h.forward_hw(self.xd.data_ptr(), self.yd.data_ptr(), 1, hh, ww, self.ws.data_ptr(), self.need, mem.stream)
+            mem.sync()
+            self.where = {n: h.debug_tensor_hw(1, hh, ww, n) for n in unit_names(res) if n != f"synthesis.b{res}.img"}
+        finally:
+            h.close()
+        self.launches, self._local = [], threading.local()
+
+    @property
+    def strip(self):                      # per thread: run_window_case evaluates the units on a few threads
+        return self._local.strip
+
+    @strip.setter
+    def strip(self, v):
+        self._local.strip = v
+
+    def dev_tensor(self, name):
+        """(tensor on the device, True if NCHW): the network input, y and the images are planar, the feature maps NHWC"""
+        if name is None:
+            return self.xd, True
+        if name == f"synthesis.b{self.res}.img":
+            return self.yd, True
+        off, shape = self.where[name]
+        n = int(np.prod(shape))
+        return self.ws[off:off + 4 * n].view(self.torch.float32).view(*[int(v) for v in shape]), name.endswith(".img")
+
+    def rows(self, name, r0, r1):
+        t, planar = self.dev_tensor(name)
+        return t[:, :, r0:r1].cpu().numpy() if planar else nchw(t[:, r0:r1].cpu().numpy())
+
+    def read(self, name, role, cls):
+        from tests.large_extent_case import in_rows
+        o0, o1 = self.strip
+        if role == "in":
+            o0, o1 = in_rows(o0, o1, 2 if cls == "enc.conv2.down" else 1, 2 if cls == "syn.conv1.up" else 1)
+        elif role == "prev":
+            o0, o1 = o0 // 2, (o1 + 1) // 2
+        return self.rows(name, o0, o1)
+
+    def noise(self, p):
+        """noise_const [r][r] is tiled periodically down the layer (orc.noise_plane): the strip starts at row o0 of it"""
+        if "m.noise_const" in p:
+            p["m.noise_const"] = np.roll(p["m.noise_const"], -(self.strip[0] % p["m.noise_const"].shape[0]), axis=0)
+        return p
+
+
+WHOLE_BELOW = 1 << 22          # elements: smaller units are evaluated whole, the others on the row windows of tests/large_extent_case.py
+
+
+def run_window_case(lib, pkg, dev, *, res, hw, seed, tag="", report=None):
+    """run_case for a size whose taps cannot visit the host: one debug-plan forward through migan_forward_hw, then every unit on row
+    windows of its output (the first rows, the last, the strips around byte 2^31 of its input and output, four seeded random strips), from
+    the device's own input rows, under the same bounds and guards as run_case.  Every tap is finite everywhere (checked on the device)."""
+    from tests.large_extent_case import all_finite, strips
+    t0 = time.perf_counter()
+    T = WindowTaps(lib, pkg, dev, res=res, hw=hw, seed=seed)
+    us = units(T)
+    assert len(us) == 5 * levels(res) == len(unit_names(res)), (tag, len(us))
+
+    def check(k):
+        name, cls, fn = us[k]
+        failures = []
+        t, planar = T.dev_tensor(name)
+        ho = int(t.shape[2] if planar else t.shape[1])
+        is_img = cls == "img"
+        if not all_finite(t):
+            return None, [(name, "elements are not finite (unwritten output, or a read of unwritten memory)")]
+        if t.numel() < WHOLE_BELOW:
+            ss = [(0, ho, 0, ho, "whole")]
+        else:
+            src, src_planar = T.dev_tensor(fn.src)
+            xb, yb = (0 if src_planar else src.numel() * 4), (0 if planar else t.numel() * 4)
+            ss = strips(ho, max(1, xb // ho), max(1, yb // ho), xb, yb, seed + k)
+        worst, bound_max, wmax, seen = 0.0, 0.0, 0.0, {}
+        for o0, o1, c0, c1, sname in ss:
+            T.strip = (o0, o1)
+            want, terms = fn(np.float64)
+            if not is_img:
+                want = orc.round_storage(want, "f32")
+            got = T.rows(name, o0, o1)
+            assert got.shape == want.shape, (name, sname, got.shape, want.shape)
+            wv, gv = want[:, :, c0 - o0:c1 - o0], got[:, :, c0 - o0:c1 - o0]
+            scale = max(1.0, float(np.abs(wv).max()))
+            bound = (3e-5 if is_img else 2e-5) * scale
+            err = float(np.abs(gv.astype(np.float64) - wv.astype(np.float64)).max())
+            if not err <= bound:
+                failures.append((name, sname, f"rows [{c0}, {c1}): max abs error {err:.3e} over the bound {bound:.3e}"))
+            worst, bound_max, wmax = max(worst, err / bound), max(bound_max, bound), max(wmax, float(np.abs(wv).max()))
+            for term, mag in terms.items():
+                seen[term] = max(seen.get(term, 0.0), mag)
+        for term, mag in seen.items():
+            if not mag > 10 * bound_max:
+                failures.append((name, f"vacuous: the {term} term ({mag:.3e}) is below 10 x the bound ({bound_max:.3e})"))
+        return (tag, name, cls, tuple(t.shape), len(ss), f"{wmax:.3g}", f"{worst:.3f}"), failures
+
+    # the units are independent of each other (each reads the device's taps): a few threads, as in run_case
+    with ThreadPoolExecutor(max_workers=8) as pool:
+        done = list(pool.map(check, range(len(us))))
+    rows = [r for r, _ in done if r is not None]
+    failures = [f for _, fs in done for f in fs]
+    print("| case | unit | class | shape | windows | max abs want | error / bound |\n|---|---|---|---|---|---|---|")
+    for r in rows:
+        print("| " + " | ".join(str(v) for v in r) + " |")
+    if report is not None:
+        report.update(rows=rows, seconds=time.perf_counter() - t0, workspace_bytes=T.need)
+    assert not failures, (tag, "units over their bound (layer, window, what)", failures)
 
 
 def format_rows(rows):

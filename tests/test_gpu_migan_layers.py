@@ -4,7 +4,7 @@ wall time of each case: profiles/migan_layers.md."""
 import pytest
 import torch
 
-from tests.migan_layers_case import GPU_16BIT, GPU_16BIT_KNOBS, GPU_CASES, GPU_F32, is_small, run_case
+from tests.migan_layers_case import GPU_16BIT, GPU_16BIT_KNOBS, GPU_CASES, GPU_F32, is_small, run_case, run_window_case
 from tests.sepconv_case import CudaMem
 
 pytestmark = pytest.mark.gpu
@@ -39,6 +39,18 @@ def _run(pkg, lib, dev, name):
 def test_every_launch_in_isolation(pkg, lib, dev, name):
     _run(pkg, lib, dev, name)
     print(f"{name}: {REPORT[name]['seconds']:.2f} s, of which bind + forward + read-back {REPORT[name]['device_seconds']:.2f} s")
+
+
+def test_generator_at_the_extent_limit(pkg, lib, dev):
+    """Generator(512) through migan_forward_hw at 4096 x 3968, the largest multiples of 128 whose full-resolution tensors (64 channels)
+    stay within the extent limit of the kernels, 2^30 - 1024 elements (4096 x 4096 is refused): every unit in plan context, on row
+    windows read back from the device (the debug workspace is some 30 GiB)"""
+    import torch
+    assert 4096 * 3968 * 64 <= 2 ** 30 - 1024 < 4096 * 4096 * 64
+    rep = {}
+    run_window_case(lib, pkg, dev, res=512, hw=(4096, 3968), seed=251, tag="r512_4096x3968", report=rep)
+    torch.cuda.empty_cache()
+    print(f"r512_4096x3968: {rep['seconds']:.2f} s, debug workspace {rep['workspace_bytes']} bytes")
 
 
 def _union(pkg, lib, dev, names):

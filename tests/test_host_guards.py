@@ -45,6 +45,51 @@ def test_oversize_forward_hw_is_refused_by_the_offset_width_not_a_pixel_cap(pkg,
         h512.workspace_bytes_hw(1, 4096, 4096)
 
 
+# the extent limit (kMaxImageElems in migan_host.hpp): h * w * channels <= 2^30 - 1024 for every per-image tensor
+LIMIT = 2 ** 30 - 1024
+OPERATOR_EDGES = [
+    # name, layer, (h, w) one step beyond the limit, the step before it (one row less)
+    ("64to64", dict(cin=64, cout=64), (4096, 4096), (4095, 4096)),
+    ("64to256", dict(cin=64, cout=256), (2048, 2048), (2047, 2048)),
+    ("64to64_up", dict(cin=64, cout=64, up=2), (2048, 2048), (2047, 2048)),             # the output is the larger tensor
+    ("64to128_down", dict(cin=64, cout=128, down=2), (4096, 4096), (4094, 4096)),       # the input is
+    ("narrow", dict(cin=32, cout=32), (8192, 4096), (8191, 4096)),
+    ("sliver", dict(cin=64, cout=64), (4095, 4097), (4095, 4096)),                      # 2^32 - 256 bytes: the padding marker in range
+]
+
+
+@pytest.mark.parametrize("name,layer,beyond,inside", OPERATOR_EDGES, ids=[e[0] for e in OPERATOR_EDGES])
+def test_operator_refuses_one_step_beyond_the_extent_limit(pkg, lib, name, layer, beyond, inside):
+    """migan_sepconv_forward applies the plan's limit, on the tiled and on the narrow branch, before any launch: small buffers suffice,
+    and they keep their fill.  (The size just inside cannot run on the emulator; tests/test_gpu_large_extents.py runs it on the GPU.)"""
+    cin, cout = layer["cin"], layer["cout"]
+    f = lambda h, w: (h // 2, w // 2) if layer.get("down") == 2 else ((2 * h, 2 * w) if layer.get("up") == 2 else (h, w))
+    top = lambda h, w: max(h * w * cin, f(h, w)[0] * f(h, w)[1] * cout)
+    assert top(*inside) <= LIMIT < top(*beyond)
+    fill = lambda n: aligned(np.full(n, 7.5, np.float32))
+    x, y, skip, scratch, img = fill(4096), fill(4096), fill(4096), fill(4096), fill(4096)
+    w1, b1, w2 = fill(cin * 9), fill(cin), fill(cin * cout)
+    nc, ns, wsp = fill(4096), fill(1), fill(2 * cin * cout + 64)
+    for samples in ((None,) if name == "narrow" or layer.get("down") else (None, 1)):
+        with pytest.raises(ValueError, match="too large"):
+            lib.sepconv_forward(samples=samples, x=x.ctypes.data, y=y.ctypes.data, skip=skip.ctypes.data, conv1_weight=w1.ctypes.data,
+                                conv1_bias=b1.ctypes.data, conv2_weight=w2.ctypes.data, noise_const=nc.ctypes.data,
+                                noise_strength=ns.ctypes.data, batch=1, cin=cin, cout=cout, res_in=beyond[0], width_in=beyond[1],
+                                down=layer.get("down", 1), up=layer.get("up", 1), scratch=scratch.ctypes.data, scratch_bytes=1 << 40,
+                                wsplit=wsp.ctypes.data, wsplit_bytes=wsp.nbytes, dtype=0)
+    for a in (x, y, skip, scratch, img, w1, b1, w2, nc, ns, wsp):
+        assert (a == 7.5).all(), "a refused call wrote a buffer"
+
+
+def test_the_size_just_inside_the_extent_limit_plans(pkg, lib):
+    """the plan and the operator share the function: Generator(512) has 64 channels at full size, 4096 x 3968 is the largest multiple of
+    128 below 2^24 - 16 pixels"""
+    h512 = pkg.hipbind.MiganHandle(lib, 512)
+    assert 4096 * 3968 * 64 <= LIMIT < 4096 * 4096 * 64
+    assert h512.workspace_bytes_hw(1, 4096, 3968) > 0
+    assert h512.workspace_bytes_hw(1, 3968, 4096) > 0
+
+
 def test_a_failed_plan_is_not_cached(pkg, lib):
     """sizes that are refused leave nothing behind: asking again fails the same way, and a valid size still plans and runs"""
     res = 8
