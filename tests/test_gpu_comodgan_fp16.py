@@ -73,7 +73,7 @@ def test_default_mode_names_no_single_plane_kernel_and_the_exports_exist(pkg, de
     assert not any(F16 in i["kernel"] for i in m.launch_info())
     assert m._handle.fp16_blocks() == (None, None)
     for name in ("comodgan_set_fp16_blocks", "comodgan_get_fp16_blocks"):
-        assert name in pkg.hipbind.FP16_EXPORTS and hasattr(m._lib.lib, name)
+        assert name in pkg.hipbind.exports("comodgan_fp16_hip.h") and hasattr(m._lib.lib, name)
     with pytest.raises(ValueError):
         m._handle.set_fp16_blocks(-2, 4)
     assert m._lib.backend() == "hip:gfx950"

@@ -70,7 +70,7 @@ def test_nothing_moves_without_marked_blocks(pkg, dev, golden_dir):
     assert m._handle.get_fp16_storage() is True
     assert m.launch_info() == info32 and m._handle.workspace_bytes(n) == ws32
     assert torch.equal(y, y32)
-    for name in pkg.hipbind.FP16_STORAGE_EXPORTS:
+    for name in pkg.hipbind.exports("comodgan_fp16_storage_hip.h"):
         assert hasattr(m._lib.lib, name)
 
 

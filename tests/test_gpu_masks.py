@@ -161,5 +161,5 @@ def test_exports_in_the_built_libraries(pkg, lib):
     assert lib.backend() == "hip:gfx950"
     for path in (pkg.library_path(), os.path.join(os.path.dirname(pkg.library_path()), "libmigan_hip_nanclamp.so")):
         loaded = pkg.hipbind.MiganLib(path)
-        for name in pkg.hipbind.MASKS_EXPORTS:
+        for name in pkg.hipbind.exports("migan_masks_hip.h"):
             assert hasattr(loaded.lib, name), f"{path} does not export {name}"

@@ -152,7 +152,7 @@ def test_both_libraries_export_the_entries(pkg):
     build = importlib.import_module("mi-gan_amd.build")
     for path in (build.OUT, build.NAN_CLAMP_OUT):
         L = pkg.hipbind.MiganLib(path)                   # (refuses a library that lacks one of hipbind's export lists)
-        for name in pkg.hipbind.NOISE_SAMPLES_EXPORTS:
+        for name in pkg.hipbind.exports("migan_noise_samples_hip.h"):
             assert hasattr(L.lib, name), (path, name)
 
 

@@ -60,7 +60,7 @@ def test_exports_in_the_built_libraries(pkg, lib):
     assert lib.backend() == "hip:gfx950"
     for path in (pkg.library_path(), os.path.join(os.path.dirname(pkg.library_path()), "libmigan_hip_nanclamp.so")):
         loaded = pkg.hipbind.MiganLib(path)
-        for name in pkg.hipbind.PHOTO_EXPORTS:
+        for name in pkg.hipbind.exports("migan_photo_hip.h"):
             assert hasattr(loaded.lib, name), f"{path} does not export {name}"
 
 
