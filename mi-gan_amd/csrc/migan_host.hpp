@@ -24,6 +24,7 @@
 #include "../../include/migan_pipeline_patches_hip.h"
 #include "../../include/migan_pipeline_regions_hip.h"
 #include "../../include/migan_pipeline_region_patches_hip.h"
+#include "../../include/migan_pipeline_native_hip.h"
 #include "../../include/migan_metrics_hip.h"
 #include "../../include/migan_photo_hip.h"
 #include "../../include/migan_masks_hip.h"
@@ -2633,6 +2634,62 @@ int migan_pipeline_regions_post(const migan_pipeline_region_row* rows, int m, in
   migan_pipeline_gauss(gauss25, a.gauss);
   migan_pipeline_rows_launch(pipe_post_rows_kernel, "migan::pipe_post_rows_kernel", a, its,
                              [](const PipeRowItem& it) { return migan_pipeline_box_tiles(it.box); }, (size_t)kPostLdsBytes + 16, stream);
+  MIGAN_API_END
+}
+
+// ---- crops at native size (include/migan_pipeline_native_hip.h): rows whose network window [height][width] has one size ----
+// the rows -> the kernels' table: migan_pipeline_rows_plan's checks, the window, and every box against it
+static void migan_pipeline_native_plan(const migan_pipeline_region_row* rows, int m, int height, int width, std::vector<migan::PipeRowItem>* out) {
+  using namespace migan;
+  MIGAN_CHECK(height >= 1 && width >= 1 && (unsigned long long)height * (unsigned long long)width < (1ull << 28), MIGAN_EINVAL,
+              "the window must be at least 1 x 1 and below 2^28 pixels (the four planes of a row stay below 2^30 elements)");
+  migan_pipeline_rows_plan(rows, m, 8, out);                          // (no resolution here: 8 passes its check)
+  for (int i = 0; i < m; ++i)
+    MIGAN_CHECK(rows[i].box[1] - rows[i].box[0] <= width && rows[i].box[3] - rows[i].box[2] <= height, MIGAN_EINVAL,
+                "row " + std::to_string(i) + ": the box is wider or taller than the window");
+}
+// one kernel over all rows (table_split, table_launch): x and y of a launch begin at its first row, 64-bit
+extern "C++" template <class Tiles>
+static void migan_pipeline_native_launch(void (*kernel)(const migan::PipeNativeArgs), const char* name, const migan::PipeNativeArgs& proto,
+                                         const std::vector<migan::PipeRowItem>& rows, Tiles tiles, size_t lds, void* stream) {
+  using namespace migan;
+  const size_t plane = (size_t)proto.height * proto.width;
+  const auto t = [&](int i) { return (unsigned long long)tiles(rows[(size_t)i]); };
+  for (const TableLaunch& l : table_split((int)rows.size(), t, table_items<PipeNativeArgs>))
+    table_launch(kernel, name, proto, l, t, [&](PipeNativeArgs& a, int j, int i) { a.item[j] = rows[(size_t)i]; },
+                 [&](PipeNativeArgs& a, int i0) {
+                   if (a.x) a.x += (size_t)i0 * 4 * plane;
+                   if (a.y) a.y += (size_t)i0 * 3 * plane;
+                 },
+                 kThreads, lds, stream);
+}
+int migan_pipeline_native_pre(const migan_pipeline_region_row* rows, int m, int height, int width, void* x_nchw, void* stream) {
+  MIGAN_API_BEGIN
+  using namespace migan;
+  MIGAN_CHECK(x_nchw, MIGAN_EINVAL, "null tensor");
+  std::vector<PipeRowItem> its;
+  migan_pipeline_native_plan(rows, m, height, width, &its);
+  PipeNativeArgs a{};
+  a.x = (float*)x_nchw; a.height = height; a.width = width;
+  // four columns per thread, one 16-byte store per plane: every window row, plane and row of x then begins on a 16-byte boundary
+  a.quads = width % 4 == 0 && (uintptr_t)x_nchw % 16 == 0 ? 1 : 0;
+  const unsigned long long per_row = (unsigned long long)cdiv(height * (a.quads ? width / 4 : width), kThreads);
+  migan_pipeline_native_launch(pipe_pre_native_kernel, "migan::pipe_pre_native_kernel", a, its, [=](const PipeRowItem&) { return per_row; }, 0, stream);
+  MIGAN_API_END
+}
+// the box is host data: the grid has exactly the box's tiles
+int migan_pipeline_native_post(const migan_pipeline_region_row* rows, int m, int height, int width, const void* y_nchw, const float* gauss25,
+                               void* stream) {
+  MIGAN_API_BEGIN
+  using namespace migan;
+  MIGAN_CHECK(y_nchw, MIGAN_EINVAL, "null tensor");
+  std::vector<PipeRowItem> its;
+  migan_pipeline_native_plan(rows, m, height, width, &its);
+  PipeNativeArgs a{};
+  a.y = (const float*)y_nchw; a.height = height; a.width = width;
+  migan_pipeline_gauss(gauss25, a.gauss);
+  migan_pipeline_native_launch(pipe_post_native_kernel, "migan::pipe_post_native_kernel", a, its,
+                               [](const PipeRowItem& it) { return migan_pipeline_box_tiles(it.box); }, (size_t)kPostLdsBytes + 16, stream);
   MIGAN_API_END
 }
 

@@ -17,6 +17,7 @@
 // migan_pipeline_batch_post_samples) and as box-sized patches (PipePatchesArgs; migan_pipeline_batch_post_patches).
 // A fourth form gives every hole region of an image a box of its own (migan_pipeline_regions.inc; migan_pipeline_regions_*), in
 // place, or out of place as S box-sized patches per region with a paste step back (migan_pipeline_region_patches.inc).
+// A fifth form runs rows at the photo's own scale, around the fully convolutional forward (migan_pipeline_native.inc).
 #pragma once
 
 #ifndef MIGAN_HOST_DEVICE          // (the CPU emulator build is host code throughout)
@@ -523,6 +524,8 @@ MIGAN_GLOBAL void MIGAN_LAUNCH_BOUNDS(256, 2) pipe_post_patches_kernel(const Pip
 #include "migan_pipeline_regions.inc"
 // ---- S completions per hole region as patches, and the paste back (include/migan_pipeline_region_patches_hip.h) ----------------------
 #include "migan_pipeline_region_patches.inc"
+// ---- crops at native size around the fully convolutional forward: no resampling (include/migan_pipeline_native_hip.h) ----------------
+#include "migan_pipeline_native.inc"
 #endif  // MIGAN_TEMPLATE_KERNELS_ONLY
 
 }  // namespace migan

@@ -295,6 +295,10 @@ ABI = {
         "migan_forward_samples_hw": (ci, (vp, vp, vp, vp, ci, ci, ci, ci, vp, sz, vp)),
         "migan_sepconv_forward_samples": (ci, (P(SepConvDesc), ci, vp)),
     },
+    "migan_pipeline_native_hip.h": {
+        "migan_pipeline_native_pre": (ci, (P(PipelineRegionRow), ci, ci, ci, vp, vp)),
+        "migan_pipeline_native_post": (ci, (P(PipelineRegionRow), ci, ci, ci, vp, P(fl), vp)),
+    },
 }
 
 
@@ -514,6 +518,16 @@ class MiganLib:
         row's patches; it is copied into the image where labels == label (label 0: the whole box)"""
         self.check(self.lib.migan_pipeline_regions_paste(pipeline_region_paste_rows(rows), 0 if rows is None else len(rows),
                                                          C.c_void_p(stream)))
+
+    # crops at native size (include/migan_pipeline_native_hip.h): rows as for pipeline_regions_pre, the box = the part of the
+    # [height, width] network window inside the photo; x [len(rows), 4, height, width], y [len(rows), 3, height, width]
+    def pipeline_native_pre(self, rows, height: int, width: int, x_ptr: int, stream: int = 0) -> None:
+        self.check(self.lib.migan_pipeline_native_pre(pipeline_region_rows(rows), 0 if rows is None else len(rows), int(height), int(width),
+                                                      C.c_void_p(x_ptr), C.c_void_p(stream)))
+
+    def pipeline_native_post(self, rows, height: int, width: int, y_ptr: int, gauss25=None, stream: int = 0) -> None:
+        self.check(self.lib.migan_pipeline_native_post(pipeline_region_rows(rows), 0 if rows is None else len(rows), int(height), int(width),
+                                                       C.c_void_p(y_ptr), _gauss(gauss25), C.c_void_p(stream)))
 
     # PSNR / SSIM of completions against the photo (include/migan_metrics_hip.h): `items` = [(gt_ptr, pred_ptr, mask_ptr or None, H, W), ...]
     def metrics_scratch_bytes(self, items, samples: int) -> int:

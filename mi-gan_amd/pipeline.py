@@ -70,6 +70,10 @@ class MIGAN_Pipeline(torch.nn.Module):
     ``forward_regions(images, masks)`` is ``forward_batch`` with one crop per hole region instead of one per image: a photo with
     several marked objects far apart gets each of them completed at its own scale (``migan_pipeline_regions_find / _pre / _post``).
 
+    ``forward_native(images, masks)`` is ``forward_regions`` without the two resamplings: every crop is rounded up to the generator's
+    granularity and completed at the photo's own scale by the fully convolutional forward (``migan_pipeline_native_pre / _post``
+    around ``Generator.forward_any_size``).  Its effect on image quality has not been measured.
+
     ``forward_region_patches(images, masks, z)`` joins the two: S completions per hole region, returned as box-sized patches, with the
     photos left as they are; ``paste_patches`` writes the chosen completion of every region into its photo
     (``migan_pipeline_regions_post_patches / _paste``)."""
@@ -412,6 +416,142 @@ class MIGAN_Pipeline(torch.nn.Module):
                     y = self.model(x[r0:r0 + len(chunk) + (1 if lone and len(chunk) == 1 else 0)]).contiguous()
                     lib.pipeline_regions_post(chunk, res, y.data_ptr(), gauss25=self._gauss, stream=stream)
         return (images, used, labels) if return_regions else images
+
+    def native_window(self, box, H: int, W: int):
+        """The window rule of ``forward_native``, a pure function of integers: ``box`` = (x_min, x_max, y_min, y_max), the
+        reference's box inside an H x W photo -> ``((x0, x1, y0, y1), (Hc, Wc))``: the network window Hc x Wc, both sides the box's
+        rounded up to a multiple of q = resolution / 4 (the granularity of ``Generator.forward_any_size``), and the part of it that
+        lies inside the photo.
+
+        Per axis (columns; rows alike): Wc = ceil(cw / q) q.  Wc <= W: the window lies inside the photo, the extra columns taken
+        evenly from either side of the box and shifted back inside at a border, x0 = clamp(x_min - (Wc - cw) // 2, 0, W - Wc),
+        x1 = x0 + Wc -- real photo context.  Wc > W (the photo is narrower than the window): x0 = 0, x1 = W, and columns W ... Wc - 1
+        of the network input are unknown pixels.  The in-photo box always sits at the window's top-left corner; a box whose sides
+        are multiples of q comes back unchanged."""
+        q = self.res // 4
+        x_min, x_max, y_min, y_max = (int(v) for v in box)
+
+        def axis(lo, hi, n):
+            side = hi - lo
+            full = -(-side // q) * q
+            if full > n:
+                return 0, n, full
+            at = min(max(lo - (full - side) // 2, 0), n - full)
+            return at, at + full, full
+
+        x0, x1, wc = axis(x_min, x_max, int(W))
+        y0, y1, hc = axis(y_min, y_max, int(H))
+        return (x0, x1, y0, y1), (hc, wc)
+
+    @torch.no_grad()
+    def forward_native(self, images, masks, *, max_side=None, gap=None, max_regions: int = 8, max_batch: int = 32,
+                       return_rows: bool = False):
+        """``forward_regions`` WITHOUT RESAMPLING: every row's crop goes through the generator at the photo's own scale
+        (``Generator.forward_any_size``, the fully convolutional forward) instead of being squeezed to R x R and blown up again.
+        Arguments, checks and error types are ``forward_regions``'; the images are modified in place and returned as a list.  The
+        model must have ``forward_any_size`` (the MI-GAN ``Generator``): any other model (Co-Mod-GAN, whose encoder ends in a dense
+        layer; ``NoiseSampler``) raises ``RuntimeError`` before anything is launched.
+
+        WHAT IS AND IS NOT KNOWN ABOUT THIS MODE: it is an exact composition of pieces that are each tested -- the window rule, the
+        network input and the blend of ``migan_pipeline_native_pre / _post``, ``forward_any_size`` -- and the tests hold it to that,
+        byte for byte.  No trained checkpoint was at hand when it was written: what it does to IMAGE QUALITY (a generator trained
+        at R x R, run on a larger window with its noise planes tiled) HAS NOT BEEN MEASURED.
+
+        Rows and boxes are ``forward_regions``' (``_regions_rows``: the same one host synchronisation per call, the same "when not
+        to split" rule; ``max_regions=1`` gives one box per photo).  Every box goes through ``native_window``: its sides rounded up
+        to multiples of R / 4, grown into the photo around it; where the photo is smaller than the window the missing part of the
+        network input is unknown pixels, mask 0 -- x = (-0.5, 0, 0, 0) -- not replicated or reflected photo.
+
+        A row is a FALLBACK row, run resized at R exactly as ``forward_regions`` runs it, when its window has a side above
+        ``max_side`` (default 4 R; must be in R ... 4096) or when Hc Wc max(4, 32768 // R) exceeds 2^30 - 1024, the extent limit of
+        ``migan_forward_hw`` (32768 // R = the generator's channels at full resolution).
+
+        Order of work: the network input of ALL rows first (``migan_pipeline_native_pre`` per window size,
+        ``migan_pipeline_regions_pre`` for the fallback rows), as in ``forward_regions``.  Then, per window size in ascending
+        (Hc, Wc) order, the rows in row order in calls of at most ``max(1, max_batch R^2 // (Hc Wc))`` rows -- no more activation
+        memory than a ``forward_batch`` chunk -- each ONE ``model.forward_any_size(x)`` and one ``migan_pipeline_native_post``.
+        The rows with an R x R window and the fallback rows run, at (R, R)'s place in that order, as ``forward_regions`` runs its
+        rows: ``self.model(x)`` on chunks of ``max_batch``, a lone last chunk at batch 2.
+
+        Consequences.  A call in which every row is a fallback or has an R x R window that lies inside its photo leaves
+        ``forward_regions``' bytes (``torch.equal``).  In every other group a row's result may differ by fp32 rounding with the
+        batch it shares a forward with, as ``forward`` differs from ``forward_batch``; a lone row of such a group runs at batch 1.
+
+        With ``return_rows`` also returns the list of generator calls in the order they ran, each ``(Hc, Wc, [(image index, label,
+        box), ...])`` with the rows in the order of x: box = the in-photo box of ``native_window``; a fallback row is listed in an
+        (R, R) call with the reference's box."""
+        images, masks = list(images), list(masks)
+        any_size = getattr(self.model, "forward_any_size", None)
+        if any_size is None:
+            raise RuntimeError(f"forward_native needs a model with forward_any_size (the MI-GAN Generator's fully convolutional "
+                               f"forward); {type(self.model).__name__} has none")
+        if len(images) != len(masks) or not images:
+            raise RuntimeError(f"expected as many masks as images and at least one, got {len(images)} images and {len(masks)} masks")
+        if int(max_batch) < 1:
+            raise RuntimeError(f"max_batch must be at least 1, got {max_batch}")
+        res = self.res
+        max_side = 4 * res if max_side is None else int(max_side)
+        if not res <= max_side <= max(4096, 4 * res):
+            raise ValueError(f"max_side must be in {res} ... 4096, got {max_side}")
+        gap, max_regions, max_batch = *self._regions_args(gap, max_regions), int(max_batch)
+        items, device = self._batch_items(images, masks)
+        lib = load_library()
+        calls = []
+        with torch.cuda.device(device):                          # the handle-free entry points launch on the CURRENT device
+            stream = int(torch.cuda.current_stream(device).cuda_stream)
+            rows, owner, _, labels, full = self._regions_rows(lib, items, device, stream, gap, max_regions)  # (`full`, `labels`: kept alive)
+            # window size -> [(row as the kernels take it, its entry in a call's list, native or fallback), ...] in row order;
+            # (R, R) also holds the fallback rows
+            groups = {}
+            for row, i in zip(rows, owner):
+                win, (hc, wc) = self.native_window(row[6], row[3], row[4])
+                if max(hc, wc) > max_side or hc * wc * max(4, 32768 // res) > 2 ** 30 - 1024:
+                    groups.setdefault((res, res), []).append((row, (i, row[5], tuple(row[6])), False))
+                else:
+                    groups.setdefault((hc, wc), []).append((row[:6] + (win,), (i, row[5], win), True))
+
+            def runs(group):
+                """maximal runs of one kind: (first index, rows as the kernels take them, native or fallback)"""
+                at = 0
+                while at < len(group):
+                    end = at
+                    while end < len(group) and group[end][2] == group[at][2]:
+                        end += 1
+                    yield at, [g[0] for g in group[at:end]], group[at][2]
+                    at = end
+
+            xs = {}
+            for (hc, wc), group in groups.items():
+                square = (hc, wc) == (res, res)
+                # forward_regions' rule for a lone last chunk: it runs at batch 2 (its x twice), so no row sees a batch-1 forward
+                lone = square and len(group) % max_batch == 1 and len(group) > 1 and max_batch > 1
+                x = torch.empty((len(group) + (1 if lone else 0), 4, hc, wc), dtype=torch.float32, device=device)
+                for at, part, native in runs(group):
+                    if native:
+                        lib.pipeline_native_pre(part, hc, wc, x[at].data_ptr(), stream)
+                    else:
+                        lib.pipeline_regions_pre(part, res, x[at].data_ptr(), stream)
+                if lone:
+                    x[-1].copy_(x[-2])
+                xs[(hc, wc)] = (x, lone)
+            for (hc, wc) in sorted(groups):
+                group, (x, lone) = groups[(hc, wc)], xs.pop((hc, wc))
+                square = (hc, wc) == (res, res)
+                per_call = max_batch if square else max(1, max_batch * res * res // (hc * wc))
+                for r0 in range(0, len(group), per_call):
+                    chunk = group[r0:r0 + per_call]
+                    if square:
+                        y = self.model(x[r0:r0 + len(chunk) + (1 if lone and len(chunk) == 1 else 0)]).contiguous()
+                    else:
+                        y = any_size(x[r0:r0 + len(chunk)]).contiguous()
+                    for at, part, native in runs(chunk):
+                        if native:
+                            lib.pipeline_native_post(part, hc, wc, y[at].data_ptr(), gauss25=self._gauss, stream=stream)
+                        else:
+                            lib.pipeline_regions_post(part, res, y[at].data_ptr(), gauss25=self._gauss, stream=stream)
+                    calls.append((hc, wc, [g[1] for g in chunk]))
+            del full, labels                                     # (the masks and label maps lived until their readers were queued)
+        return (images, calls) if return_rows else images
 
     def _regions_args(self, gap, max_regions):
         """the checks of ``gap`` and ``max_regions`` forward_regions and forward_region_patches share -> gap, max_regions"""
