@@ -356,9 +356,11 @@ class Layers:
 
 
 def check_layers(lib, mem, cfg, sd, x, z, *, psi=1.0, cutoff=None, noise_mode="const", noise=None, flags=(None, None), storage=False,
-                 samples=1, u8=None, kernels=(), tag="", report=None):
+                 samples=1, u8=None, kernels=(), tag="", report=None, premise=None):
     """One normal-plan and one debug-plan forward on a fresh handle; every assertion the layer test makes.  x [N,4,R,R] (or None
-    with u8 = (img [N,R,R,3], mask [N,R,R])), z [N*S, z_dim].  -> (rows of the per-unit table, unit count)"""
+    with u8 = (img [N,R,R,3], mask [N,R,R])), z [N*S, z_dim].  premise(L): what the case claims to reach, asserted on the Layers
+    object once L.wants / L.fns hold every unit's float64 value and function (never on the device's output).
+    -> (rows of the per-unit table, unit count)"""
     R, S = cfg.resolution, samples
     n = (u8[0] if u8 is not None else x).shape[0]
     B = n * S
@@ -398,7 +400,8 @@ def check_layers(lib, mem, cfg, sd, x, z, *, psi=1.0, cutoff=None, noise_mode="c
     y_debug, info_debug, ws_host = forward(True)
     # the two plans run the same kernels on the same operands: only the buffers and the side stream differ
     assert info_debug == info_normal, (tag, [a for a in zip(info_debug, info_normal) if a[0] != a[1]][:4])
-    assert np.array_equal(y_debug, y_normal), (tag, "y differs between the debug and the normal plan")
+    # (bytes, not values: an output that is NaN in both plans goes on to the units below, which name the launch it came from)
+    assert y_debug.tobytes() == y_normal.tobytes(), (tag, "y differs between the debug and the normal plan")
     kernel_of = dict(info_debug)
     if report is not None:
         report["kernels"] = sorted(set(kernel_of.values()))
@@ -484,8 +487,16 @@ def check_layers(lib, mem, cfg, sd, x, z, *, psi=1.0, cutoff=None, noise_mode="c
                 if not d > 10 * b_abs:
                     vacuous.append((name, f"the {term} term is below 10 x the bound", d, b_abs))
         print(format_rows(rows))
-        assert not vacuous, (tag, "units that could pass vacuously", vacuous)
+        # a faulty launch first: a NaN or an unclamped value that it hands on makes the units behind it look vacuous
         assert not failures, (tag, "units over their bound (unit, class, error, bound, ratio)", failures)
+        assert not vacuous, (tag, "units that could pass vacuously", vacuous)
+        # after the units, so that a faulty launch is reported as such and not as the premise it breaks downstream
+        if premise is not None:
+            L.wants, L.fns = {r[0]: r[5] for r in res}, {r[0]: r[3] for r in res}
+            notes = premise(L)
+            print(tag, "premises reached:", notes)
+            if report is not None:
+                report["premise"] = notes
     return rows, len(units)
 
 
@@ -635,6 +646,152 @@ GPU_CASES = {
 }
 
 
+# ---- at the bounds the operand scaling is derived from -------------------------------------------------------------------------
+# kCmInBound = 512 (a convolution input: 256 from lrelu_agc's clamp + 256 of skip tensor), kCmF16Top = 2^15 (the scaled A operand)
+# and the per-sample style exponent e = 6 - (floor(log2 mx) + 1) of cm_style_block.  Random weights stay two orders of magnitude
+# below all three, so the cases below dress the state dict until every layer sits on them.
+def demodulated(cfg):
+    """[(prefix, widx, input tap)] of the modulated 3x3 layers, in launch order"""
+    out, prev = [("synthesis.b4.conv", 0, "synthesis.b4.fc")], "synthesis.b4.conv"
+    for k, r in enumerate(resolutions(cfg)):
+        out += [(f"synthesis.b{r}.conv0", 1 + 2 * k, prev), (f"synthesis.b{r}.conv1", 2 + 2 * k, f"synthesis.b{r}.conv0")]
+        prev = f"synthesis.b{r}.conv1"
+    return out
+
+
+def pinned_m(t, ci):
+    """|style| of the one channel whose normalised value is t when the other ci - 1 styles are +-1: t = m * sqrt(ci / (ci - 1 + m^2))"""
+    assert 1.0 < t * t < ci
+    return float(np.sqrt(np.float64(t) ** 2 * (ci - 1) / (ci - np.float64(t) ** 2)))
+
+
+def dress(cfg, sd, styles=None):
+    """A copy of a make_comodgan_state_dict() result that drives every layer to its bounds.
+    Locked channels: in every bias in front of an lrelu_agc that produces a feature map (the conv_b entries, and synthesis.b4.fc's by
+    channel), channel co % 4 == 1 becomes +1e5 and co % 4 == 3 becomes -1e5: exactly +256 / -256 behind the clamp whatever the input.
+    The encoder's skip tensor and the synthesis conv0 it is added to are locked on the same channels with the same sign, so a
+    synthesis conv1 (and synthesis.b4.conv) reads exactly +-512 there.  The other half of the channels stays as drawn.
+    styles = t: the largest normalised style of every demodulated layer is pinned to t, on channel 1 (a +256 / +512 channel): the
+    affine weight becomes zero and the affine bias +1, -1, +1, ... with channel 1 = -m (pinned_m).  t = 1.0: all +-1, so that the
+    normalised styles are exactly +-1 and mx is exactly a power of two.  ToRGB affines stay."""
+    out = {k: np.array(v, copy=True) for k, v in sd.items()}
+
+    def lock(b, co):
+        b[co % 4 == 1], b[co % 4 == 3] = 1e5, -1e5
+
+    for e in cs.entries(cfg):
+        if e.role == "conv_b" and not e.name.startswith("mapping."):
+            lock(out[e.name], np.arange(e.shape[0]))
+    lock(out["synthesis.b4.fc.bias"], np.arange(out["synthesis.b4.fc.bias"].shape[0]) // 16)
+    if styles is not None:
+        for p, _, _ in demodulated(cfg):
+            b = out[p + ".affine.bias"]
+            out[p + ".affine.weight"][...] = 0.0
+            b[0::2], b[1::2] = 1.0, -1.0
+            if styles != 1.0:
+                b[1] = -pinned_m(styles, b.shape[0])
+    return out
+
+
+def below_a_power_of_two(t):
+    return float(np.frexp(t)[0]) >= 0.75
+
+
+def dressed_premise(styles):
+    """What a dressed case claims to reach, on the oracle's float64 values and the dressed weights only.  -> the figures reached"""
+    def check(L):
+        cfg, sd, notes = L.cfg, L.sd[F64], {}
+        weakest = min(abs(float(sd[p + ".noise_strength"])) for p, _, _ in demodulated(cfg))
+        assert weakest >= MIN_NOISE_STRENGTH, ("this seed draws a noise strength the guards cannot see", weakest)
+        top = {}
+        for name in L.wants:
+            if name in ("mapping", "encoder.b4.fc") or name.endswith((".img", ".raw")):
+                continue
+            skipped = name == "synthesis.b4.fc" or (name.startswith("synthesis.") and name.endswith((".conv0", "->conv0")))
+            top[name] = 512.0 if skipped else 256.0
+        assert len(top) == 4 + 4 * len(resolutions(cfg)) + 1, sorted(top)
+        inside = {}
+        for name, tv in top.items():
+            w = L.wants[name]
+            assert bool((w == tv).any()) and bool((w == -tv).any()) and float(w.abs().max()) == tv, (name, tv, float(w.abs().max()))
+            # strictly inside the clamp: of the activation, so before the skip tensor is added where there is one
+            v = w if tv == 256.0 else L.fns[name](F64, "skip")[0]
+            inside[name] = float((v.abs() < 256.0).double().mean())
+            assert inside[name] >= 0.25, (name, "elements strictly inside the clamp", inside[name])
+        notes["least fraction inside the clamp"] = min(inside.values())
+        if styles is None:
+            return notes
+        rel, prod = [], {}
+        for p, widx, src in demodulated(cfg):
+            assert not sd[p + ".affine.weight"].any()
+            st = sd[p + ".affine.bias"]
+            mx = float((st * st.square().mean().rsqrt()).abs().max())
+            rel.append(abs(mx / styles - 1.0))
+            assert rel[-1] <= 2.0 ** -15, (p, mx, styles)
+            if p.endswith(".conv0"):
+                continue
+            sa = orc.modulated_factors(sd[p + ".weight"], L.styles(p, widx, F64))[0]
+            prod[p] = float((L.tap(src, F64) * sa.view(sa.shape[0], -1, 1, 1)).abs().max())
+            if below_a_power_of_two(styles):
+                assert 2.0 ** 15 * (1 - 2.0 ** -12) <= prod[p] < 2.0 ** 15, (p, prod[p])
+            else:
+                assert 2.0 ** 14 <= prod[p] <= 2.0 ** 14 * (1 + 2.0 ** -11), (p, prod[p])
+        notes["largest |mx / t - 1|"] = max(rel)
+        notes["|x * sa|max / 2^15, least and largest"] = (min(prod.values()) / 2.0 ** 15, max(prod.values()) / 2.0 ** 15)
+        return notes
+    return check
+
+
+MIN_NOISE_STRENGTH = 0.04
+HUGE_PIXELS = ((0, 1, 3, 5, np.inf), (1, 2, 9, 12, -np.inf), (2, 3, 15, 0, 3e38))      # (image, plane, row, column, value)
+
+
+def huge_premise(L):
+    """each huge pixel is +-256 in every channel behind FromRGB's clamp, and every unit's float64 value is finite"""
+    w = L.wants[f"encoder.b{L.cfg.resolution}.fromrgb"]
+    for b, _, iy, ix, _ in HUGE_PIXELS:
+        assert bool((w[b, :, iy, ix].abs() == 256.0).all()), (b, iy, ix)
+    assert float((w.abs() == 256.0).double().mean()) < 0.01
+    for name, v in L.wants.items():
+        assert bool(torch.isfinite(v).all()), name
+    return {}
+
+
+BELOW2, ABOVE2, BELOW4 = 2.0 * (1 - 2.0 ** -13), 2.0 * (1 + 2.0 ** -13), 4.0 * (1 - 2.0 ** -13)
+
+
+def _dressed(like, cfg, n, seed, styles, **kw):
+    src = CASES[like]
+    return _case(cfg, n, seed, env=src["env"], kernels=src["kernels"], dress=True, styles=styles, **kw)
+
+
+# Seeds: each dressed case takes the smallest seed above the previous case's at which every noise strength of its forward (drawn
+# N(0, 0.3^2), one per modulated layer of its resolution) is at least MIN_NOISE_STRENGTH; dressed_premise() asserts it.  The bound of
+# a dressed unit is relative to 512, so the noise guard needs a strength of about 0.03 to see the term, and every seventh draw is
+# smaller.  Skipped: 126, 128, 130, 132 (R16), 136-138, 140, 142, 143, 145 (R32), 147, 148 (R16).  r16_huge is not dressed: the next seed.
+CASES.update({
+    # two-plane operands on 64 columns: the clamp alone; mx exactly a power of two; mx just below and just above one, in two binades
+    "r16_dress": _dressed("r16_const", R16, 3, 125, None),
+    "r16_dress_t1": _dressed("r16_const", R16, 3, 127, 1.0),
+    "r16_dress_below2": _dressed("r16_const", R16, 3, 129, BELOW2),
+    "r16_dress_above2": _dressed("r16_const", R16, 3, 131, ABOVE2),
+    "r16_dress_below4": _dressed("r16_const", R16, 3, 133, BELOW4),
+    # the per-row noise epilogue on saturated values
+    "r16_dress_t1_random": _dressed("r16_random", R16, 3, 134, 1.0, random_noise=True),
+    # 256 columns, 16 x 16 tiles, accumulators in AGPRs
+    "r16_c256_mti4_dress_below2": _dressed("r16_c256_mti4", R16W, 1, 135, BELOW2),
+    # single-plane operands, and the fp16 loads and stores of +-512 and of saturated +-256
+    "r32_f16_dress": _dressed("r32_f16", R32, 2, 139, None, flags=(8, 8)),
+    "r32_f16_dress_below2": _dressed("r32_f16", R32, 2, 141, BELOW2, flags=(8, 8)),
+    "r32_f16_st_dress": _dressed("r32_f16_st", R32, 2, 144, None, flags=(8, 8), storage=True),
+    "r32_f16_st_dress_below2": _dressed("r32_f16_st", R32, 2, 146, BELOW2, flags=(8, 8), storage=True),
+    # the per-sample scale read through the three per-image-operand kernels of an S-samples forward
+    "r16_samples_dress_below2": _dressed("r16_samples", R16, 2, 149, BELOW2, samples=3),
+    # one +inf, one -inf and one 3e38 pixel, in different images: +-256 behind FromRGB's clamp, finite from there on
+    "r16_huge": _case(R16, 3, 150, kernels=CASES["r16_const"]["kernels"], huge=True),
+})
+
+
 def run_case(name, lib, mem, monkeypatch, report=None):
     c = CASES.get(name) or GPU_CASES[name]
     for k in ("COMODGAN_MTI", "COMODGAN_UP4", "COMODGAN_UP4_NT"):
@@ -649,6 +806,13 @@ def run_case(name, lib, mem, monkeypatch, report=None):
     x = pkg.synth.make_input(n, cfg.resolution, seed)
     if kw.pop("random_noise", False):
         kw.update(noise_mode="random", noise=pkg.synth.normal((n * s * noise_floats(cfg),), seed, "layer-noise").astype(np.float32))
+    if kw.pop("dress", False):
+        styles = kw.pop("styles")
+        sd, kw["premise"] = dress(cfg, sd, styles), dressed_premise(styles)
+    if kw.pop("huge", False):
+        for b, ch, iy, ix, v in HUGE_PIXELS:
+            x[b, ch, iy, ix] = v
+        kw["premise"] = huge_premise
     if kw.pop("bytes", False):
         from tests.comodgan_u8_case import make_u8
         kw["u8"], x = make_u8(n, cfg.resolution, seed), None
